@@ -13,14 +13,20 @@ With N GPUs every rank trains its own signal(s) (one model per signal, no collec
 
 `python bench.py --gpus N` starts its own one-process-per-GPU launcher when none is present.
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps and prints the line: metric, value, unit, ms_per_step, dtype, the workload's
+config.  `--dump-outputs DIR` writes what the last timed step computed -- its per-iteration losses and the trained weights,
+float32 -- as DIR/<name>.npy; the inputs are seeded, so runs with the same arguments are comparable output for output.
+
+With `--full` the run goes on behind the timed region, and the line also carries
   roofline         -- the kernel holding the largest share of the epoch, its algorithmic FLOPs per launch over its mean
                       duration measured with HIP events on the launch stream (hypad_profile_iteration);
   roofline_hbm     -- kernel-only GB/s of the row-wise Poincare-ball kernels (pre-allocated outputs, HIP events);
   roofline_scoring -- the same for every scoring kernel (fused test-loop forward, un-roll median, DTW, ...);
   secondary        -- BASELINE.json configs[2]'s per-GPU share: 8 signals per GPU;
   cpu_baseline     -- the CPU oracle (oracle/train_iters.py: the reference's nn.LSTM / autograd / Adam structure)
-                      timed on this node's host cores over a bounded sample of the same workload.
+                      timed on this node's host cores over a bounded sample of the same workload;
+and one figure for each of the other sections (euclidean, multivariate, signals32, drop_in, scoring, ...), every section whole
+in bench_detail.json.  The --no-* options and --strict act on this part.
 """
 import argparse
 import json
@@ -1075,6 +1081,33 @@ def emit(full, json_out, detail_path=None, final=True):
     json_out.flush()
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays, max_bytes=DUMP_MAX_BYTES):
+    """`--dump-outputs`: every array as <path>/<name>.npy in float32.  Above `max_bytes` in all, each array is cut to the same
+    fraction of its elements -- a fixed seeded sample of its flat indices, in order -- so two runs with the same arguments stay
+    comparable element for element."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    budget = max_bytes - 4096 * len(arrays)                  # (room for the .npy headers)
+    total = sum(a.nbytes for a in arrays.values())
+    for i, (name, a) in enumerate(arrays.items()):
+        if total > budget:
+            keep = np.random.default_rng(i).choice(a.size, a.size * budget // total, replace=False)
+            a = a.reshape(-1)[np.sort(keep)]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def _tear_down(dist):
+    if dist is not None:
+        try:
+            dist.barrier()
+            dist.destroy_process_group()
+        except Exception as e:                  # (the line is out: a failing tear-down is reported, not fatal)
+            print("process group tear-down: %s: %s" % (type(e).__name__, e), file=sys.stderr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1094,7 +1127,12 @@ def main():
                                                                       "a one-rank nccl group at --gpus 1)")
     ap.add_argument("--sharded-scoring", action="store_true", help="run that section at --gpus > 1 too (it is on by default at one GPU)")
     ap.add_argument("--detail", default=None, help="where every section goes whole (default: bench_detail.json in the working directory)")
+    ap.add_argument("--full", action="store_true", help="after the headline: per-kernel roofline, the other configurations, scoring, drop-in, "
+                                                        "CPU baseline and sharded sections (the --no-* / --strict options apply to these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed (losses, weights) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(args.gpus)
@@ -1142,18 +1180,65 @@ def main():
     eng.check_status()              # (a resident critic launch that gave up would have raised here: the timed epochs were complete)
     last = losses.float().mean(dim=(0, 1)).cpu().tolist()
     assert all(np.isfinite(last)), "training diverged"
+    ms_step = 1e3 * elapsed / args.steps
+    if args.dump_outputs:
+        # what a caller of the timed path holds after its last step: that epoch's per-iteration losses and the trained weights
+        # (the engine's flat per-signal arenas, include/hypad.h layout).  Every rank trains its own signals: one set per rank
+        tag = "" if world == 1 else ".rank%d" % rank
+        arrays = {"losses" + tag: losses.cpu().numpy()}
+        arrays.update({"weights_%s%s" % (k, tag): t.cpu().numpy() for k, t in eng.params.items()})
+        dump_outputs(args.dump_outputs, arrays)
+    n_it = N_CRITICS * N_BATCHES
+    persistent, producers = eng.critic_phase_persistent(), eng.critic_phase_producers(n_it)
+
+    # ---- the headline object: everything the contract asks for is known here.  A plain run prints it and ends; with --full, rank 0
+    # prints it NOW (a provisional last line) and again after the detail sections with their figures filled in: nothing that happens
+    # later -- a detail section that raises, hangs in a collective or takes the process down -- can cost the run its line (main.py:32-70
+    # is the loop these sections stand for)
+    out = None
+    if rank == 0:
+        windows = world * spg * N_BATCHES * B * args.steps
+        out = {
+            "metric": "training windows/sec (seq_len=100)",
+            "value": windows / elapsed,
+            "unit": "windows/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": ms_step,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f32",
+            "data": "synthetic",
+            "config": {"workload": (("configs[1]" if hyperbolic else "configs[0] on the GPU") + ": univariate synthetic (sine+noise+jump), hyperbolic=%s, batch=64, window=100, "
+                                    "latent=20, 1916 windows/signal, %d signal(s) per GPU; step = 1 epoch = 29 x "
+                                    "(5 critic_x + 5 critic_z + 1 decoder) iterations") % (hyperbolic, spg),
+                       "signals_per_gpu": spg, "iterations_per_step": (2 * N_CRITICS + 1) * N_BATCHES,
+                       "iteration_windows_per_s": windows * (2 * N_CRITICS + 1) / elapsed,
+                       "critic_phase": ("one resident launch per epoch (critic_persistent_kernel)" + (", records produced by that launch's own "
+                                        "producer workgroups" if producers else " behind a precompute launch")) if persistent else "one launch per iteration",
+                       "launch": "eager" if args.no_graph else "hipGraph replay of the captured epoch",
+                       "shuffles": "torch rand + argsort per epoch (host-driven)" if args.host_shuffle else
+                                   "drawn inside the epoch's launch sequence (hypad_epoch_shuffles)", "rccl_world_size": world,
+                       "critics_on_one_xcd": int(eng.counters[5])},        # placement census of the last resident critic launch (of 2 per signal)
+            "final_losses": {"loss": last[0], "aux": last[1]},
+        }
+    if not args.full:
+        if rank == 0:
+            emit(out, json_out, detail_path=args.detail)
+        _tear_down(dist)
+        return 0
 
     # ---- per-kernel durations, HIP events on the launch stream (same workload, after the timed region)
     prof = profile_kernels(eng, x, spg, device, cfg=cfg_main)
     mac_main = cfg_main.mac()
     per_launch, launches, epoch_share, dom = prof["per_launch"], prof["launches"], prof["epoch_share_ms"], prof["dominant"]
-    persistent, producers, n_it = prof["persistent"], prof["producers"], N_CRITICS * N_BATCHES
     flop = prof["flop_per_launch"][dom]                  # algorithmic FLOPs of ONE launch of the dominant kernel
     achieved = flop / (per_launch[dom] * 1e-3) / 1e12
     # the per-kernel times must add up to no more than the step they were taken from (+ the three small launches not listed:
     # shuffle, pack, decay): they are kernel times, not event-path times
     share_sum = float(sum(epoch_share.values()))
-    ms_step = 1e3 * elapsed / args.steps
     share_ok = share_sum <= 1.01 * ms_step
     if args.strict:
         assert share_ok, (share_sum, ms_step)
@@ -1249,54 +1334,23 @@ def main():
     except (OSError, KeyError, ValueError, NameError):
         pass
 
-    # ---- the headline object: everything the contract asks for is known here, so rank 0 prints it NOW (a provisional last line) and
-    # again after the detail sections with their figures filled in: nothing that happens later -- a detail section that raises, hangs
-    # in a collective or takes the process down -- can cost the run its line (main.py:32-70 is the loop these sections stand for)
     guard = RankGuard(dist, device, world)
-    out = None
     if rank == 0:
-        windows = world * spg * N_BATCHES * B * args.steps
-        out = {
-            "metric": "training windows/sec (seq_len=100)",
-            "value": windows / elapsed,
-            "unit": "windows/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": 1e3 * elapsed / args.steps,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic",
-            "config": {"workload": (("configs[1]" if hyperbolic else "configs[0] on the GPU") + ": univariate synthetic (sine+noise+jump), hyperbolic=%s, batch=64, window=100, "
-                                    "latent=20, 1916 windows/signal, %d signal(s) per GPU; step = 1 epoch = 29 x "
-                                    "(5 critic_x + 5 critic_z + 1 decoder) iterations") % (hyperbolic, spg),
-                       "signals_per_gpu": spg, "iterations_per_step": (2 * N_CRITICS + 1) * N_BATCHES,
-                       "iteration_windows_per_s": windows * (2 * N_CRITICS + 1) / elapsed,
-                       "critic_phase": ("one resident launch per epoch (critic_persistent_kernel)" + (", records produced by that launch's own "
-                                        "producer workgroups" if producers else " behind a precompute launch")) if persistent else "one launch per iteration",
-                       "launch": "eager" if args.no_graph else "hipGraph replay of the captured epoch",
-                       "shuffles": "torch rand + argsort per epoch (host-driven)" if args.host_shuffle else
-                                   "drawn inside the epoch's launch sequence (hypad_epoch_shuffles)", "rccl_world_size": world},
-            "roofline": {"bound": "mfma", "kernel": dom, "achieved": achieved, "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s",
-                         "frac": achieved / PEAK_F32_MFMA_TFLOPS, "traffic": traffic, "traffic_source": traffic_note,
-                         "traffic_algorithmic": traffic_algorithmic, "traffic_algorithmic_by_kernel": traffic_alg_all,
-                         "traffic_by_kernel": traffic_all,
-                         "traffic_ratio": (traffic / traffic_algorithmic) if traffic and traffic_algorithmic else None,
-                         "launch_ms": per_launch[dom], "launches_per_step": launches[dom],
-                         "iterations_per_launch": n_it if dom == "critic_persistent_kernel" else 1,
-                         "us_per_critic_iteration": 1e3 * prof["kern_ms"]["critic_iteration"],
-                         "kernel_ms": per_launch, "epoch_share_ms": epoch_share, "epoch_share_sum_ms": share_sum,
-                         "epoch_share_le_step": bool(share_ok), "flop_per_launch": flop,
-                         "flop_per_launch_parts": ({"critic_iterations": 2.0 * mac_main["critic_iteration"] * n_it * B * spg,
-                                                    "record_producers": 2.0 * (mac_main["critic_precompute"] if producers else 0) * n_it * B * spg}
-                                                   if dom == "critic_persistent_kernel" else None)},
-            "final_losses": {"loss": last[0], "aux": last[1]},
-        }
+        out["roofline"] = {"bound": "mfma", "kernel": dom, "achieved": achieved, "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s",
+                           "frac": achieved / PEAK_F32_MFMA_TFLOPS, "traffic": traffic, "traffic_source": traffic_note,
+                           "traffic_algorithmic": traffic_algorithmic, "traffic_algorithmic_by_kernel": traffic_alg_all,
+                           "traffic_by_kernel": traffic_all,
+                           "traffic_ratio": (traffic / traffic_algorithmic) if traffic and traffic_algorithmic else None,
+                           "launch_ms": per_launch[dom], "launches_per_step": launches[dom],
+                           "iterations_per_launch": n_it if dom == "critic_persistent_kernel" else 1,
+                           "us_per_critic_iteration": 1e3 * prof["kern_ms"]["critic_iteration"],
+                           "kernel_ms": per_launch, "epoch_share_ms": epoch_share, "epoch_share_sum_ms": share_sum,
+                           "epoch_share_le_step": bool(share_ok), "flop_per_launch": flop,
+                           "flop_per_launch_parts": ({"critic_iterations": 2.0 * mac_main["critic_iteration"] * n_it * B * spg,
+                                                      "record_producers": 2.0 * (mac_main["critic_precompute"] if producers else 0) * n_it * B * spg}
+                                                     if dom == "critic_persistent_kernel" else None)}
         if roofline_mfma is not None:
             out["roofline_mfma"] = roofline_mfma
-        out["config"]["critics_on_one_xcd"] = int(eng.counters[5])          # placement census of the last resident critic launch (of 2 per signal)
 
     def checkpoint(final=False):
         if rank == 0:
@@ -1377,12 +1431,7 @@ def main():
     if not args.no_sharded_scoring and not args.no_scoring and (world == 1 or args.sharded_scoring):
         put("scoring_sharded", guard.run(bench_scoring_sharded, device, world, rank))
     checkpoint(final=True)
-    if dist is not None:
-        try:
-            dist.barrier()
-            dist.destroy_process_group()
-        except Exception as e:                  # (the line is out: a failing tear-down is reported, not fatal)
-            print("process group tear-down: %s: %s" % (type(e).__name__, e), file=sys.stderr)
+    _tear_down(dist)
 
 
 if __name__ == "__main__":

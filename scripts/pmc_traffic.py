@@ -1,6 +1,6 @@
 """profiles/*_pmc_traffic.json from two rocprofv3 counter passes of bench.py:
 
-    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d out_f -o pmc -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-scoring
+    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d out_f -o pmc -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-scoring
     rocprofv3 --pmc WRITE_SIZE ...                               -d out_w ...
     python scripts/pmc_traffic.py out_f out_w > profiles/rNN_pmc_traffic.json
 
@@ -29,7 +29,7 @@ def medians(d, counter):
 fetch, write = medians(sys.argv[1], "FETCH_SIZE"), medians(sys.argv[2], "WRITE_SIZE")
 from hypad_amd.build import source_digest
 out = {"source_sha256": source_digest(),
-       "command": "rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE --kernel-trace --output-format csv -- python3 bench.py --steps 3 --warmup 1 "
+       "command": "rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE --kernel-trace --output-format csv -- python3 bench.py --full --steps 3 --warmup 1 "
                   "--no-cpu-baseline (two separate passes; scripts/pmc_traffic.py)",
        "correction": "hbm_bytes = (2*FETCH_SIZE + WRITE_SIZE) * 1024: FETCH_SIZE reads half of a wide coalesced read stream on gfx950 "
                      "(MI355X_MICROARCH.md, HBM)",

@@ -11,13 +11,13 @@ REPO=$(pwd)
 OUT=$REPO/gpurun_out/prof_r05
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-BENCH="python3 $REPO/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-secondary --no-drop-in --no-sharded-scoring --no-extra-configs"
+BENCH="python3 $REPO/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-secondary --no-drop-in --no-sharded-scoring --no-extra-configs"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- $BENCH > $OUT/bench_trace.json 2> $OUT/bench_trace.err
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/pmc_fetch -o pmc -- $BENCH > $OUT/bench_fetch.json 2> $OUT/bench_fetch.err
 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/pmc_write -o pmc -- $BENCH > $OUT/bench_write.json 2> $OUT/bench_write.err
 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $OUT/pmc_mfma -o pmc -- python3 $REPO/scripts/profile_mfma_target.py > $OUT/mfma_target.log 2> $OUT/mfma_target.err
 for n in 8 32; do
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_sig$n -o trace -- python3 $REPO/bench.py --steps 10 --warmup 3 --signals-per-gpu $n --no-graph --no-cpu-baseline --no-scoring --no-drop-in --no-extra-configs > $OUT/bench_sig$n.json 2> $OUT/bench_sig$n.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_sig$n -o trace -- python3 $REPO/bench.py --full --steps 10 --warmup 3 --signals-per-gpu $n --no-graph --no-cpu-baseline --no-scoring --no-drop-in --no-extra-configs > $OUT/bench_sig$n.json 2> $OUT/bench_sig$n.err
   f=$(find $OUT/trace_sig$n -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && head -30 "$f" > $OUT/r05_signals${n}_kernel_stats.csv
 done
 cd $REPO

@@ -65,3 +65,48 @@ def test_emit_writes_detail_file_sections_to_stderr_and_one_stdout_line(tmp_path
     names = [next(iter(json.loads(ln))) for ln in err if ln.startswith("{")]
     assert "secondary" in names and "roofline" in names and "cpu_baseline" in names
     assert capsys.readouterr().out == ""
+
+
+def test_dump_outputs_writes_float32_npy_and_samples_the_same_elements_above_the_cap(tmp_path):
+    import numpy as np
+    small = {"losses": np.arange(12, dtype=np.float32).reshape(1, 3, 4), "weights_enc": np.linspace(0, 1, 7)}
+    bench.dump_outputs(str(tmp_path / "a"), small)
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in small}
+    for n, a in small.items():
+        assert got[n].dtype == np.float32 and np.array_equal(got[n], a.astype(np.float32))
+    big = {"x": np.random.default_rng(0).standard_normal(300_000).astype(np.float32), "y": np.arange(50_000, dtype=np.float32)}
+    cap = 512 * 1024
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), big, max_bytes=cap)
+    files = sorted(os.listdir(tmp_path / "b"))
+    assert files == ["x.npy", "y.npy"]
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in files) <= cap
+    y = np.load(tmp_path / "b" / "y.npy")
+    assert 0 < y.size < 50_000 and np.all(np.diff(y) > 0)             # a sample of the flat elements, in order
+    for f in files:                                                  # the same sample every time
+        assert np.array_equal(np.load(tmp_path / "b" / f), np.load(tmp_path / "c" / f))
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_line_and_dumps_the_last_step(tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR` without --full: one stdout line with the contract's keys and no detail sections;
+    the last timed epoch's losses and weights in DIR as float32."""
+    import subprocess
+    import numpy as np
+    dump = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(dump)],
+                       cwd=str(tmp_path), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = r.stdout.splitlines()
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and "provisional" not in d
+    assert abs(d["value"] - 29 * 64 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    assert "roofline" not in d and not d["also_windows_per_s"]
+    losses = np.load(dump / "losses.npy")
+    assert losses.dtype == np.float32 and losses.shape == (1, 11 * 29, 4) and np.isfinite(losses).all()
+    for net in ("enc", "dec", "cx", "cz"):
+        w = np.load(dump / ("weights_%s.npy" % net))
+        assert w.dtype == np.float32 and w.ndim == 2 and w.shape[0] == 1 and np.isfinite(w).all()
