@@ -182,6 +182,14 @@ _SIGS = {
     "hypad_critic_score": (c_int, [P, P, c_int64, P, c_size_t, P]),
     "hypad_row_norms": (c_int, [P, P, c_int64, c_int, P]),
     "hypad_combine_scores": (c_int, [c_int, P, P, P, P, c_int64, P]),
+    "hypad_score_signals_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "hypad_score_forward_signals": (c_int, [P, P, P, c_int, POINTER(c_int64), POINTER(c_int64), P, c_int64, P, P, P, P, P, c_int, c_int, c_int,
+                                            c_void_p, c_size_t, P]),
+    "hypad_score_signals_tiles": (c_int, [c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int), POINTER(c_int64)]),
+    "hypad_kde_mode_signals": (c_int, [P, P, c_int, POINTER(c_int64), c_int, P]),
+    "hypad_critic_score_signals_workspace_bytes": (c_size_t, [c_int, POINTER(c_int64), c_int]),
+    "hypad_critic_score_signals": (c_int, [P, P, c_int, POINTER(c_int64), c_int, P, c_size_t, P]),
+    "hypad_combine_scores_signals": (c_int, [c_int, P, P, P, P, c_int, POINTER(c_int64), c_int, P]),
 }
 EXPORTS = tuple(_SIGS)
 for _name, (_res, _args) in _SIGS.items():
@@ -212,6 +220,12 @@ def check(rc, what=""):
     if rc != 0:
         msg = lib.hypad_error_string(int(rc))
         raise HypadError(f"{what or 'hypad call'} failed: {msg.decode() if msg else rc} ({rc})")
+
+
+def int64s(values):
+    """A host int64 array for the offset arguments of the signal-group entry points (row_off, x_off)."""
+    vals = [int(v) for v in values]
+    return (c_int64 * max(len(vals), 1))(*vals)
 
 
 def ptr(t):

@@ -140,3 +140,70 @@ def _to_host(tensors):
         out[k].copy_(t, non_blocking=True)
     torch.cuda.current_stream().synchronize()
     return {k: v.numpy() for k, v in out.items()}
+
+
+def signal_offsets(counts):
+    """Windows per signal -> row_off (n + 1,): signal s owns rows row_off[s] .. row_off[s + 1] of the grouped outputs."""
+    off = [0]
+    for c in counts:
+        if int(c) < 1:
+            raise ValueError("every signal of a group needs at least one window")
+        off.append(off[-1] + int(c))
+    return off
+
+
+def tile_plan(row_off, signal_shape, latent_dim):
+    """(windows per tile, tiles) of the grouped forward launch for these offsets (hypad_score_signals_tiles)."""
+    import ctypes
+    rows, tiles = ctypes.c_int(), ctypes.c_int64()
+    _C.check(_C.lib.hypad_score_signals_tiles(int(signal_shape), int(latent_dim), len(row_off) - 1, _C.int64s(row_off),
+                                              ctypes.byref(rows), ctypes.byref(tiles)), "score_signals_tiles")
+    return rows.value, tiles.value
+
+
+def _stacked_arenas(models):
+    """(enc, dec, cx) as (n_signals, param_count) device tensors: an Engine's own arenas, or the modules' arenas stacked."""
+    if hasattr(models, "params") and isinstance(getattr(models, "params"), dict):
+        return tuple(models.params[k].contiguous() for k in ("enc", "dec", "cx"))
+    return tuple(torch.stack([m[i].arena() for m in models]) for i in range(3))
+
+
+def score_signals(x_list, models, signal_shape, latent_dim, hyperbolic):
+    """The test-loop forward (score_windows) of many trained models at once: one pack launch for all of them, one critic launch and one
+    forward launch (per 64 signals) over their ragged windows (hypad_score_forward_signals).
+    x_list: per signal a SignalDataset (its windows in the series view, as score_batches reads them) or an (N, S[, 1]) window array;
+    models: [(encoder, decoder, critic_x)] per signal, or an Engine (its arenas as they are).  Signal s's rows of every output are
+    those of score_windows on that signal alone, bit for bit.
+    Returns dict(recons, eucl, hyper_real, critic, rowdist: device tensors concatenated in signal order (None where the mode has
+    none), row_off: [0, n_0, n_0 + n_1, ...])."""
+    S, L, hyp = int(signal_shape), int(latent_dim), bool(hyperbolic)
+    enc, dec, cx = _stacked_arenas(models)
+    n_sig = len(x_list)
+    if enc.shape[0] != n_sig:
+        raise ValueError(f"{n_sig} signals, {enc.shape[0]} models")
+    views = [x.series_windows() if hasattr(x, "series_windows") else None for x in x_list]
+    if all(v is not None for v in views):
+        # the series view: signal s's T_s + S - 1 scaled values, back to back; window n of signal s at x_off[s] + n
+        counts = [v[1] for v in views]
+        parts = [v[0][: c + S - 1] for v, c in zip(views, counts)]
+        stride = 1
+    else:
+        mats = [torch.as_tensor(np.asarray(x.X)) if hasattr(x, "X") else torch.as_tensor(x) for x in x_list]
+        parts = [m.reshape(len(m), -1) for m in mats]
+        if any(p.shape[1] != S for p in parts):
+            raise ValueError(f"windows must be (N, {S}[, 1])")
+        counts = [p.shape[0] for p in parts]
+        stride = S
+    row_off = signal_offsets(counts)
+    x_off = np.cumsum([0] + [p.numel() for p in parts])[:-1].tolist()
+    x = torch.cat([p.reshape(-1).to("cuda", torch.float32) for p in parts]).contiguous()
+    n = row_off[-1]
+    new = lambda *s: torch.empty(*s, device="cuda", dtype=torch.float32)
+    eucl, critic = new(n, S), new(n)
+    hyper, hreal, dist = (new(n, S), new(n, S), new(n)) if hyp else (None, None, None)
+    ws_bytes = _C.lib.hypad_score_signals_workspace_bytes(S, L, int(hyp), n_sig)
+    ws = torch.empty(max(ws_bytes // 4, 1), dtype=torch.float32, device="cuda")
+    _C.check(_C.lib.hypad_score_forward_signals(_C.ptr(enc), _C.ptr(dec), _C.ptr(cx), n_sig, _C.int64s(row_off), _C.int64s(x_off), _C.ptr(x),
+                                                stride, _C.ptr(hyper), _C.ptr(eucl), _C.ptr(hreal), _C.ptr(critic), _C.ptr(dist), S, L, int(hyp),
+                                                ws.data_ptr(), ws_bytes, _C.stream()), "score_forward_signals")
+    return {"recons": hyper if hyp else eucl, "eucl": eucl, "hyper_real": hreal, "critic": critic, "rowdist": dist, "row_off": row_off}

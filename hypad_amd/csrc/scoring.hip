@@ -2,6 +2,7 @@
 // Post-processing arithmetic is fp64 because the reference computes it in NumPy/pandas fp64.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <type_traits>
@@ -1107,6 +1108,43 @@ __global__ __launch_bounds__(THREADS) void combine_kernel(int mode, const double
   }
 }
 
+// ------------------------------------------------------------------------------------------------ signal groups
+// Segmented combine (hypad_combine_scores_signals): grid (blocks, segments of the launch); segment blockIdx.y (a scalar) writes its rows
+// row_off[s] .. row_off[s + 1] from critic scores that start at row_off[s] + s * (window - 1) -- each segment's critic scores are
+// the n_s + window - 1 timesteps of its own final_critic_scores.  Per element combine_kernel's arithmetic.
+constexpr int SEG_CHUNK = 64;
+struct SegTable { int n, seg0; int64_t off[SEG_CHUNK + 1]; };
+__global__ __launch_bounds__(THREADS) void combine_signals_kernel(int mode, const double* __restrict__ c, const double* __restrict__ r,
+                                                                   const double* __restrict__ u, double* __restrict__ out, SegTable t, int window) {
+  const int sl = blockIdx.y;
+  const int64_t o = t.off[sl], n = t.off[sl + 1] - o, co = o + (int64_t)(t.seg0 + sl) * (window - 1);
+  for (int64_t i = (int64_t)blockIdx.x * THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * THREADS) {
+    double cv = c ? c[co + i] : 0.0, rv = r ? r[o + i] : 0.0, uv = u ? u[o + i] : 0.0, v;
+    switch (mode) {
+      case HYPAD_COMB_SUM: v = 0.2 * cv + 0.8 * rv; break;
+      case HYPAD_COMB_MULT: v = cv * rv; break;
+      case HYPAD_COMB_UNCERTAINTY: v = cv * rv * uv; break;
+      case HYPAD_COMB_CRITIC: v = cv; break;
+      case HYPAD_COMB_CRITIC_UNCERTAINTY: v = cv * uv; break;
+      case HYPAD_COMB_SUM_UNCERTAINTY: v = 0.5 * cv * uv + 0.5 * rv * uv; break;
+      case HYPAD_COMB_REC: v = rv; break;
+      case HYPAD_COMB_REC_UNCERTAINTY: v = rv * uv; break;
+      case HYPAD_COMB_EUCL_MULT: v = cv * rv; break;
+      default: v = 0.5 * (cv - 1.0) + 0.5 * (rv - 1.0); break;   // HYPAD_COMB_EUCL_SUM, lambda_rec = 0.5
+    }
+    out[o + i] = v;
+  }
+}
+__global__ __launch_bounds__(THREADS) void fill_nan_kernel(double* __restrict__ out, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * THREADS) out[i] = __builtin_nan("");
+}
+// offsets of a group: row_off[0] = 0, every segment > 0 rows
+int seg_check(int n_signals, const int64_t* row_off) {
+  if (n_signals < 1 || !row_off || row_off[0] != 0) return HYPAD_EINVAL;
+  for (int i = 0; i < n_signals; ++i) if (row_off[i + 1] <= row_off[i]) return HYPAD_EINVAL;
+  return HYPAD_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1289,6 +1327,66 @@ int hypad_combine_scores(int mode, const double* c, const double* r, const doubl
   if (n == 0) return HYPAD_OK;
   hipLaunchKernelGGL(combine_kernel, dim3(grid_for(n, THREADS)), dim3(THREADS), 0, (hipStream_t)s, mode, c, r, u, out, n);
   HYPAD_CHECK_LAUNCH();
+  return HYPAD_OK;
+}
+
+int hypad_kde_mode_signals(const float* critic, double* modes, int n_signals, const int64_t* row_off, int window, hypad_stream_t s) {
+  int rc = seg_check(n_signals, row_off);
+  if (rc) return rc;
+  if (!critic || !modes || window <= 0) return HYPAD_EINVAL;
+  if (window > MAX_WINDOW) return HYPAD_EUNSUPPORTED;
+  for (int i = 0; i < n_signals && !rc; ++i)          // (each segment as hypad_kde_mode partitions it: the same modes bit for bit)
+    rc = hypad_kde_mode(critic + row_off[i], modes + row_off[i] + (int64_t)i * (window - 1), row_off[i + 1] - row_off[i], window, s);
+  return rc;
+}
+// workspace: [critic_score's | rolling mean's for the longest segment | the unsmoothed scores of all segments]
+static size_t seg_roll_bytes(int n_signals, const int64_t* row_off, int window) {
+  int64_t t = 0;
+  for (int i = 0; i < n_signals; ++i) t = std::max<int64_t>(t, row_off[i + 1] - row_off[i] + window - 1);
+  return (hypad_rolling_workspace_bytes(t) + 255) & ~(size_t)255;
+}
+size_t hypad_critic_score_signals_workspace_bytes(int n_signals, const int64_t* row_off, int window) {
+  if (seg_check(n_signals, row_off) || window <= 0) return 0;
+  const size_t head = (hypad_critic_score_workspace_bytes() + 255) & ~(size_t)255;
+  return head + seg_roll_bytes(n_signals, row_off, window) + (size_t)(row_off[n_signals] + (int64_t)n_signals * (window - 1)) * sizeof(double);
+}
+int hypad_critic_score_signals(const double* modes, double* out, int n_signals, const int64_t* row_off, int window, void* workspace,
+                               size_t workspace_bytes, hypad_stream_t s) {
+  int rc = seg_check(n_signals, row_off);
+  if (rc) return rc;
+  if (!modes || !out || window <= 0) return HYPAD_EINVAL;
+  if (!workspace || workspace_bytes < hypad_critic_score_signals_workspace_bytes(n_signals, row_off, window)) return HYPAD_EWORKSPACE;
+  const size_t head = (hypad_critic_score_workspace_bytes() + 255) & ~(size_t)255, roll = seg_roll_bytes(n_signals, row_off, window);
+  char* ws = (char*)workspace;
+  double* tmp = (double*)(ws + head + roll);
+  for (int i = 0; i < n_signals && !rc; ++i) {
+    const int64_t n = row_off[i + 1] - row_off[i], t = n + window - 1, o = row_off[i] + (int64_t)i * (window - 1);
+    rc = hypad_critic_score(modes + o, tmp + o, t, ws, head, s);
+    if (rc) break;
+    const int w = (int)std::trunc((double)n * 0.01);       // final_critic_scores :404: math.trunc(n * 0.01), the segment's own n
+    if (w == 0) {                                            // pandas' rolling(0): all NaN (hypad_amd rolling_mean)
+      hipLaunchKernelGGL(fill_nan_kernel, dim3(grid_for(t, THREADS)), dim3(THREADS), 0, (hipStream_t)s, out + o, t);
+      HYPAD_CHECK_LAUNCH();
+    } else {
+      rc = hypad_rolling_mean(tmp + o, nullptr, out + o, t, w, 0, ws + head, roll, s);
+    }
+  }
+  return rc;
+}
+int hypad_combine_scores_signals(int mode, const double* c, const double* r, const double* u, double* out, int n_signals, const int64_t* row_off,
+                                 int window, hypad_stream_t s) {
+  int rc = seg_check(n_signals, row_off);
+  if (rc) return rc;
+  if (!out || window <= 0 || mode < 0 || mode > HYPAD_COMB_EUCL_SUM) return HYPAD_EINVAL;
+  for (int c0 = 0; c0 < n_signals; c0 += SEG_CHUNK) {        // (SEG_CHUNK segments per launch: the table is a kernel argument)
+    SegTable t{};
+    t.n = std::min(SEG_CHUNK, n_signals - c0); t.seg0 = c0;
+    int64_t most = 0;
+    for (int i = 0; i <= t.n; ++i) t.off[i] = row_off[c0 + i];
+    for (int i = 0; i < t.n; ++i) most = std::max<int64_t>(most, t.off[i + 1] - t.off[i]);
+    hipLaunchKernelGGL(combine_signals_kernel, dim3(grid_for(most, THREADS), (unsigned)t.n), dim3(THREADS), 0, (hipStream_t)s, mode, c, r, u, out, t, window);
+    HYPAD_CHECK_LAUNCH();
+  }
   return HYPAD_OK;
 }
 

@@ -74,10 +74,13 @@ def _detect(params, test_dataset, read_path, encoder, decoder, critic_x, path, d
     return out
 
 
-def run_signals(params, names, config_path=None, data_dir="./data", log=print):
+def run_signals(params, names, config_path=None, data_dir="./data", log=print, grouped_scoring=True):
     """One model per signal for a list of signals (``--signals a,b,c``): datasets -> ``train.train_signals_resident`` (groups of up
-    to 32 models per launch sequence; under ``torchrun`` the signals are sharded over the ranks, one process per GPU) -> per
-    signal the test loop and the detector on the rank that trained it -> the metrics of all signals gathered on every rank."""
+    to 32 models per launch sequence; under ``torchrun`` the signals are sharded over the ranks, one process per GPU) -> the test
+    loop and the detector on the rank that trained each signal -> the metrics of all signals gathered on every rank.
+    ``grouped_scoring`` (default): the signals this rank trained are scored together (_detect_grouped: one grouped forward, the
+    hyperbolic critic chain per segment, one copy back), with the same numbers and artefacts as the per-signal ``_detect`` loop
+    (``grouped_scoring=False``, ``--per-signal-scoring``)."""
     import copy
 
     from . import parallel as par
@@ -90,17 +93,96 @@ def run_signals(params, names, config_path=None, data_dir="./data", log=print):
         sets.append((p,) + tuple(od.dataset_selection(p, data_dir)))
     trained = ht.train_signals_resident([t[1] for t in sets], params, names=names, log=log)
     local = {}
+    group = [(t, name) for t, name in zip(sets, names) if trained[name].get("modules") is not None and _groupable(t, trained[name]["path"])]
+    outs = _detect_grouped(group, trained, data_dir, log) if grouped_scoring and group else {}
     for (p, train_ds, test_ds, read_path), name in zip(sets, names):
         mods = trained[name].get("modules")
         if mods is None:
             continue                                   # another rank's signal
         p.latent_space_dim = 20
-        out = _detect(p, test_ds, read_path, mods[0], mods[1], mods[2], trained[name]["path"], data_dir, hasattr(train_ds, "device_windows"), log)
+        out = outs.get(name)
+        if out is None:
+            out = _detect(p, test_ds, read_path, mods[0], mods[1], mods[2], trained[name]["path"], data_dir, hasattr(train_ds, "device_windows"), log)
         # (tn is None in the overlap-segment count)
         local[name] = {"confusion": [None if v is None else int(v) for v in out.get("confusion", [])] or None, "metrics": out.get("metrics"),
                        "n_intervals": int(len(out["intervals"])), "final": trained[name]["final"], "path": trained[name]["path"],
                        "rank": trained[name]["rank"]}
     return par.gather_signal_metrics(local)
+
+
+def _groupable(t, path):
+    """A signal _detect_grouped scores: univariate, in the series view, and without a critic_scores.pickle that ``params.load`` would
+    read back (those take _detect)."""
+    import os
+    p, train_ds, test_ds, _ = t
+    if hasattr(train_ds, "device_windows") or p.signal == "multivariate" or not hasattr(test_ds, "series_windows"):
+        return False
+    if getattr(p, "load", False) and path and os.path.exists(os.path.join(path, "critic_scores.pickle")):
+        return False
+    return test_ds.series_windows("cpu") is not None and len(test_ds.X) > 0
+
+
+def _detect_grouped(group, trained, data_dir, log):
+    """_detect for several trained signals at once: one score_signals call (pack, critic and forward launches for all of them), for
+    hyperbolic models hyperbolic_scores_signals, everything back in one page-locked copy and one wait; then per signal on the host
+    the cache files test_tadgan writes, critic_scores.pickle, and detect_intervals (anomalies.csv, counts, metrics, results row) --
+    the same contents as _detect's.  Euclidean models: the grouped forward, then univariate_anomaly_detection per signal."""
+    import pickle
+
+    import pandas as pd
+    import torch
+
+    from . import anomaly_detection
+    from .utils import anomaly_detection_utils as adu
+    from .utils import data as od
+    P0 = group[0][0][0]
+    hyp = bool(P0.hyperbolic)
+    S, L = int(P0.signal_shape), 20
+    models = [tuple(trained[name]["modules"][:3]) for _, name in group]
+    res = anomaly_detection.score_signals([t[2] for t, _ in group], models, S, L, hyp)
+    row_off = res["row_off"]
+    want = {"recons": res["recons"], "critic": res["critic"]}
+    if hyp:
+        want.update(hyper_real=res["hyper_real"], eucl=res["eucl"])
+        comb = adu.hyperbolic_scores_signals(res, P0.combination)
+        want["final"] = comb["final_scores"]
+        if comb["critic_scores"] is not None:
+            want["critic_scores"] = comb["critic_scores"]
+    host = anomaly_detection._to_host(want)
+    outs = {}
+    for k, ((p, _, test_ds, read_path), name) in enumerate(group):
+        a, b = row_off[k], row_off[k + 1]
+        raw = trained[name]["path"]                           # (the detector's files are named raw + file, as _detect names them)
+        path = raw + "/" if raw else ""
+        recons_signal = host["recons"][a:b]
+        gt_signal = np.asarray(test_ds.X)
+        critic_score = list(host["critic"][a:b])
+        true_signal = host["hyper_real"][a:b] if hyp else gt_signal
+        if path:
+            torch.save(recons_signal, path + "recons_signal.pt")
+            torch.save(gt_signal, path + "gt_signal.pt")
+            torch.save(critic_score, path + "critic_score.pt")
+            if hyp:
+                torch.save(host["eucl"][a:b], path + "eucl_recons.pt")
+                torch.save(true_signal, path + "real_hyper.pt")
+        if p.dataset in ("A1", "A2", "A3", "A4"):
+            known = pd.read_csv(read_path[:-4] + "_known_anomalies.csv")
+        else:
+            known = od.load_anomalies(p.signal, data_dir=data_dir)
+        if hyp:
+            if raw and "critic_scores" in host:                # (compute_critic_scores' cache, the signal's whole segment)
+                with open(raw + "critic_scores.pickle", "wb") as f:
+                    pickle.dump(host["critic_scores"][a + k * (S - 1): b + (k + 1) * (S - 1)], f, protocol=pickle.HIGHEST_PROTOCOL)
+            out = adu.detect_intervals(host["final"][a:b], p, raw, _true_index(test_ds, p), known, p.signal)
+        else:
+            out = adu.univariate_anomaly_detection(recons_signal, true_signal, p, p.combination, critic_score, raw, read_path, p.rec_error,
+                                                   _true_index(test_ds, p), known, p.signal, p.signal_shape)
+        log("predicted intervals:\n{}".format(out["intervals"]))
+        log("tn, fp, fn, tp: {}".format(out["confusion"]))
+        if out["metrics"]:
+            log("precision: {precision}, recall: {recall}\nf1_score: {f1}, gmean: {gmean}".format(**out["metrics"]))
+        outs[name] = out
+    return outs
 
 
 def _true_index(test_dataset, params):
@@ -121,6 +203,8 @@ def main(argv=None):
     ap.add_argument("--signals", type=str, default=None, help="comma-separated signal names of params.dataset: one model per signal, trained side by "
                                                                "side in groups of up to 32 per GPU (train.train_signals_resident); under torchrun the "
                                                                "signals are sharded over the ranks")
+    ap.add_argument("--per-signal-scoring", action="store_true", help="with --signals: score the trained signals one by one (the test loop "
+                                                                         "and the detector per signal) instead of as one group")
     args = ap.parse_args(argv)
     params = SimpleNamespace(**yaml.load(open(args.config), Loader=yaml.FullLoader))
     if args.signals:
@@ -133,7 +217,8 @@ def main(argv=None):
             dist.init_process_group("nccl", device_id=torch.device("cuda", torch.cuda.current_device()))
             own_group = True
         try:
-            res = run_signals(params, [n.strip() for n in args.signals.split(",") if n.strip()], args.config, args.data_dir)
+            res = run_signals(params, [n.strip() for n in args.signals.split(",") if n.strip()], args.config, args.data_dir,
+                              grouped_scoring=not args.per_signal_scoring)
         finally:
             if own_group:
                 dist.destroy_process_group()

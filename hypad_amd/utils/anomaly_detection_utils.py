@@ -377,6 +377,12 @@ def univariate_anomaly_detection(recons_signal, true_signal, params, combination
                                                          rec_error_type=rec_error_type, comb=combination, path=path, with_true=False)
     else:
         final_scores = hyperbolic_scores(recons_signal, true_signal, critic_score, params.signal_shape, combination, params, path)
+    return detect_intervals(final_scores, params, path, true_index, known_anomalies, signal)
+
+
+def detect_intervals(final_scores, params, path=None, true_index=None, known_anomalies=None, signal=None):
+    """The host tail of univariate_anomaly_detection (:87-127) from the final scores on: intervals, ``anomalies.csv``, the
+    overlap-segment counts and metrics, the results table row."""
     final_scores = np.asarray(final_scores, dtype=np.float64).reshape(-1)
     if true_index is None:
         true_index = np.arange(final_scores.size)
@@ -426,3 +432,37 @@ def multivariate_anomaly_detection(recons_signal, true_signal, params, combinati
         if out["intervals"].shape[0] and len(known):
             out["metrics"] = compute_metrics(known, [(r[0], r[1]) for r in out["intervals"]], verbose=False)
     return out
+
+
+def hyperbolic_scores_signals(res, combination="mult"):
+    """hyperbolic_scores for every signal of a score_signals result at once (no cache files): the row-wise Poincare distance over all
+    rows, per signal the KDE modes of its critic values (hypad_kde_mode_signals), its quantile-trimmed |z| + 1 and its own centred
+    rolling mean (hypad_critic_score_signals), then the combination (hypad_combine_scores_signals) -- each signal's numbers those of
+    hyperbolic_scores on it alone, bit for bit, nothing through the host.
+    Returns dict(final_scores (sum n_s,) fp64, critic_scores (sum (n_s + S - 1),) fp64 or None -- signal s's final_critic_scores at
+    row_off[s] + s (S - 1) --, row_off) on the device."""
+    if combination not in ("sum", "mult", "uncertainty", "critic", "critic_uncertainty", "sum_uncertainty", "rec", "rec_uncertainty"):
+        raise ValueError(combination)
+    row_off = [int(v) for v in res["row_off"]]
+    k = len(row_off) - 1
+    recons, real = res["recons"], res["hyper_real"]
+    if real is None:
+        raise ValueError("hyperbolic_scores_signals needs a hyperbolic score_signals result")
+    w = recons.shape[1]
+    offs = _C.int64s(row_off)
+    rec = gmath.poincare_rowdist(_f32(real), _f32(recons))
+    rec = rec if rec.dtype == torch.float64 else rec.to(torch.float64)
+    critic_scores = None
+    if combination in ("mult", "uncertainty", "sum", "sum_uncertainty", "critic", "critic_uncertainty"):
+        modes = torch.empty(row_off[-1] + k * (w - 1), device=recons.device, dtype=torch.float64)
+        _C.check(_C.lib.hypad_kde_mode_signals(_C.ptr(_f32(res["critic"]).reshape(-1)), _C.ptr(modes), k, offs, w, _C.stream()), "kde_mode_signals")
+        critic_scores = torch.empty_like(modes)
+        nbytes = _C.lib.hypad_critic_score_signals_workspace_bytes(k, offs, w)
+        ws = _scratch(modes.device, nbytes, "critic_score_signals")
+        _C.check(_C.lib.hypad_critic_score_signals(_C.ptr(modes), _C.ptr(critic_scores), k, offs, w, ws.data_ptr(), nbytes, _C.stream()),
+                 "critic_score_signals")
+    u = row_norms(recons) if "uncertainty" in combination else None
+    out = torch.empty(row_off[-1], device=recons.device, dtype=torch.float64)
+    _C.check(_C.lib.hypad_combine_scores_signals(_C.COMB[combination], _C.ptr(critic_scores), _C.ptr(rec), _C.ptr(u), _C.ptr(out), k, offs, w,
+                                                 _C.stream()), "combine_signals")
+    return {"final_scores": out, "critic_scores": critic_scores, "row_off": row_off}

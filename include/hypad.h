@@ -523,6 +523,42 @@ enum { HYPAD_COMB_SUM = 0, HYPAD_COMB_MULT = 1, HYPAD_COMB_UNCERTAINTY = 2, HYPA
 int hypad_combine_scores(int combination, const double* critic_scores, const double* rec_scores,
                          const double* uncertainty, double* out, int64_t n, hypad_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Signal groups: the test loop and the critic-score chain of many trained models at once (the per-signal
+ * anomaly_detection.py:20-155 + utils/anomaly_detection_utils.py:54-86, :336-404 of a dataset run, one model per signal).
+ * row_off (n_signals + 1) and x_off (n_signals) are HOST int64 arrays: the launch plan is taken from them and they travel in the
+ * kernel arguments.  row_off[0] = 0 and every signal has at least one window, else HYPAD_EINVAL without any launch.
+ * ---------------------------------------------------------------------------------------------- */
+/* hypad_score_forward_packed for n_signals models: enc / dec / cx are stacked arenas, (n_signals, hypad_param_count(net, ...))
+ * each (hypad_amd Engine.params).  Signal s has windows row_off[s] .. row_off[s + 1]; its window n is x[x_off[s] + n * x_row_stride ..]
+ * (x_row_stride 0 / S: window matrix, 1: the signal's scaled series).  Outputs as hypad_score_forward_packed's, concatenated in row
+ * order, each optional.  One pack launch for all signals, then per 64 signals one critic launch and one forward launch whose tiles
+ * never straddle two signals.  The tile form (16 or 32 windows) follows from row_off[n_signals] as hypad_score_forward_packed's
+ * from its `rows`; every signal's rows equal a hypad_score_forward_packed call on that signal alone, bit for bit.
+ * workspace: hypad_score_signals_workspace_bytes(S, L, hyperbolic, n_signals). */
+size_t hypad_score_signals_workspace_bytes(int signal_shape, int latent_dim, int hyperbolic, int n_signals);
+int hypad_score_forward_signals(const float* enc, const float* dec, const float* cx, int n_signals, const int64_t* row_off,
+                                const int64_t* x_off, const float* x, int64_t x_row_stride, float* hyper, float* eucl,
+                                float* hyper_real, float* critic, float* rowdist, int signal_shape, int latent_dim, int hyperbolic,
+                                void* workspace, size_t workspace_bytes, hypad_stream_t stream);
+/* The forward launch's plan for such a group: windows per tile (16 or 32) and the number of tiles. */
+int hypad_score_signals_tiles(int signal_shape, int latent_dim, int n_signals, const int64_t* row_off, int* rows_per_tile, int64_t* tiles);
+/* final_critic_scores :365-404 per signal, KDE step: segment s of `modes` (row_off[s] + s (window - 1), n_s + window - 1 fp64)
+ * is hypad_kde_mode of critic[row_off[s] .. row_off[s + 1]). */
+int hypad_kde_mode_signals(const float* critic, double* modes, int n_signals, const int64_t* row_off, int window, hypad_stream_t stream);
+/* final_critic_scores :365-404 per signal, the rest (_compute_critic_score :307-333): per segment of `modes` (layout as above)
+ * hypad_critic_score, then the centred rolling mean with the signal's own window trunc(n_s * 0.01) -- all NaN where that is 0, as
+ * pandas gives.  Each segment is reduced with the single-signal partition: the same bits as the per-signal calls.
+ * workspace: hypad_critic_score_signals_workspace_bytes(n_signals, row_off, window). */
+size_t hypad_critic_score_signals_workspace_bytes(int n_signals, const int64_t* row_off, int window);
+int hypad_critic_score_signals(const double* modes, double* out, int n_signals, const int64_t* row_off, int window, void* workspace,
+                               size_t workspace_bytes, hypad_stream_t stream);
+/* combine_scores :336-362 per signal: out[row_off[s] + i] from critic_scores[row_off[s] + s (window - 1) + i] (the first n_s of the
+ * signal's final_critic_scores), rec_scores[row_off[s] + i] and uncertainty[row_off[s] + i]; any input may be NULL as for
+ * hypad_combine_scores.  One launch per 64 signals. */
+int hypad_combine_scores_signals(int combination, const double* critic_scores, const double* rec_scores, const double* uncertainty,
+                                 double* out, int n_signals, const int64_t* row_off, int window, hypad_stream_t stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -1,0 +1,89 @@
+"""Scoring a group of trained hyperbolic signals: the grouped path (score_signals + hyperbolic_scores_signals, one copy back) against the
+per-signal loop (score_windows + hyperbolic_scores per signal, as main._detect runs it), from trained models to final scores on the host.
+    python scripts/time_score_signals.py [--cases 1000,5000,20000,ragged] [--reps 5] [--only grouped|per_signal]
+Prints one JSON line per case: median wall ms of each path over --reps (after one warm-up), and whether the final scores are equal bit
+for bit.  Launch counts: run one case under `rocprofv3 --kernel-trace --stats -- python scripts/time_score_signals.py --cases ragged
+--reps 1 --only grouped` (and --only per_signal)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+S, L = 100, 20
+
+
+def _case(name, rng):
+    if name == "ragged":
+        return [int(v) for v in rng.integers(1_500, 9_001, size=32)]
+    return [int(name)] * 32
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--cases", default="1000,5000,20000,ragged")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--only", default="")
+    args = ap.parse_args()
+    from hypad_amd import anomaly_detection as ad
+    from hypad_amd.models import tadgan
+    from hypad_amd.utils import anomaly_detection_utils as adu
+    rng = np.random.default_rng(0)
+    for case in args.cases.split(","):
+        counts = _case(case, rng)
+        models = []
+        for k in range(len(counts)):
+            torch.manual_seed(k)
+            models.append(tuple(m.cuda().eval() for m in (tadgan.Encoder(S, L), tadgan.Decoder(S, L, True), tadgan.CriticX(S, L))))
+        series = []
+        for k, n in enumerate(counts):
+            t = np.arange(n + S - 1)
+            series.append(torch.from_numpy(np.clip(np.sin(t * 2 * np.pi / (40 + k)) + 0.1 * rng.standard_normal(n + S - 1), -1, 1)
+                                           .astype(np.float32)).cuda())
+
+        class _View:
+            def __init__(self, s, n):
+                self.s, self.n = s, n
+
+            def series_windows(self, device="cuda"):
+                return self.s, self.n, 1
+
+        def per_signal():
+            out = []
+            for k, n in enumerate(counts):
+                r = ad.score_windows(torch.empty(n, S), *models[k], S, L, True, series=series[k])
+                host = ad._to_host({"recons": r["recons"], "critic": r["critic"], "hyper_real": r["hyper_real"]})
+                out.append(np.asarray(adu.hyperbolic_scores(host["recons"], host["hyper_real"], list(host["critic"]), S, "mult")))
+            return np.concatenate(out)
+
+        def grouped():
+            r = ad.score_signals([_View(s, n) for s, n in zip(series, counts)], models, S, L, True)
+            f = adu.hyperbolic_scores_signals(r, "mult")
+            return ad._to_host({"final": f["final_scores"]})["final"].copy()
+
+        row = {"case": case, "signals": len(counts), "windows": int(sum(counts))}
+        finals = {}
+        for name, fn in (("per_signal", per_signal), ("grouped", grouped)):
+            if args.only and name != args.only:
+                continue
+            finals[name] = fn()
+            ts = []
+            for _ in range(args.reps):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                ts.append((time.perf_counter() - t0) * 1e3)
+            row[name + "_ms"] = round(float(np.median(ts)), 3)
+        if len(finals) == 2:
+            row["bit_equal"] = finals["grouped"].tobytes() == finals["per_signal"].tobytes()
+            row["speedup"] = round(row["per_signal_ms"] / row["grouped_ms"], 2)
+        print(json.dumps(row), flush=True)
+
+
+if __name__ == "__main__":
+    main()
