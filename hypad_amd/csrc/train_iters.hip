@@ -1377,10 +1377,23 @@ DwTable gen_table(const hypad_dims& dm, bool with_decay = true) {
 }
 
 // ------------------------------------------------------------------------------------------------ host: launches
+// LDS of the stand-alone critic launches (cx_pass / cz_pass and their pair form, critic_gp), which every training path falls back
+// on: the window tile, the critic's weights and the 48-row activation tiles.  Latent 29..32 with windows above 240 need more than
+// the 160 KiB of a CU (256 x 32: 164 544 bytes): refused by check_dims, before any launch, instead of by a failed hipFuncSetAttribute.
+bool critic_launches_fit(int S, int L) {
+  const int cxf = cx_layout(S, L).total, czf = cz_layout(L).total, scratch = critic_batch_lds_floats(48, L);
+  const int f[4] = {lds_plan(S, 16, 16, cxf, scratch).total, lds_plan(S, 16, 16, czf, scratch).total, gp_lds_floats(S, cxf),
+                    gp_lds_floats(L, czf)};
+  for (int v : f)
+    if ((size_t)v * sizeof(float) > 160 * 1024) return false;
+  return true;
+}
+
 int check_dims(const hypad_dims* d) {
   if (!d || d->signal_shape <= 0 || d->latent_dim <= 0 || d->batch <= 0 || d->n_signals <= 0 || d->first_signal < 0) return HYPAD_EINVAL;
   if (d->batch % 16 != 0) return HYPAD_EINVAL;
   if (d->signal_shape > MAX_S || d->latent_dim > MAX_L) return HYPAD_EUNSUPPORTED;
+  if (!critic_launches_fit(d->signal_shape, d->latent_dim)) return HYPAD_EUNSUPPORTED;
   if (gen_table(*d).n < 0) return HYPAD_EUNSUPPORTED;      // cannot happen within MAX_S / MAX_L; the critic tables are far smaller
   // the closed forms device code uses for a critic's tensor offsets (layout.h CriticLayout::wof / bof) ARE the layout's table
   const CriticLayout cls[2] = {cx_layout(d->signal_shape, d->latent_dim), cz_layout(d->latent_dim)};

@@ -41,7 +41,8 @@ typedef void* hypad_stream_t; /* hipStream_t */
 
 int hypad_abi_version(void);
 const char* hypad_error_string(int code);
-/* signal_shape <= max_signal_shape, latent_dim <= max_latent for the fused network kernels */
+/* signal_shape <= max_signal_shape, latent_dim <= max_latent for the fused network kernels.  The training calls (hypad_dims) also
+ * refuse latent 29..32 with windows above 240 (HYPAD_EUNSUPPORTED): their stand-alone critic launches would need more LDS than a CU has. */
 void hypad_limits(int* max_signal_shape, int* max_latent);
 
 /* ------------------------------------------------------------------------------------------------
