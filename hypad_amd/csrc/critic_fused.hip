@@ -1811,8 +1811,15 @@ __device__ __forceinline__ void critic_persistent_body(const IterArgs& a, const 
     __syncthreads();
     if (ctl[0]) { if (writer && threadIdx.x == 0) lo_base[(int64_t)(2 * it) * 4] = __builtin_nanf(""); return; }
     PSTAMP(13);                                                          // siblings' scalars are there
-    if (ph.clear_each) clear_tiles();                     // (every read of this iteration's tiles is behind the barrier above; one
-                                                          // wave -- wave 2 has no share to store -- clearing alone took 5 k cycles)
+    if (ph.clear_each) {                                  // (every read of this iteration's tiles is behind the barrier above; one
+      clear_tiles();                                      // wave -- wave 2 has no share to store -- clearing alone took 5 k cycles)
+      // ... and every clearing write is behind this one: the next iteration's record is staged further down, into the same tiles,
+      // by waves that may get there before a clearing wave is done -- a late clear would zero its constant d loss / d out words
+      // and that iteration would back-propagate 0 for their rows.  (Staging at the loop top instead keeps the record registers
+      // alive across the optimizer step, in the default path too, which never clears: built that way, <100, 20, 64> went from 254
+      // to 255 VGPRs and 219 to 225 spilled SGPRs, <123, 20, 64> from 270 to 295, <51, 20, 64> from 210 to 230.)
+      __syncthreads();
+    }
     const float coef = xsc[3 * MAXCH + 2];
     PSTAMP(17);
     // ---- merged share -> compact valid quads, write-through; then the epoch word
