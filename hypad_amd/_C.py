@@ -88,6 +88,7 @@ class EpochIO(Structure):
 
 
 STATS_WORKSPACE_BYTES = 256 * 5 * 8  # HYPAD_STATS_WORKSPACE_BYTES
+REC_KINDS = {"point": 1, "area": 2, "dtw": 4}      # HYPAD_REC_*
 EPOCH_PER_ITERATION = 1            # hypad_epoch_io.flags (include/hypad.h: HYPAD_EPOCH_*)
 EPOCH_NO_PRODUCERS, EPOCH_ID_ORDER, EPOCH_CLEAR_TILES, EPOCH_PER_MINIBATCH, EPOCH_DW_COLOC, EPOCH_DW_SPREAD = 2, 4, 8, 16, 32, 64
 EPOCH_TEST_GIVE_UP_SHIFT = 8
@@ -190,6 +191,9 @@ _SIGS = {
     "hypad_critic_score_signals_workspace_bytes": (c_size_t, [c_int, POINTER(c_int64), c_int]),
     "hypad_critic_score_signals": (c_int, [P, P, c_int, POINTER(c_int64), c_int, P, c_size_t, P]),
     "hypad_combine_scores_signals": (c_int, [c_int, P, P, P, P, c_int, POINTER(c_int64), c_int, P]),
+    "hypad_unroll_median_signals": (c_int, [P, P, c_int, POINTER(c_int64), c_int, P]),
+    "hypad_rec_scores_signals_workspace_bytes": (c_size_t, [c_int, POINTER(c_int64), c_int]),
+    "hypad_rec_scores_signals": (c_int, [c_int, P, P, P, P, P, c_int, POINTER(c_int64), c_int, c_int, c_void_p, c_size_t, P]),
 }
 EXPORTS = tuple(_SIGS)
 for _name, (_res, _args) in _SIGS.items():

@@ -1145,6 +1145,421 @@ int seg_check(int n_signals, const int64_t* row_off) {
   return HYPAD_OK;
 }
 
+// ---- Euclidean (TadGAN) scores of a group: score_anomalies :407-576 for every segment at once, in TIMESTEP LAYOUT (include/hypad.h).
+// Every kernel below takes its segment from blockIdx.y -- a scalar: the segment's offsets come out of the kernel arguments with scalar
+// loads and every clip is against the segment's own ends -- and does, per output element, what the single-signal kernel above does
+// on that segment alone.
+__device__ __forceinline__ int64_t seg_toff(const SegTable& t, int sl, int window) { return t.off[sl] + (int64_t)(t.seg0 + sl) * (window - 1); }
+
+// unroll_median_kernel<EPL, true, UT> without the summary, per segment: grid (tiles, segments).  A tile lies inside one segment (the
+// tile loop runs over the segment's own timesteps), the interior fast path holds for tiles inside it, n / T are the segment's.
+// (The tile loop is a copy, not a shared function: with the loop moved into one the single-signal kernels' register allocation
+// changed -- their code objects are held identical.)
+template <int EPL, int UT>
+__global__ __launch_bounds__(UT * 4) __attribute__((amdgpu_waves_per_eu(HYPAD_UNROLL_WPE, HYPAD_UNROLL_WPE))) void unroll_median_signals_kernel(
+    const float* __restrict__ y_all, float* __restrict__ median_all, SegTable tab, int W) {
+  const int sl = blockIdx.y;
+  const int64_t n = tab.off[sl + 1] - tab.off[sl];
+  const float* __restrict__ y_hat = y_all + tab.off[sl] * W;
+  float* __restrict__ median = median_all + seg_toff(tab, sl, W);
+  constexpr int THREADS = UT * 4;                           // (shadows the file's 256: this kernel's block size follows its tile)
+  constexpr int RUN = UT / 64;                               // elements per lane of one source row's run
+  extern __shared__ __attribute__((aligned(16))) float usm[];
+  const int WS = (W + 3) & ~3;                              // tile row stride (floats)
+  float* tile = usm;                                        // [UT][WS]
+  float* sorted = usm + UT * WS;                            // [waves][MAX_WINDOW]   (summary / candidates)
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int wave_s = __builtin_amdgcn_readfirstlane(wave);
+  constexpr int NWV = THREADS / 64;
+  const int64_t T = n + W - 1;
+  float* s = sorted + (wave_s) * MAX_WINDOW;
+  const float INF = __int_as_float(0x7f800000);
+  for (int64_t t0 = (int64_t)blockIdx.x * UT; t0 < T; t0 += (int64_t)gridDim.x * UT) {
+    // ---- stage: rows r in [t0 - (W - 1), t0 + UT) (clipped to the matrix), their runs of this tile's timesteps
+    constexpr int RB = 8 / RUN;                              // rows in flight per wave (8 loads per lane either way)
+    if (t0 >= W - 1 && t0 + UT <= n) {
+      // interior tile (all but the first and last two of a long series): no clipping, j0 == 0, 32-bit indices relative to the
+      // tile's first row, the row number a scalar -- ~9 vector instructions per row and lane instead of ~30 of 64-bit arithmetic
+      const float* base = y_hat + (t0 - (W - 1)) * W;
+      const int nrows = W + UT - 1;
+      for (int kb = wave_s * RB; kb < nrows; kb += NWV * RB) {
+        float val[RB][RUN];
+        int dst[RB][RUN];
+#pragma unroll
+        for (int u = 0; u < RB; ++u) {
+          const int k = kb + u;                              // (scalar) row of the tile's parallelogram
+          const int jb = W - 1 - k > 0 ? W - 1 - k : 0;
+#pragma unroll
+          for (int h = 0; h < RUN; ++h) {
+            const int j = jb + lane + 64 * h, tt = k - (W - 1) + j;
+            const bool ok = k < nrows && j < W && tt < UT;
+            dst[u][h] = ok ? tt * WS + j : -1;
+            val[u][h] = ok ? base[k * W + j] : 0.f;
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < RB; ++u)
+#pragma unroll
+          for (int h = 0; h < RUN; ++h)
+            if (dst[u][h] >= 0) tile[dst[u][h]] = val[u][h];
+      }
+    } else {
+      const int64_t r_lo = t0 - (W - 1) > 0 ? t0 - (W - 1) : 0;
+      const int64_t r_hi = t0 + UT < n ? t0 + UT : n;         // exclusive
+      for (int64_t rb = r_lo + wave * RB; rb < r_hi; rb += NWV * RB) {
+        float val[RB][RUN];
+        int dst[RB][RUN];
+#pragma unroll
+        for (int u = 0; u < RB; ++u) {
+          const int64_t r = rb + u;
+          const int jb = (int)(t0 - r > 0 ? t0 - r : 0);       // first column of row r inside the tile
+#pragma unroll
+          for (int h = 0; h < RUN; ++h) {
+            const int j = jb + lane + 64 * h;                  // (a run is at most UT columns: RUN elements per lane)
+            const int64_t t = r + j;
+            dst[u][h] = -1; val[u][h] = 0.f;
+            if (r < r_hi && j < W && t < t0 + UT && t < T) {
+              const int j0 = (int)(t - n + 1 > 0 ? t - n + 1 : 0);
+              dst[u][h] = (int)(t - t0) * WS + (j - j0);
+              val[u][h] = y_hat[r * W + j];
+            }
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < RB; ++u)
+#pragma unroll
+          for (int h = 0; h < RUN; ++h)
+            if (dst[u][h] >= 0) tile[dst[u][h]] = val[u][h];
+      }
+    }
+    __syncthreads();
+    // (round 6: the timestep a wave works on is a scalar -- as a vector value every count, address and "wave-uniform" branch below was
+    // vector arithmetic and exec-mask code)
+    for (int tt = wave_s; tt < UT; tt += NWV) {
+      const int64_t t = t0 + tt;
+      if (t >= T) break;
+      const int j0 = (int)(t - n + 1 > 0 ? t - n + 1 : 0);
+      const int j1 = (int)(t + 1 < W ? t + 1 : W);
+      const int cnt = j1 - j0;
+      float* v = tile + tt * WS;
+      // pad the row to a multiple of 4 with +inf (never below or equal to a finite value)
+      if (lane < 4 && cnt + lane < ((cnt + 3) & ~3)) v[cnt + lane] = INF;
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): LDS writes of this wave landed
+      float mine[EPL];
+#pragma unroll
+      for (int e = 0; e < EPL; ++e) { const int i = lane + 64 * e; mine[e] = i < cnt ? v[i] : INF; }
+      const int m1 = (cnt - 1) >> 1, m2 = cnt >> 1;
+      float lo_med = 0.f, hi_med = 0.f;
+      bool done = false;
+      if (cnt >= 64) {                                       // wave-uniform (FILTER: median only)
+        // ranks inside the sample v[0 .. 31] (lanes >= 32 idle along)
+        const float sv = v[lane & 31];
+        int less = 0;
+#pragma unroll
+        for (int k0 = 0; k0 < 32; k0 += 4) {
+          const float4 q = *reinterpret_cast<const float4*>(v + k0);
+          less += (q.x < sv ? 1 : 0) + (q.y < sv ? 1 : 0) + (q.z < sv ? 1 : 0) + (q.w < sv ? 1 : 0);
+        }
+        float plo = less <= 10 ? sv : -INF, phi = less >= 21 ? sv : INF;     // 11th smallest (largest with <= 10 below), 22nd smallest
+        plo = hypad::wave_max(plo); phi = hypad::wave_min(phi);                // (DPP butterflies: no LDS round trips on this chain)
+        int c_lt = 0, c_le = 0;
+        unsigned long long cm[EPL];
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) {
+          const bool in = lane + 64 * e < cnt;
+          c_lt += __builtin_popcountll(__ballot(in && mine[e] < plo));
+          c_le += __builtin_popcountll(__ballot(in && mine[e] <= phi));
+          cm[e] = __ballot(in && mine[e] >= plo && mine[e] <= phi);
+        }
+        const int nc = c_le - c_lt;
+        if (c_lt <= m1 && m2 < c_le && nc <= 64 && nc > 0) {
+          // compact the candidates into the wave's slab, rank them against each other
+          int base = 0;
+#pragma unroll
+          for (int e = 0; e < EPL; ++e) {
+            const int pos = base + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(cm[e] >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)cm[e], 0u));
+            if ((cm[e] >> lane) & 1ull) s[pos] = mine[e];
+            base += __builtin_popcountll(cm[e]);
+          }
+          if (lane < 4 && nc + lane < ((nc + 3) & ~3)) s[nc + lane] = INF;
+          __builtin_amdgcn_wave_barrier();
+          __builtin_amdgcn_s_waitcnt(0xc07f);
+          const float c = lane < nc ? s[lane] : INF;
+          int rk = 0;
+          for (int k0 = 0; k0 < nc; k0 += 4) {
+            const float4 q = *reinterpret_cast<const float4*>(s + k0);
+            rk += (q.x < c ? 1 : 0) + (q.y < c ? 1 : 0) + (q.z < c ? 1 : 0) + (q.w < c ? 1 : 0);
+          }
+          // without ties the "less" counts are a permutation of 0 .. nc - 1 (their sum tells): then the lanes holding local ranks
+          // m1 - c_lt and m2 - c_lt hold the two middle values
+          const float rsum = hypad::wave_sum(lane < nc ? (float)rk : 0.f);
+          if (rsum == 0.5f * (float)nc * (float)(nc - 1)) {
+            const unsigned long long k1 = __ballot(lane < nc && rk == m1 - c_lt), k2 = __ballot(lane < nc && rk == m2 - c_lt);
+            lo_med = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c), (int)__builtin_ctzll(k1)));
+            hi_med = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c), (int)__builtin_ctzll(k2)));
+            done = true;
+          }
+          __builtin_amdgcn_wave_barrier();
+        }
+      }
+      if (!done) {
+        // rank = #{k : v[k] < mine} + #{k < i : v[k] == mine}.  Fast pass: count "less" only (one compare + add-carry per value).
+        // Without ties those counts are a permutation of 0 .. cnt-1, with ties two values share a count and the counts' sum falls
+        // short of cnt (cnt - 1) / 2: only then is the ordered tie count needed.  (The sum is exact in fp32: < 2^15 at window 256.)
+        int rank[EPL];
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) rank[e] = 0;
+        for (int k0 = 0; k0 < cnt; k0 += 4) {
+          const float4 q = *reinterpret_cast<const float4*>(v + k0);
+          const float vk[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+          for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int e = 0; e < EPL; ++e) rank[e] += vk[u] < mine[e] ? 1 : 0;
+        }
+        float rsum = 0.f;
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) rsum += lane + 64 * e < cnt ? (float)rank[e] : 0.f;
+        const bool ties = hypad::wave_sum(rsum) != 0.5f * (float)cnt * (float)(cnt - 1);
+        if (ties) {                                      // wave-uniform
+#pragma unroll
+          for (int e = 0; e < EPL; ++e) rank[e] = 0;
+          for (int k = 0; k < cnt; ++k) {
+            const float vk = v[k];
+#pragma unroll
+            for (int e = 0; e < EPL; ++e) {
+              const int i = lane + 64 * e;
+              rank[e] += (vk < mine[e]) || (vk == mine[e] && k < i);
+            }
+          }
+        }
+#pragma unroll
+        for (int e = 0; e < EPL; ++e)
+          if (lane + 64 * e < cnt) s[rank[e]] = mine[e];
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_s_waitcnt(0xc07f);
+        lo_med = s[m1]; hi_med = s[m2];
+      }
+      if (lane == 0) {
+        median[t] = (cnt & 1) ? lo_med : (lo_med + hi_med) * 0.5f;     // np.median of float32 stays float32
+      }
+      __builtin_amdgcn_wave_barrier();
+    }
+    __syncthreads();
+  }
+}
+
+
+// area_error_kernel per segment
+__global__ __launch_bounds__(THREADS) void area_error_signals_kernel(const double* __restrict__ y_all, const float* __restrict__ yh_all,
+                                                                      double* __restrict__ out_all, SegTable tab, int window, int w) {
+  const int sl = blockIdx.y;
+  const int64_t to = seg_toff(tab, sl, window), T = tab.off[sl + 1] - tab.off[sl] + window - 1;
+  const double* __restrict__ y = y_all + to;
+  const float* __restrict__ yh = yh_all + to;
+  double* __restrict__ out = out_all + to;
+  for (int64_t i = (int64_t)blockIdx.x * THREADS + threadIdx.x; i < T; i += (int64_t)gridDim.x * THREADS) {
+    int64_t lo, hi;
+    centred_window(i, w, T, lo, hi);
+    if (hi - lo + 1 < w / 2) { out[i] = NAN; continue; }
+    double a = 0.0, b = 0.0;
+    for (int64_t k = lo; k < hi; ++k) {
+      a += (y[k] + y[k + 1]) * 0.5;
+      b += ((double)yh[k] + (double)yh[k + 1]) * 0.5;
+    }
+    out[i] = fabs(a - b);
+  }
+}
+// dtw_error_kernel<LEN> per segment (the zero framing against the segment's T)
+template <int LEN>
+__global__ __launch_bounds__(THREADS) void dtw_error_signals_kernel(const double* __restrict__ y_all, const float* __restrict__ yh_all,
+                                                                     double* __restrict__ out_all, SegTable tab, int window) {
+  constexpr int HALF = LEN / 2;
+  const int sl = blockIdx.y;
+  const int64_t to = seg_toff(tab, sl, window), T = tab.off[sl + 1] - tab.off[sl] + window - 1;
+  const double* __restrict__ y = y_all + to;
+  const float* __restrict__ yh = yh_all + to;
+  double* __restrict__ out = out_all + to;
+  for (int64_t p = (int64_t)blockIdx.x * THREADS + threadIdx.x; p < T; p += (int64_t)gridDim.x * THREADS) {
+    const int64_t i = p - HALF;                 // window start in padded coordinates
+    if (i < 0 || i >= T - LEN) { out[p] = 0.0; continue; }
+    double a[LEN], b[LEN], row[LEN];
+#pragma unroll
+    for (int k = 0; k < LEN; ++k) {
+      int64_t src = i + k - HALF;               // y_pad[i + k] = y[i + k - HALF]
+      bool ok = src >= 0 && src < T;
+      a[k] = ok ? y[src] : 0.0;
+      b[k] = ok ? (double)yh[src] : 0.0;
+    }
+    double acc = 0.0;
+#pragma unroll
+    for (int j = 0; j < LEN; ++j) { double d = a[0] - b[j]; acc += d * d; row[j] = acc; }
+#pragma unroll
+    for (int r = 1; r < LEN; ++r) {
+      double diag = row[0];
+      double d0 = a[r] - b[0];
+      row[0] = row[0] + d0 * d0;
+#pragma unroll
+      for (int j = 1; j < LEN; ++j) {
+        double up = row[j];
+        double d = a[r] - b[j];
+        double m = fmin(fmin(up, row[j - 1]), diag);
+        row[j] = d * d + m;
+        diag = up;
+      }
+    }
+    out[p] = sqrt(row[LEN - 1]);
+  }
+}
+
+// The smoothing, statistics and z-score of up to three error kinds (blockIdx.z) of every segment (blockIdx.y).  Kind k smooths src[k]
+// (the point-wise error fused as in RollSrc) into out[k], which the z-score then rewrites in place.  Per segment: the smoothing window
+// trunc(n_s * 0.01) of score_anomalies (0: all NaN, rolling_mean's fill), the chunk sums aligned to the segment's start (origin 0),
+// stat_blocks(T_s) slices.  Chunk sums of segment s start at slot (toff_s >> 4) + 2 s resp. (toff_s >> 8) + 2 s of the kind's arrays
+// (segments need at most T_s / 16 + 1 resp. T_s / 256 + 1 slots: no overlap), its partials at [(kind, s)][STAT_G].
+struct RecKinds { RollSrc src[3]; double* out[3]; double* s1[3]; double* s2[3]; int* c1[3]; int* c2[3]; StatPart* parts[3]; };
+__host__ __device__ inline int seg_smooth_window(int64_t n) { return (int)((double)n * 0.01); }        // math.trunc(n * 0.01), n > 0
+__host__ __device__ inline int stat_blocks_of(int64_t t) { int64_t g = (t + 1023) / 1024; return (int)(g < 1 ? 1 : (g > STAT_G ? STAT_G : g)); }
+struct SegRoll {                                   // one segment of one kind, as the single-signal kernels see it
+  RollSrc src; RollWs ws; double* out; StatPart* parts; int64_t T; int w;
+};
+__device__ __forceinline__ SegRoll seg_roll(const RecKinds& kd, const SegTable& tab, int window) {
+  const int sl = blockIdx.y, kz = blockIdx.z, sg = tab.seg0 + sl;
+  const int64_t n = tab.off[sl + 1] - tab.off[sl], to = seg_toff(tab, sl, window);
+  SegRoll r;
+  r.T = n + window - 1; r.w = seg_smooth_window(n);
+  r.src.in = kd.src[kz].in + to; r.src.sub = kd.src[kz].sub ? kd.src[kz].sub + to : nullptr;
+  r.out = kd.out[kz] + to;
+  const int64_t b1 = (to >> 4) + 2 * sg, b2 = (to >> 8) + 2 * sg;
+  r.ws.s1 = kd.s1[kz] + b1; r.ws.c1 = kd.c1[kz] + b1; r.ws.s2 = kd.s2[kz] + b2; r.ws.c2 = kd.c2[kz] + b2;
+  roll_counts(r.T, 0, r.ws.n1, r.ws.n2);
+  r.parts = kd.parts[kz] + (size_t)sg * STAT_G;
+  return r;
+}
+// roll_chunks_kernel at origin 0, for the segments whose window takes the chunked path
+__global__ __launch_bounds__(THREADS) void roll_chunks_signals_kernel(RecKinds kd, SegTable tab, int window) {
+  __shared__ double sh_s[THREADS];
+  __shared__ int sh_c[THREADS];
+  const SegRoll g = seg_roll(kd, tab, window);
+  const int64_t c2_0 = (int64_t)blockIdx.x * 16;                                     // this workgroup's first 256-chunk
+  if (g.w <= ROLL_DIRECT_MAX || c2_0 >= g.ws.n2) return;                             // (workgroup-uniform)
+  const RollSrc src = g.src; const RollWs ws = g.ws; const int64_t T = g.T;
+  const int64_t first1 = c2_0 << 4;                                                  // level-1 slot of its first 16-chunk
+  const int64_t j = first1 + threadIdx.x;
+  double s = 0.0; int cnt = 0;
+  if (j >= 0 && j < ws.n1) {
+    const int64_t g0 = j << 4;
+#pragma unroll 4
+    for (int k = 0; k < RC1; ++k) {
+      const int64_t i = g0 + k;
+      if (i >= 0 && i < T) { const double v = src(i); if (v == v) { s += v; ++cnt; } }
+    }
+    ws.s1[j] = s; ws.c1[j] = cnt;
+  }
+  sh_s[threadIdx.x] = s; sh_c[threadIdx.x] = cnt;
+  __syncthreads();
+  if (threadIdx.x < 16 && c2_0 + threadIdx.x < ws.n2) {
+    double s2 = 0.0; int c2 = 0;
+#pragma unroll 4
+    for (int k = 0; k < 16; ++k) {
+      const int64_t jj = first1 + 16 * threadIdx.x + k;
+      if (jj >= 0 && jj < ws.n1) { s2 += sh_s[16 * threadIdx.x + k]; c2 += sh_c[16 * threadIdx.x + k]; }
+    }
+    ws.s2[c2_0 + threadIdx.x] = s2; ws.c2[c2_0 + threadIdx.x] = c2;
+  }
+}
+// rolling_mean_kernel<false / true> by the segment's window (workgroup-uniform), fill_nan_kernel's value at window 0
+__global__ __launch_bounds__(THREADS) void rolling_mean_signals_kernel(RecKinds kd, SegTable tab, int window) {
+  const SegRoll g = seg_roll(kd, tab, window);
+  const RollSrc src = g.src; const RollWs ws = g.ws; const int64_t T = g.T; const int w = g.w;
+  double* __restrict__ out = g.out;
+  for (int64_t i = (int64_t)blockIdx.x * THREADS + threadIdx.x; i < T; i += (int64_t)gridDim.x * THREADS) {
+    if (w == 0) { out[i] = __builtin_nan(""); continue; }
+    int64_t lo, hi;
+    centred_window(i, w, T, lo, hi);
+    int cnt = 0;
+    double s = 0.0;
+    if (w <= ROLL_DIRECT_MAX) {
+      for (int64_t k = lo; k <= hi; ++k) {
+        const double v = src(k);
+        if (v == v) { s += v; ++cnt; }            // pandas skips NaN
+      }
+    } else {
+      const int64_t end = hi + 1;
+      int64_t p = lo;
+      auto elems = [&](int64_t to) { for (; p < to; ++p) { const double v = src(p); if (v == v) { s += v; ++cnt; } } };
+      const int64_t a16 = (p + RC1 - 1) & ~(int64_t)(RC1 - 1);
+      elems(a16 < end ? a16 : end);
+      while (p + RC1 <= end && (p & (RC2 - 1))) { s += ws.s1[p >> 4]; cnt += ws.c1[p >> 4]; p += RC1; }
+      while (p + RC2 <= end) { s += ws.s2[p >> 8]; cnt += ws.c2[p >> 8]; p += RC2; }
+      while (p + RC1 <= end) { s += ws.s1[p >> 4]; cnt += ws.c1[p >> 4]; p += RC1; }
+      elems(end);
+    }
+    out[i] = cnt >= w / 2 && cnt > 0 ? s / (double)cnt : NAN;
+  }
+}
+// stat_partials_kernel<false> with the segment cut into stat_blocks(T_s) slices (grid.x = STAT_G: the blocks beyond them leave)
+__global__ __launch_bounds__(256) void stat_partials_signals_kernel(RecKinds kd, SegTable tab, int window) {
+  __shared__ double sh[4];
+  const SegRoll g = seg_roll(kd, tab, window);
+  const int64_t T = g.T;
+  const int nb = stat_blocks_of(T);
+  if ((int)blockIdx.x >= nb) return;                                                  // (workgroup-uniform)
+  const double* __restrict__ in = g.out;
+  const int64_t len = (T + nb - 1) / nb;
+  const int64_t b = (int64_t)blockIdx.x * len, e = b + len < T ? b + len : T;
+  double s = 0.0;
+  for (int64_t i = b + threadIdx.x; i < e; i += 256) {
+    const double x = in[i];
+    s += x;
+  }
+  const double n = e > b ? (double)(e - b) : 0.0;
+  const double mean = n > 0.0 ? block_sum_256(s, sh) / n : 0.0;
+  double q = 0.0;
+  for (int64_t i = b + threadIdx.x; i < e; i += 256) { const double d = in[i] - mean; q += d * d; }
+  q = block_sum_256(q, sh);
+  if (threadIdx.x == 0) { StatPart p; p.n = n; p.mean = mean; p.m2 = q; p.rsum = 0.0; p.rcnt = 0.0; g.parts[blockIdx.x] = p; }
+}
+// zscore_apply_kernel per segment, in place
+__global__ __launch_bounds__(256) void zscore_apply_signals_kernel(RecKinds kd, SegTable tab, int window) {
+  __shared__ StatPart sh[STAT_G];
+  const SegRoll g = seg_roll(kd, tab, window);
+  const int64_t T = g.T;
+  const StatPart st = stat_merge_all(g.parts, stat_blocks_of(T), sh);
+  const double mean = st.mean, sd = sqrt(st.m2 / st.n);
+  double* io = g.out;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < T; i += (int64_t)gridDim.x * 256) {
+    double z = (io[i] - mean) / sd;
+    io[i] = (z != z) ? z : fmax(z, 0.0) + 1.0;  // np.clip keeps NaN
+  }
+}
+inline SegTable seg_table(const int64_t* row_off, int c0, int n_signals) {
+  SegTable t{};
+  t.n = std::min(SEG_CHUNK, n_signals - c0); t.seg0 = c0;
+  for (int i = 0; i <= t.n; ++i) t.off[i] = row_off[c0 + i];
+  return t;
+}
+inline int64_t seg_longest(const SegTable& t) {
+  int64_t most = 0;
+  for (int i = 0; i < t.n; ++i) most = std::max<int64_t>(most, t.off[i + 1] - t.off[i]);
+  return most;
+}
+// workspace of hypad_rec_scores_signals: [area errors | dtw errors] (timestep layout) | per kind [16-chunk sums | 256-chunk sums] | their
+// counts | per kind and segment STAT_G partials
+struct RecWsLayout { int64_t total, cap1, cap2; size_t err, sums, counts, parts, bytes; };
+RecWsLayout rec_ws_layout(int n_signals, const int64_t* row_off, int window) {
+  RecWsLayout l;
+  l.total = row_off[n_signals] + (int64_t)n_signals * (window - 1);
+  l.cap1 = (l.total >> 4) + 2 * (int64_t)n_signals + 2; l.cap2 = (l.total >> 8) + 2 * (int64_t)n_signals + 2;
+  l.err = 0;
+  l.sums = l.err + 2 * (size_t)l.total * sizeof(double);
+  l.counts = l.sums + 3 * (size_t)(l.cap1 + l.cap2) * sizeof(double);
+  l.parts = (l.counts + 3 * (size_t)(l.cap1 + l.cap2) * sizeof(int) + 63) & ~(size_t)63;
+  l.bytes = l.parts + 3 * (size_t)n_signals * STAT_G * sizeof(StatPart);
+  return l;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1385,6 +1800,94 @@ int hypad_combine_scores_signals(int mode, const double* c, const double* r, con
     for (int i = 0; i <= t.n; ++i) t.off[i] = row_off[c0 + i];
     for (int i = 0; i < t.n; ++i) most = std::max<int64_t>(most, t.off[i + 1] - t.off[i]);
     hipLaunchKernelGGL(combine_signals_kernel, dim3(grid_for(most, THREADS), (unsigned)t.n), dim3(THREADS), 0, (hipStream_t)s, mode, c, r, u, out, t, window);
+    HYPAD_CHECK_LAUNCH();
+  }
+  return HYPAD_OK;
+}
+
+int hypad_unroll_median_signals(const float* y_hat, float* median, int n_signals, const int64_t* row_off, int window, hypad_stream_t s) {
+  const int rc = seg_check(n_signals, row_off);
+  if (rc) return rc;
+  if (!y_hat || !median || window <= 0) return HYPAD_EINVAL;
+  if (window > MAX_WINDOW) return HYPAD_EUNSUPPORTED;
+  constexpr int UT = 128;
+  const size_t lds = (size_t)(UT * ((window + 3) & ~3) + (UT / 16) * MAX_WINDOW) * sizeof(float);      // hypad_unroll_median's: 59 KB at window 100
+  const void* kf = window <= 64 ? (const void*)unroll_median_signals_kernel<1, UT>
+                 : window <= 128 ? (const void*)unroll_median_signals_kernel<2, UT> : (const void*)unroll_median_signals_kernel<4, UT>;
+  if (lds > 64 * 1024 && hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+    (void)hipGetLastError();                                  // (the refusal is reported by the status, not left behind)
+    return HYPAD_EUNSUPPORTED;
+  }
+  for (int c0 = 0; c0 < n_signals; c0 += SEG_CHUNK) {
+    const SegTable t = seg_table(row_off, c0, n_signals);
+    const dim3 grid(grid_for(seg_longest(t) + window - 1, UT), (unsigned)t.n), block(UT * 4);
+    if (window <= 64) hipLaunchKernelGGL((unroll_median_signals_kernel<1, UT>), grid, block, lds, (hipStream_t)s, y_hat, median, t, window);
+    else if (window <= 128) hipLaunchKernelGGL((unroll_median_signals_kernel<2, UT>), grid, block, lds, (hipStream_t)s, y_hat, median, t, window);
+    else hipLaunchKernelGGL((unroll_median_signals_kernel<4, UT>), grid, block, lds, (hipStream_t)s, y_hat, median, t, window);
+    HYPAD_CHECK_LAUNCH();
+  }
+  return HYPAD_OK;
+}
+size_t hypad_rec_scores_signals_workspace_bytes(int n_signals, const int64_t* row_off, int window) {
+  if (seg_check(n_signals, row_off) || window <= 0) return 0;
+  return rec_ws_layout(n_signals, row_off, window).bytes;
+}
+int hypad_rec_scores_signals(int kinds, const double* true_unrolled, const float* median, double* out_point, double* out_area, double* out_dtw,
+                             int n_signals, const int64_t* row_off, int window, int score_window, void* workspace, size_t workspace_bytes,
+                             hypad_stream_t s) {
+  const int rc = seg_check(n_signals, row_off);
+  if (rc) return rc;
+  if (!true_unrolled || !median || window <= 0 || kinds < 1 || kinds > (HYPAD_REC_POINT | HYPAD_REC_AREA | HYPAD_REC_DTW)) return HYPAD_EINVAL;
+  if (((kinds & HYPAD_REC_POINT) && !out_point) || ((kinds & HYPAD_REC_AREA) && !out_area) || ((kinds & HYPAD_REC_DTW) && !out_dtw)) return HYPAD_EINVAL;
+  if ((kinds & (HYPAD_REC_AREA | HYPAD_REC_DTW)) && score_window < 2) return HYPAD_EINVAL;
+  const int len = (score_window / 2) * 2 + 1;
+  if ((kinds & HYPAD_REC_DTW) && len != 3 && len != 5 && len != 7 && len != 9 && len != 11 && len != 21) return HYPAD_EUNSUPPORTED;
+  const RecWsLayout l = rec_ws_layout(n_signals, row_off, window);
+  if (!workspace || workspace_bytes < l.bytes) return HYPAD_EWORKSPACE;
+  char* ws = (char*)workspace;
+  double* err_area = (double*)(ws + l.err);
+  double* err_dtw = err_area + l.total;
+  RecKinds kd{};
+  int nk = 0;
+  auto add = [&](const double* in, const float* sub, double* out) {
+    kd.src[nk] = RollSrc{in, sub}; kd.out[nk] = out;
+    kd.s1[nk] = (double*)(ws + l.sums) + (size_t)nk * (l.cap1 + l.cap2); kd.s2[nk] = kd.s1[nk] + l.cap1;
+    kd.c1[nk] = (int*)(ws + l.counts) + (size_t)nk * (l.cap1 + l.cap2); kd.c2[nk] = kd.c1[nk] + l.cap1;
+    kd.parts[nk] = (StatPart*)(ws + l.parts) + (size_t)nk * n_signals * STAT_G;
+    ++nk;
+  };
+  if (kinds & HYPAD_REC_POINT) add(true_unrolled, median, out_point);       // |true - median| inside the smoothing, as rolling_mean(minus=) does
+  if (kinds & HYPAD_REC_AREA) add(err_area, nullptr, out_area);
+  if (kinds & HYPAD_REC_DTW) add(err_dtw, nullptr, out_dtw);
+  const hipStream_t st = (hipStream_t)s;
+  for (int c0 = 0; c0 < n_signals; c0 += SEG_CHUNK) {
+    const SegTable t = seg_table(row_off, c0, n_signals);
+    const int64_t most = seg_longest(t) + window - 1;
+    const dim3 ge(grid_for(most, THREADS), (unsigned)t.n), b(THREADS);
+    if (kinds & HYPAD_REC_AREA) {
+      hipLaunchKernelGGL(area_error_signals_kernel, ge, b, 0, st, true_unrolled, median, err_area, t, window, score_window);
+      HYPAD_CHECK_LAUNCH();
+    }
+    if (kinds & HYPAD_REC_DTW) {
+      switch (len) {
+        case 3: hipLaunchKernelGGL(dtw_error_signals_kernel<3>, ge, b, 0, st, true_unrolled, median, err_dtw, t, window); break;
+        case 5: hipLaunchKernelGGL(dtw_error_signals_kernel<5>, ge, b, 0, st, true_unrolled, median, err_dtw, t, window); break;
+        case 7: hipLaunchKernelGGL(dtw_error_signals_kernel<7>, ge, b, 0, st, true_unrolled, median, err_dtw, t, window); break;
+        case 9: hipLaunchKernelGGL(dtw_error_signals_kernel<9>, ge, b, 0, st, true_unrolled, median, err_dtw, t, window); break;
+        case 11: hipLaunchKernelGGL(dtw_error_signals_kernel<11>, ge, b, 0, st, true_unrolled, median, err_dtw, t, window); break;   // reference default
+        default: hipLaunchKernelGGL(dtw_error_signals_kernel<21>, ge, b, 0, st, true_unrolled, median, err_dtw, t, window); break;
+      }
+      HYPAD_CHECK_LAUNCH();
+    }
+    // (always the same launches, whatever the segments' windows: a segment that does not take the chunked path leaves at once)
+    const unsigned gc = (unsigned)((((most - 1) >> 8) + 1 + 15) / 16);
+    hipLaunchKernelGGL(roll_chunks_signals_kernel, dim3(gc, (unsigned)t.n, (unsigned)nk), b, 0, st, kd, t, window);
+    HYPAD_CHECK_LAUNCH();
+    hipLaunchKernelGGL(rolling_mean_signals_kernel, dim3(ge.x, (unsigned)t.n, (unsigned)nk), b, 0, st, kd, t, window);
+    HYPAD_CHECK_LAUNCH();
+    hipLaunchKernelGGL(stat_partials_signals_kernel, dim3(STAT_G, (unsigned)t.n, (unsigned)nk), dim3(256), 0, st, kd, t, window);
+    HYPAD_CHECK_LAUNCH();
+    hipLaunchKernelGGL(zscore_apply_signals_kernel, dim3(grid_for(most, 1024), (unsigned)t.n, (unsigned)nk), dim3(256), 0, st, kd, t, window);
     HYPAD_CHECK_LAUNCH();
   }
   return HYPAD_OK;

@@ -111,14 +111,17 @@ def run_signals(params, names, config_path=None, data_dir="./data", log=print, g
 
 
 def _groupable(t, path):
-    """A signal _detect_grouped scores: univariate, in the series view, and without a critic_scores.pickle that ``params.load`` would
-    read back (those take _detect)."""
+    """A signal _detect_grouped scores: univariate, in the series view, and without a score cache that the per-signal detector
+    would read back -- critic_scores.pickle under ``params.load``; for a Euclidean model any of the four pickles score_anomalies
+    keeps (``path + "dtw.pickle"`` etc., the names it reads).  Those take _detect."""
     import os
     p, train_ds, test_ds, _ = t
     if hasattr(train_ds, "device_windows") or p.signal == "multivariate" or not hasattr(test_ds, "series_windows"):
         return False
     if getattr(p, "load", False) and path and os.path.exists(os.path.join(path, "critic_scores.pickle")):
         return False
+    if not p.hyperbolic and path and any(os.path.exists(path + f + ".pickle") for f in ("critic_scores", "point", "area", "dtw")):
+        return False                                   # score_anomalies reads those back whatever params.load says; the group never does
     return test_ds.series_windows("cpu") is not None and len(test_ds.X) > 0
 
 
@@ -126,7 +129,9 @@ def _detect_grouped(group, trained, data_dir, log):
     """_detect for several trained signals at once: one score_signals call (pack, critic and forward launches for all of them), for
     hyperbolic models hyperbolic_scores_signals, everything back in one page-locked copy and one wait; then per signal on the host
     the cache files test_tadgan writes, critic_scores.pickle, and detect_intervals (anomalies.csv, counts, metrics, results row) --
-    the same contents as _detect's.  Euclidean models: the grouped forward, then univariate_anomaly_detection per signal."""
+    the same contents as _detect's.  Euclidean models: euclidean_scores_signals (the un-roll, the reconstruction scores -- all three
+    kinds when a model directory keeps score_anomalies' pickles -- and the critic chain of all signals, in timestep layout), one
+    copy back, then the pickles and detect_intervals per signal; the reconstruction matrix comes back only for recons_signal.pt."""
     import pickle
 
     import pandas as pd
@@ -141,22 +146,33 @@ def _detect_grouped(group, trained, data_dir, log):
     models = [tuple(trained[name]["modules"][:3]) for _, name in group]
     res = anomaly_detection.score_signals([t[2] for t, _ in group], models, S, L, hyp)
     row_off = res["row_off"]
-    want = {"recons": res["recons"], "critic": res["critic"]}
+    keep = any(trained[name]["path"] for _, name in group)          # (some directory wants the test loop's files and the score pickles)
+    want = {"recons": res["recons"], "critic": res["critic"]} if hyp or keep else {}
     if hyp:
         want.update(hyper_real=res["hyper_real"], eucl=res["eucl"])
         comb = adu.hyperbolic_scores_signals(res, P0.combination)
         want["final"] = comb["final_scores"]
         if comb["critic_scores"] is not None:
             want["critic_scores"] = comb["critic_scores"]
+    else:
+        tests = [t[2] for t, _ in group]
+        comb = adu.euclidean_scores_signals(res, adu.unroll_true_signals(tests, row_off, S), P0.rec_error, P0.combination,
+                                            kinds=("point", "area", "dtw") if keep else None, with_critic=keep or None)
+        t_off = comb["t_off"]
+        want["final"] = comb["final_scores"]
+        if keep:
+            want["critic_scores"] = comb["critic_scores"]
+            want.update({kind: v for kind, v in comb["rec_scores"].items()})
     host = anomaly_detection._to_host(want)
     outs = {}
     for k, ((p, _, test_ds, read_path), name) in enumerate(group):
         a, b = row_off[k], row_off[k + 1]
         raw = trained[name]["path"]                           # (the detector's files are named raw + file, as _detect names them)
         path = raw + "/" if raw else ""
-        recons_signal = host["recons"][a:b]
         gt_signal = np.asarray(test_ds.X)
-        critic_score = list(host["critic"][a:b])
+        if path or hyp:
+            recons_signal = host["recons"][a:b]
+            critic_score = list(host["critic"][a:b])
         true_signal = host["hyper_real"][a:b] if hyp else gt_signal
         if path:
             torch.save(recons_signal, path + "recons_signal.pt")
@@ -175,8 +191,11 @@ def _detect_grouped(group, trained, data_dir, log):
                     pickle.dump(host["critic_scores"][a + k * (S - 1): b + (k + 1) * (S - 1)], f, protocol=pickle.HIGHEST_PROTOCOL)
             out = adu.detect_intervals(host["final"][a:b], p, raw, _true_index(test_ds, p), known, p.signal)
         else:
-            out = adu.univariate_anomaly_detection(recons_signal, true_signal, p, p.combination, critic_score, raw, read_path, p.rec_error,
-                                                   _true_index(test_ds, p), known, p.signal, p.signal_shape)
+            ta, tb = t_off[k], t_off[k + 1]
+            if raw:                                            # (score_anomalies' caches: the arrays and the protocol it writes)
+                for f in ("critic_scores", "point", "area", "dtw"):
+                    adu._dump_pickle(host[f][ta:tb].copy(), raw + f + ".pickle")
+            out = adu.detect_intervals(host["final"][ta:tb], p, raw, _true_index(test_ds, p), known, p.signal)
         log("predicted intervals:\n{}".format(out["intervals"]))
         log("tn, fp, fn, tp: {}".format(out["confusion"]))
         if out["metrics"]:

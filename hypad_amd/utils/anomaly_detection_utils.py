@@ -466,3 +466,95 @@ def hyperbolic_scores_signals(res, combination="mult"):
     _C.check(_C.lib.hypad_combine_scores_signals(_C.COMB[combination], _C.ptr(critic_scores), _C.ptr(rec), _C.ptr(u), _C.ptr(out), k, offs, w,
                                                  _C.stream()), "combine_signals")
     return {"final_scores": out, "critic_scores": critic_scores, "row_off": row_off}
+
+
+def timestep_offsets(row_off, S):
+    """Timestep layout (include/hypad.h, "Signal groups") of a group with window offsets ``row_off``: signal s owns the
+    n_s + S - 1 entries from t_off[s] = row_off[s] + s (S - 1) on.  Host list, len(row_off) entries."""
+    return [int(r) + s * (int(S) - 1) for s, r in enumerate(row_off)]
+
+
+def _upload(a):
+    """A host array as a device tensor (one copy)."""
+    return torch.from_numpy(np.ascontiguousarray(a)).to(_dev())
+
+
+def unroll_true_signals(x_list, row_off, S):
+    """unroll_true (:908-910) of every signal of a group as ONE fp64 device vector in timestep layout.  x_list: per signal a dataset
+    (its ``X``) or an (N, S[, 1]) window array.  Gathered on the host from each window matrix in its own dtype -- the first value of
+    every window, then the rest of the last one -- and widened to fp64: a pure gather, hence the bits unroll_true gives."""
+    S = int(S)
+    t_off = timestep_offsets(row_off, S)
+    out = np.empty(t_off[-1], dtype=np.float64)
+    for s, x in enumerate(x_list):
+        X = np.asarray(x.X if hasattr(x, "X") else x)
+        X = X.reshape(len(X), -1)
+        n = int(row_off[s + 1]) - int(row_off[s])
+        if X.shape != (n, S):
+            raise ValueError(f"signal {s}: windows {X.shape}, offsets say ({n}, {S})")
+        out[t_off[s]: t_off[s] + n] = X[:, 0]
+        out[t_off[s] + n: t_off[s + 1]] = X[-1, 1:]
+    return _upload(out)
+
+
+def euclidean_scores_signals(res, true_unrolled, rec_error_type="dtw", comb="mult", kinds=None, score_window=10, with_critic=None):
+    """score_anomalies (:407-576, no cache files) for every signal of a Euclidean score_signals result at once, everything in
+    timestep layout and nothing through the host: the anti-diagonal medians of all reconstructions (hypad_unroll_median_signals),
+    the z-scored reconstruction scores of ``kinds`` (default: the requested one; hypad_rec_scores_signals), beside them the critic
+    chain of final_critic_scores (hypad_kde_mode_signals + hypad_critic_score_signals; ``with_critic``: default unless comb is
+    "rec"), then the combination over the whole vector.  Each signal's numbers are score_anomalies' on it alone, bit for bit.
+    ``true_unrolled``: unroll_true_signals of the group.
+    Returns dict(final_scores, critic_scores (or None), rec_scores {kind: tensor}, row_off, t_off); tensors fp64 on the device."""
+    mode = {"mult": "eucl_mult", "sum": "eucl_sum", "rec": "rec", "critic": "critic"}.get(comb)
+    if mode is None:
+        raise ValueError('Unknown combination specified {}, use "mult", "sum", or "rec" instead.'.format(comb))
+    kind = rec_error_type.lower()
+    kinds = [kind] if kinds is None else [k.lower() for k in kinds]
+    if kind not in kinds:
+        kinds.append(kind)
+    for k in kinds:
+        if k not in _C.REC_KINDS:
+            raise ValueError(k)
+    if res.get("hyper_real") is not None:
+        raise ValueError("euclidean_scores_signals needs a Euclidean score_signals result")
+    row_off = [int(v) for v in res["row_off"]]
+    k_sig = len(row_off) - 1
+    recons = _f32(res["recons"])
+    w = recons.shape[1]
+    t_off = timestep_offsets(row_off, w)
+    total = t_off[-1]
+    true = _f64(true_unrolled).reshape(-1)
+    if true.numel() != total:
+        raise ValueError(f"true_unrolled has {true.numel()} entries, the group {total} timesteps")
+    offs = _C.int64s(row_off)
+    with_critic = (comb != "rec") if with_critic is None else bool(with_critic) or comb != "rec"
+    rec = {k: torch.empty(total, device=recons.device, dtype=torch.float64) for k in kinds}
+
+    def rec_branch():
+        median = torch.empty(total, device=recons.device, dtype=torch.float32)
+        _C.check(_C.lib.hypad_unroll_median_signals(_C.ptr(recons), _C.ptr(median), k_sig, offs, w, _C.stream()), "unroll_median_signals")
+        nbytes = _C.lib.hypad_rec_scores_signals_workspace_bytes(k_sig, offs, w)
+        ws = _scratch(recons.device, nbytes, "rec_scores_signals")
+        mask = sum(_C.REC_KINDS[k] for k in kinds)
+        _C.check(_C.lib.hypad_rec_scores_signals(mask, _C.ptr(true), _C.ptr(median), _C.ptr(rec.get("point")), _C.ptr(rec.get("area")),
+                                                 _C.ptr(rec.get("dtw")), k_sig, offs, w, int(score_window), ws.data_ptr(), nbytes, _C.stream()),
+                 "rec_scores_signals")
+        return rec[kind]
+
+    def critic_branch():
+        modes = torch.empty(total, device=recons.device, dtype=torch.float64)
+        _C.check(_C.lib.hypad_kde_mode_signals(_C.ptr(_f32(res["critic"]).reshape(-1)), _C.ptr(modes), k_sig, offs, w, _C.stream()), "kde_mode_signals")
+        out = torch.empty_like(modes)
+        nbytes = _C.lib.hypad_critic_score_signals_workspace_bytes(k_sig, offs, w)
+        ws = _scratch(modes.device, nbytes, "critic_score_signals")
+        _C.check(_C.lib.hypad_critic_score_signals(_C.ptr(modes), _C.ptr(out), k_sig, offs, w, ws.data_ptr(), nbytes, _C.stream()),
+                 "critic_score_signals")
+        return out
+
+    if with_critic:                  # (the critic chain on a side stream beside the reconstruction scores, as score_anomalies runs them)
+        r, c = concurrently(rec_branch, critic_branch)
+    else:
+        r, c = rec_branch(), None
+    final = torch.empty(total, device=recons.device, dtype=torch.float64)
+    _C.check(_C.lib.hypad_combine_scores(_C.COMB[mode], _C.ptr(c), _C.ptr(r), None, _C.ptr(final), total, _C.stream()), "combine")
+    return {"final_scores": final, "critic_scores": c, "rec_scores": rec, "row_off": row_off, "t_off": t_off}

@@ -529,6 +529,8 @@ int hypad_combine_scores(int combination, const double* critic_scores, const dou
  * anomaly_detection.py:20-155 + utils/anomaly_detection_utils.py:54-86, :336-404 of a dataset run, one model per signal).
  * row_off (n_signals + 1) and x_off (n_signals) are HOST int64 arrays: the launch plan is taken from them and they travel in the
  * kernel arguments.  row_off[0] = 0 and every signal has at least one window, else HYPAD_EINVAL without any launch.
+ * TIMESTEP LAYOUT: a vector with one entry per un-rolled timestep of every signal -- signal s, n_s = row_off[s + 1] - row_off[s]
+ * windows, owns the n_s + window - 1 entries from row_off[s] + s (window - 1) on; row_off[n_signals] + n_signals (window - 1) in all.
  * ---------------------------------------------------------------------------------------------- */
 /* hypad_score_forward_packed for n_signals models: enc / dec / cx are stacked arenas, (n_signals, hypad_param_count(net, ...))
  * each (hypad_amd Engine.params).  Signal s has windows row_off[s] .. row_off[s + 1]; its window n is x[x_off[s] + n * x_row_stride ..]
@@ -559,6 +561,24 @@ int hypad_critic_score_signals(const double* modes, double* out, int n_signals, 
  * hypad_combine_scores.  One launch per 64 signals. */
 int hypad_combine_scores_signals(int combination, const double* critic_scores, const double* rec_scores, const double* uncertainty,
                                  double* out, int n_signals, const int64_t* row_off, int window, hypad_stream_t stream);
+/* The Euclidean (TadGAN) branch of a group, score_anomalies :407-576 per signal.  Un-roll (reconstruction_errors :918-935): segment s
+ * of `median` (timestep layout, fp32) is hypad_unroll_median(y_hat + row_off[s] * window, ., NULL, n_s, window) -- the median of every
+ * anti-diagonal of the signal's own rows, no summary.  One launch per 64 signals; a tile never straddles two signals. */
+int hypad_unroll_median_signals(const float* y_hat, float* median, int n_signals, const int64_t* row_off, int window, hypad_stream_t stream);
+/* Reconstruction scores (reconstruction_errors :937-961, then stats.zscore -> clip(min=0) + 1 :523-524) of the kinds in `kinds`
+ * (HYPAD_REC_* bits) from the un-rolled truth (fp64) and median (fp32), all vectors in timestep layout; out_* of a kind not asked for
+ * may be NULL.  Per segment: hypad_point_error (inside the smoothing) / hypad_area_error / hypad_dtw_error(score_window), then
+ * hypad_rolling_mean with the signal's own window trunc(n_s * 0.01) at origin 0 (all NaN where that is 0) and hypad_zscore_clip,
+ * every edge taken against the segment's own ends: the same bits as those calls on the segment alone.  Launches per 64 signals: one
+ * per error kernel, four for smoothing and z-score of all kinds together.
+ * workspace: hypad_rec_scores_signals_workspace_bytes(n_signals, row_off, window). */
+#define HYPAD_REC_POINT 1
+#define HYPAD_REC_AREA 2
+#define HYPAD_REC_DTW 4
+size_t hypad_rec_scores_signals_workspace_bytes(int n_signals, const int64_t* row_off, int window);
+int hypad_rec_scores_signals(int kinds, const double* true_unrolled, const float* median, double* out_point, double* out_area,
+                             double* out_dtw, int n_signals, const int64_t* row_off, int window, int score_window, void* workspace,
+                             size_t workspace_bytes, hypad_stream_t stream);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

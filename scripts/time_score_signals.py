@@ -1,8 +1,11 @@
 """Scoring a group of trained hyperbolic signals: the grouped path (score_signals + hyperbolic_scores_signals, one copy back) against the
 per-signal loop (score_windows + hyperbolic_scores per signal, as main._detect runs it), from trained models to final scores on the host.
     python scripts/time_score_signals.py [--cases 1000,5000,20000,ragged] [--reps 5] [--only grouped|per_signal]
-Prints one JSON line per case: median wall ms of each path over --reps (after one warm-up), and whether the final scores are equal bit
-for bit.  Launch counts: run one case under `rocprofv3 --kernel-trace --stats -- python scripts/time_score_signals.py --cases ragged
+``--euclidean [--rec-error dtw] [--all-kinds]``: Euclidean (TadGAN) models instead -- per_signal = the grouped forward, one copy back and
+score_anomalies per signal (what _detect_grouped ran before the grouped Euclidean detector), grouped = score_signals +
+euclidean_scores_signals and one copy back; --all-kinds scores point, area and dtw as a run with model directories does.
+Prints one JSON line per case: median wall ms of each path over --reps (after one warm-up) with the spread of the repetitions, and
+whether the final scores are equal bit for bit.  Launch counts: run one case under `rocprofv3 --kernel-trace --stats -- python scripts/time_score_signals.py --cases ragged
 --reps 1 --only grouped` (and --only per_signal)."""
 import argparse
 import json
@@ -29,6 +32,9 @@ def main():
     ap.add_argument("--cases", default="1000,5000,20000,ragged")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--only", default="")
+    ap.add_argument("--euclidean", action="store_true")
+    ap.add_argument("--rec-error", default="dtw")
+    ap.add_argument("--all-kinds", action="store_true")
     args = ap.parse_args()
     from hypad_amd import anomaly_detection as ad
     from hypad_amd.models import tadgan
@@ -39,7 +45,7 @@ def main():
         models = []
         for k in range(len(counts)):
             torch.manual_seed(k)
-            models.append(tuple(m.cuda().eval() for m in (tadgan.Encoder(S, L), tadgan.Decoder(S, L, True), tadgan.CriticX(S, L))))
+            models.append(tuple(m.cuda().eval() for m in (tadgan.Encoder(S, L), tadgan.Decoder(S, L, not args.euclidean), tadgan.CriticX(S, L))))
         series = []
         for k, n in enumerate(counts):
             t = np.arange(n + S - 1)
@@ -66,7 +72,35 @@ def main():
             f = adu.hyperbolic_scores_signals(r, "mult")
             return ad._to_host({"final": f["final_scores"]})["final"].copy()
 
+        if args.euclidean:
+            # the datasets' window matrices (fp64, host) -- what score_anomalies un-rolls per signal and unroll_true_signals gathers
+            xs = [s.double().cpu().numpy()[np.arange(n)[:, None] + np.arange(S)[None, :]][:, :, None] for s, n in zip(series, counts)]
+            kinds = ("point", "area", "dtw")
+
+            def per_signal():
+                r = ad.score_signals([_View(s, n) for s, n in zip(series, counts)], models, S, L, False)
+                host = ad._to_host({"recons": r["recons"], "critic": r["critic"]})
+                ro, out = r["row_off"], []
+                for k in range(len(counts)):
+                    y_hat, critic = host["recons"][ro[k]: ro[k + 1]], list(host["critic"][ro[k]: ro[k + 1]])
+                    if args.all_kinds:                  # (score_anomalies with a model directory: every kind for its pickle, then the requested one)
+                        for kind in kinds:
+                            adu.zscore_clip(adu.reconstruction_errors(xs[k], y_hat, 1, 10, int(counts[k] * 0.01), True, kind)[0]).cpu().numpy()
+                    out.append(adu.score_anomalies(xs[k], y_hat, critic, None, rec_error_type=args.rec_error, comb="mult", with_true=False)[0])
+                return np.concatenate(out)
+
+            def grouped():
+                r = ad.score_signals([_View(s, n) for s, n in zip(series, counts)], models, S, L, False)
+                f = adu.euclidean_scores_signals(r, adu.unroll_true_signals(xs, r["row_off"], S), args.rec_error, "mult",
+                                                 kinds=kinds if args.all_kinds else None)
+                want = {"final": f["final_scores"]}
+                if args.all_kinds:
+                    want.update(f["rec_scores"], critic_scores=f["critic_scores"])
+                return ad._to_host(want)["final"].copy()
+
         row = {"case": case, "signals": len(counts), "windows": int(sum(counts))}
+        if args.euclidean:
+            row.update(euclidean=True, rec_error=args.rec_error, all_kinds=args.all_kinds)
         finals = {}
         for name, fn in (("per_signal", per_signal), ("grouped", grouped)):
             if args.only and name != args.only:
@@ -79,6 +113,7 @@ def main():
                 fn()
                 ts.append((time.perf_counter() - t0) * 1e3)
             row[name + "_ms"] = round(float(np.median(ts)), 3)
+            row[name + "_min_max_ms"] = [round(float(min(ts)), 3), round(float(max(ts)), 3)]
         if len(finals) == 2:
             row["bit_equal"] = finals["grouped"].tobytes() == finals["per_signal"].tobytes()
             row["speedup"] = round(row["per_signal_ms"] / row["grouped_ms"], 2)

@@ -1,0 +1,164 @@
+"""CPU-only checks of the grouped Euclidean (TadGAN) detector: the new entry points are declared, exported and bound; the timestep
+layout and the host gather of the un-rolled truth against a NumPy loop; which signals main._groupable sends to the group; and the
+argument errors of the new entry points, which come back before anything is launched (no GPU needed)."""
+import ctypes
+import os
+import re
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+
+from hypad_amd import _C
+from hypad_amd.utils import anomaly_detection_utils as adu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = ("hypad_unroll_median_signals", "hypad_rec_scores_signals_workspace_bytes", "hypad_rec_scores_signals")
+EINVAL, EWORKSPACE, EUNSUPPORTED = -1, -2, -3
+
+
+def test_new_entry_points_are_declared_exported_and_bound():
+    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "hypad.h")).read(), flags=re.S)
+    declared = set(re.findall(r"\b(hypad_[a-z0-9_]+)\s*\(", header))
+    for name in NEW:
+        assert name in declared, name
+        assert name in _C.EXPORTS and hasattr(_C.lib, name), name
+    assert _C.lib.hypad_abi_version() == 7
+    for f in ("timestep_offsets", "unroll_true_signals", "euclidean_scores_signals"):
+        assert callable(getattr(adu, f)), f
+    assert _C.REC_KINDS == {"point": 1, "area": 2, "dtw": 4}
+    for kind, bit in _C.REC_KINDS.items():
+        assert re.search(r"#define HYPAD_REC_%s %d\b" % (kind.upper(), bit), header)
+
+
+def test_status_codes_are_the_headers():
+    header = open(os.path.join(ROOT, "include", "hypad.h")).read()
+    for name, v in (("HYPAD_EINVAL", EINVAL), ("HYPAD_EWORKSPACE", EWORKSPACE), ("HYPAD_EUNSUPPORTED", EUNSUPPORTED)):
+        assert re.search(r"%s\s*=?\s*\(?%d\)?" % (name, v), header), name
+
+
+def test_timestep_offsets():
+    assert adu.timestep_offsets([0, 1, 16, 33], 100) == [0, 1 + 99, 16 + 2 * 99, 33 + 3 * 99]
+    assert adu.timestep_offsets([0, 7], 1) == [0, 7]
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_unroll_true_signals_is_the_per_signal_gather(monkeypatch, dtype):
+    S = 12
+    counts = [1, 5, 1, 40, 13]
+    rng = np.random.default_rng(0)
+    row_off = list(np.cumsum([0] + counts))
+    xs, want = [], []
+    for k, n in enumerate(counts):
+        series = rng.standard_normal(n + S - 1).astype(dtype)
+        X = series[np.arange(n)[:, None] + np.arange(S)[None, :]]
+        # a dataset with .X (N, S, 1), or the plain window matrix
+        xs.append(SimpleNamespace(X=X[:, :, None]) if k % 2 == 0 else X)
+        loop = np.empty(n + S - 1, dtype=np.float64)
+        for t in range(n + S - 1):
+            loop[t] = X[t, 0] if t < n else X[n - 1, t - n + 1]
+        assert loop.tobytes() == series.astype(np.float64).tobytes()
+        want.append(loop)
+    got = {}
+    monkeypatch.setattr(adu, "_upload", lambda a: got.setdefault("a", a))
+    out = adu.unroll_true_signals(xs, row_off, S)
+    assert out is got["a"] and out.dtype == np.float64 and out.flags["C_CONTIGUOUS"]
+    assert out.tobytes() == np.concatenate(want).tobytes()
+    t_off = adu.timestep_offsets(row_off, S)
+    for k in range(len(counts)):
+        assert out[t_off[k]: t_off[k + 1]].tobytes() == want[k].tobytes()
+    with pytest.raises(ValueError):
+        adu.unroll_true_signals(xs, list(np.cumsum([0] + counts[::-1])), S)
+
+
+def test_unknown_combination_and_kind_raise_before_any_device_work():
+    res = {"row_off": [0, 3], "recons": None, "critic": None, "hyper_real": None}
+    with pytest.raises(ValueError, match='Unknown combination specified uncertainty, use "mult", "sum", or "rec" instead.'):
+        adu.euclidean_scores_signals(res, None, "dtw", "uncertainty")
+    with pytest.raises(ValueError, match="manhattan"):
+        adu.euclidean_scores_signals(res, None, "manhattan", "mult")
+    with pytest.raises(ValueError, match="l2"):
+        adu.euclidean_scores_signals(res, None, "dtw", "mult", kinds=("point", "l2"))
+
+
+class _DS:
+    def __init__(self, n=5, S=100):
+        self.X = np.zeros((n, S, 1))
+
+    def series_windows(self, device="cuda"):
+        return object(), len(self.X), 1
+
+
+def test_groupable_keeps_cached_euclidean_signals_per_signal(tmp_path):
+    from hypad_amd import main as hmain
+    ds = _DS()
+    eucl = SimpleNamespace(hyperbolic=False, signal="sa", load=False)
+    hyper = SimpleNamespace(hyperbolic=True, signal="sa", load=False)
+    d = tmp_path / "NAB" / "sa"
+    d.mkdir(parents=True)
+    raw = str(d)                                    # the detector's files are named raw + file (train.model_path has no trailing slash)
+    assert hmain._groupable((eucl, ds, ds, None), raw)
+    assert hmain._groupable((eucl, ds, ds, None), "")
+    for cache in ("dtw", "point", "area", "critic_scores"):
+        f = raw + cache + ".pickle"
+        open(f, "wb").close()
+        assert not hmain._groupable((eucl, ds, ds, None), raw), cache
+        assert hmain._groupable((hyper, ds, ds, None), raw), cache       # (hyperbolic: only params.load reads a cache back)
+        os.remove(f)
+    assert hmain._groupable((eucl, ds, ds, None), raw)
+
+
+def _p(v=256):
+    return ctypes.c_void_p(v)
+
+
+def _rec(kinds=7, true=256, med=256, outs=(256, 256, 256), off=(0, 4, 9), n=None, window=100, score_window=10, ws=256, ws_bytes=1 << 40):
+    o = _C.int64s(off)
+    n = len(off) - 1 if n is None else n
+    ptr = lambda v: None if v is None else _p(v)
+    return _C.lib.hypad_rec_scores_signals(kinds, ptr(true), ptr(med), ptr(outs[0]), ptr(outs[1]), ptr(outs[2]), n, o, window, score_window,
+                                           ptr(ws), ws_bytes, None)
+
+
+@pytest.mark.parametrize("off", [[0, 5, 3], [0, 5, 5, 9], [2, 5, 9], [0]])
+def test_bad_offsets_are_rejected_without_a_launch(off):
+    n = len(off) - 1
+    assert _C.lib.hypad_unroll_median_signals(_p(), _p(), n, _C.int64s(off), 100, None) == EINVAL
+    assert _rec(off=off) == EINVAL
+    assert _C.lib.hypad_rec_scores_signals_workspace_bytes(n, _C.int64s(off), 100) == 0
+
+
+def test_other_bad_arguments_are_rejected_without_a_launch():
+    off = _C.int64s([0, 4, 9])
+    um = _C.lib.hypad_unroll_median_signals
+    assert um(None, _p(), 2, off, 100, None) == EINVAL
+    assert um(_p(), None, 2, off, 100, None) == EINVAL
+    assert um(_p(), _p(), 2, off, 0, None) == EINVAL
+    assert um(_p(), _p(), 2, None, 100, None) == EINVAL
+    assert um(_p(), _p(), 2, off, 257, None) == EUNSUPPORTED          # beyond MAX_WINDOW
+    assert _rec(true=None) == EINVAL and _rec(med=None) == EINVAL
+    assert _rec(window=0) == EINVAL
+    assert _rec(kinds=0) == EINVAL and _rec(kinds=8) == EINVAL
+    assert _rec(kinds=1, outs=(None, 256, 256)) == EINVAL             # a requested kind without its output
+    assert _rec(kinds=2, outs=(256, None, 256)) == EINVAL
+    assert _rec(kinds=4, outs=(256, 256, None)) == EINVAL
+    assert _rec(kinds=6, score_window=1) == EINVAL                    # hypad_area_error / hypad_dtw_error: score_window >= 2
+    assert _rec(kinds=4, score_window=12) == EUNSUPPORTED             # DTW length 13 is not instantiated
+    assert _rec(kinds=4, score_window=30) == EUNSUPPORTED
+    need = _C.lib.hypad_rec_scores_signals_workspace_bytes(2, off, 100)
+    assert need >= 2 * (9 + 2 * 99) * 8 + 3 * 2 * _C.STATS_WORKSPACE_BYTES
+    assert _rec(ws_bytes=need - 1) == EWORKSPACE and _rec(ws=None) == EWORKSPACE
+    assert _C.lib.hypad_rec_scores_signals_workspace_bytes(2, off, 0) == 0
+    for rc in (EINVAL, EWORKSPACE, EUNSUPPORTED):
+        with pytest.raises(_C.HypadError):
+            _C.check(rc, "rec_scores_signals")
+
+
+def test_workspace_grows_with_the_group():
+    ws = _C.lib.hypad_rec_scores_signals_workspace_bytes
+    a = ws(2, _C.int64s([0, 50, 1050]), 100)
+    b = ws(3, _C.int64s([0, 50, 1050, 400_000]), 100)
+    assert 0 < a < b
+    # two error vectors + the chunk sums of three kinds (12 bytes per 16 timesteps and kind) + the partials
+    t = 400_000 + 3 * 99
+    assert b >= 2 * 8 * t + 3 * 12 * (t // 16 + t // 256) + 3 * 3 * _C.STATS_WORKSPACE_BYTES
