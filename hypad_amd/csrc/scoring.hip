@@ -1534,6 +1534,528 @@ __global__ __launch_bounds__(256) void zscore_apply_signals_kernel(RecKinds kd, 
     io[i] = (z != z) ? z : fmax(z, 0.0) + 1.0;  // np.clip keeps NaN
   }
 }
+// ---- The critic-score chain of a group (hypad_critic_chain_signals): final_critic_scores :365-404 for every segment at once.  As above,
+// every kernel takes its segment from blockIdx.y (qs_final_signals_kernel: blockIdx.x) and does on it what the single-signal kernel
+// does on that segment alone; the bodies are copies for the reason given at unroll_median_signals_kernel.
+
+// kde_mode_kernel<KPL> per segment: grid (workgroups of the longest segment, segments).  n, the critic values and the modes are the
+// segment's (scalars out of the kernel arguments); a timestep's mode depends on its own segment's values only, so the partition of
+// the timesteps over workgroups does not matter.
+template <int KPL>
+__global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(HYPAD_KDE_WPE, HYPAD_KDE_WPE))) void kde_mode_signals_kernel(
+    const float* __restrict__ critic_all, double* __restrict__ modes_all, SegTable tab, int W) {
+  const int sl = blockIdx.y;
+  const int64_t n = tab.off[sl + 1] - tab.off[sl];
+  if ((int64_t)blockIdx.x * (THREADS / 64) >= n + W - 1) return;                     // (workgroup-uniform: beyond a short segment's end)
+  const float* __restrict__ critic = critic_all + tab.off[sl];
+  double* __restrict__ modes = modes_all + seg_toff(tab, sl, W);
+  constexpr int WMAX = 64 * KPL;                            // the window class: 9 KB of LDS per workgroup and slot, 18 KB at window 100
+  __shared__ double vals[THREADS / 64][WMAX];
+  __shared__ __attribute__((aligned(16))) float vals32[THREADS / 64][WMAX + 4];      // + the padding the fp32 pass reads past the end
+  __shared__ __attribute__((aligned(16))) float nsq32[THREADS / 64][WMAX + 4];       // -(value^2) for the factored form of the fp32 pass
+  __shared__ double terms[THREADS / 64][KDE_CB * WMAX];
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t T = n + W - 1;
+  double* v = vals[wave];
+  float* vf = vals32[wave];
+  float* nf = nsq32[wave];
+  // per-thread constants of the timestep loop, held in SCALAR registers (they are wave-uniform; as vector values the compiler kept them
+  // in scratch memory across the loop: 20 bytes of private segment per lane and two scratch loads per timestep)
+  auto uniform = [](double x) __attribute__((always_inline)) {
+    return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(x)), __builtin_amdgcn_readfirstlane(__double2loint(x)));
+  };
+  // Scott's factor n^(-2/5) for every sample count 1 .. W, one power per thread, once (the 2 (W - 1) edge timesteps have fewer than W
+  // samples; a double-precision pow inside the loop -- ~200 instructions, its 40 polynomial constants hoisted into vector registers
+  // across the loop -- was what this kernel spilled around)
+  __shared__ double scott[WMAX];
+  for (int c = threadIdx.x; c < W && c < WMAX; c += THREADS) scott[c] = pow((double)(c + 1), -0.4);
+  __syncthreads();
+  const double rW1 = uniform(W > 1 ? 1.0 / (double)(W - 1) : 0.0);
+  for (int64_t t = (int64_t)blockIdx.x * (THREADS / 64) + wave; t < T; t += (int64_t)gridDim.x * (THREADS / 64)) {
+    const int j0 = (int)(t - n + 1 > 0 ? t - n + 1 : 0);
+    const int j1 = (int)(t + 1 < W ? t + 1 : W);
+    const int cnt = __builtin_amdgcn_readfirstlane(j1 - j0);      // (wave-uniform: the pair loops below run on scalar counters)
+    double s = 0.0;
+    for (int k = lane; k < cnt; k += 64) {
+      const float xf = critic[t - (j0 + k)];
+      v[k] = (double)xf;
+      vf[k] = xf;
+      s += (double)xf;
+    }
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_s_waitcnt(0xc07f);
+    const double mean = wave_sum(s) / (double)cnt;
+    double q = 0.0;
+    for (int k = lane; k < cnt; k += 64) { const double d = v[k] - mean; q += d * d; }
+    const double var = cnt > 1 ? wave_sum(q) * (cnt == W ? rW1 : 1.0 / (double)(cnt - 1)) : 0.0;      // np.cov: ddof = 1, `c *= 1 / fact`
+    // Scott: factor = n^(-1/5), squared.  (All but the 2 (W - 1) edge timesteps have cnt == W: that power is taken once per
+    // thread, not once per timestep -- a double-precision pow is ~200 instructions.)
+    const double cov = var * uniform(scott[cnt - 1]);
+    double out;
+    if (cnt > 1 && cov > 0.0 && cov == cov) {
+      // pass 1: fp32 densities of this lane's samples.  exp(-d^2 inv) = exp2(-(c d)^2) with c = sqrt(inv log2 e): the samples are
+      // centred and rescaled once (pass 2 reads the fp64 copies), so a pair costs a subtract, a multiply, an exp2 and an add; the
+      // slab is padded with +inf to a multiple of four (a padded pair contributes exp2(-inf) = 0) and read four values at a
+      // time, every value once for all of the lane's samples.
+      // The samples are CENTRED first, in fp64 (densities depend on differences only): rescaling the raw values would leave the
+      // fp32 copies with an absolute error of |value| 2^-24 c, which at |mean| / bandwidth beyond ~1e4 exceeds the screen's margin.
+      // The scale itself only has to be good to fp32 (an error in it is a slightly different bandwidth for every sample alike: 2e-7
+      // relative in the densities): one v_rsq_f32 instead of an fp64 division and square root per timestep; the fp64 1 / (2 cov) that
+      // pass 2 uses is taken only when pass 2 runs.  (A covariance outside the fp32 range makes the screen all-NaN or all-equal: pass 2
+      // then sees every sample, as before.)
+      const double c64 = (double)__builtin_amdgcn_rsqf((float)cov * 1.3862943611198906f);     // sqrt(log2 e / (2 cov))
+      float amax = 0.f;
+      for (int k = lane; k < cnt; k += 64) {
+        const float y = (float)((v[k] - mean) * c64);
+        vf[k] = y; nf[k] = -(y * y);
+        amax = fmaxf(amax, fabsf(y));
+      }
+      amax = wave_max(amax);
+      // (Measured and dropped in round 3, twice: using the kernel matrix's symmetry -- each unordered pair evaluated once.  With the
+      // partner's share delivered by ds_add_f32: 3.28 ms against 0.42 ms for 125 000 windows (LDS float atomics).  With the values
+      // parked in a small LDS matrix in chunks of eight steps and collected by the partners after a wave barrier (no atomics,
+      // conflict-free strides, immediate offsets): 0.69 ms -- three per-lane LDS operations per pair cost more issue time than the
+      // quarter-rate exponential they save; the broadcast form below reads each value once for all 64 lanes.)
+      const bool factored = amax <= 8.f;                   // (wave-uniform; NaN -> the direct form)
+      if (lane < 4 && cnt + lane < ((cnt + 3) & ~3)) {      // padding to a multiple of four: a pair that contributes exp2(-inf) = 0 in either form
+        vf[cnt + lane] = factored && HYPAD_KDE_FACTORED ? 0.f : __int_as_float(0x7f800000);
+        nf[cnt + lane] = __int_as_float(0xff800000);
+      }
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_s_waitcnt(0xc07f);
+      // (Measured and dropped in round 3: giving the cnt % 64 samples of the last slot 64 / b lanes each -- groups of b = 32, 16, ..
+      // samples by the binary digits of the remainder, each lane a share of the values, shares added by xor shuffles: 25 + 13 + 2 steps
+      // of four values per lane at window 100 instead of 25 + 25, 20 % fewer exponentials by counter, and no faster: 0.292 against
+      // 0.287 ms.  Per-lane LDS addresses and the shuffles cost what the idle lanes did.)
+      float d32[KPL], xs[KPL];
+      float acc[KPL][4];                                   // one accumulator per position in the group of four: <= ceil(cnt / 4) terms each
+#pragma unroll
+      for (int u = 0; u < KPL; ++u) {
+        const int k = lane + 64 * u;
+        xs[u] = vf[k < cnt ? k : 0];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[u][c] = 0.f;
+      }
+      const int nu = (cnt + 63) >> 6;                                             // sample slots in use (wave-uniform)
+      if (factored && HYPAD_KDE_FACTORED) {
+        // exp2(-(x - v)^2) = exp2(-x^2) exp2(2 x v - v^2): the pair costs a fused multiply-add (2 x in a register, v and -v^2 from
+        // LDS), an exp2 and an add -- three issue slots instead of four -- and exp2(-x^2) multiplies the finished sum once.
+        // |x|, |v| <= 8 keeps 2 x v - v^2 <= x^2 <= 64 inside the fp32 exponent range and its rounding (the product's and
+        // -v^2's: 2^-24 x 64 each at the very worst) inside the budget written out at the threshold below.
+        float x2[KPL];
+#pragma unroll
+        for (int u = 0; u < KPL; ++u) x2[u] = 2.f * xs[u];
+        for (int m = 0; m < (HYPAD_KDE_EXP == 1 ? 0 : cnt); m += 4) {
+          const float4 q4 = *reinterpret_cast<const float4*>(vf + m);
+          const float4 n4 = *reinterpret_cast<const float4*>(nf + m);
+          const float vm[4] = {q4.x, q4.y, q4.z, q4.w}, nm[4] = {n4.x, n4.y, n4.z, n4.w};
+#pragma unroll
+          for (int u = 0; u < KPL; ++u) {
+            if (u >= nu) continue;
+            // (two fused multiply-adds per instruction: v_pk_fma_f32 -- the same roundings)
+            typedef float v2f __attribute__((ext_vector_type(2)));
+            const v2f xx = {x2[u], x2[u]};
+            const v2f a01 = __builtin_elementwise_fma(xx, v2f{vm[0], vm[1]}, v2f{nm[0], nm[1]});
+            const v2f a23 = __builtin_elementwise_fma(xx, v2f{vm[2], vm[3]}, v2f{nm[2], nm[3]});
+            acc[u][0] += __builtin_amdgcn_exp2f(a01.x); acc[u][1] += __builtin_amdgcn_exp2f(a01.y);
+            acc[u][2] += __builtin_amdgcn_exp2f(a23.x); acc[u][3] += __builtin_amdgcn_exp2f(a23.y);
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < KPL; ++u) d32[u] = ((acc[u][0] + acc[u][1]) + (acc[u][2] + acc[u][3])) * __builtin_amdgcn_exp2f(-(xs[u] * xs[u]));
+      } else {
+        for (int m = 0; m < (HYPAD_KDE_EXP == 1 ? 0 : cnt); m += 4) {
+          const float4 q4 = *reinterpret_cast<const float4*>(vf + m);
+          const float vm[4] = {q4.x, q4.y, q4.z, q4.w};
+#pragma unroll
+          for (int u = 0; u < KPL; ++u) {
+            if (u >= nu) continue;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) { const float d = xs[u] - vm[c]; acc[u][c] += __builtin_amdgcn_exp2f(-(d * d)); }
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < KPL; ++u) d32[u] = (acc[u][0] + acc[u][1]) + (acc[u][2] + acc[u][3]);
+      }
+      if (HYPAD_KDE_EXP == 1) d32[0] = lane == 0 ? 1.f : 0.f;
+      float mx = -1.f;
+#pragma unroll
+      for (int u = 0; u < KPL; ++u) {
+        if (lane + 64 * u >= cnt) d32[u] = -1.f;
+        mx = fmaxf(mx, d32[u]);
+      }
+      mx = wave_max(mx);
+      // Relative error of an fp32 density D~ against the exact D, all terms positive.  Direct form, exp2(-(x - v)^2):
+      //  * arguments: a centred, rescaled sample y carries 2^-24 |y| <= 1e-6 (|y| < 32 for every pair that contributes: two of <= 256
+      //    samples within a few units of each other lie at most 2.6 sqrt(255 / 2) = 29 units from the mean; a lone outlier beyond that
+      //    sees only its own term, exactly 1), a difference d twice that, d^2 an absolute 2 |d| 2e-6 (+ 2^-24 d^2 from the product);
+      //    a term's relative error is ln 2 times that, and weighted by the terms themselves (|d| 2^(-d^2) <= 0.52, the self term is 1)
+      //    the sum's is <= 3e-6;
+      //  * v_exp_f32: 1 ulp = 1.2e-7;
+      //  * accumulation: four partial sums of <= 64 terms, each add 2^-24 of a partial sum that never exceeds the result: 3.8e-6, + 1.2e-7
+      //    for the two combining adds
+      // -> eps <= 7.1e-6 at window 256 (4.8e-6 at 100).  Factored form (all |y| <= 8), exp2(-x^2) exp2(2 x v - v^2):
+      //  * the samples' own rounding (|y| <= 8: 2^-24 x 8): 0.7e-6 by the same weighting;
+      //  * the argument 2 x v - v^2 (|.| <= 64): -v^2 rounded once, the fused multiply-add once, 2^-24 x 64 = 3.8e-6 absolute together
+      //    at the very worst -> ln 2 x 3.8e-6 = 2.6e-6;  exp2(-x^2): x^2 rounded (1.9e-6 absolute -> 1.3e-6) + 1 ulp;
+      //  * v_exp_f32 1.2e-7, accumulation 3.9e-6 as above, the closing product 6e-8
+      // -> eps <= 8.8e-6.  If k* is the true arg-max, D~[k*] >= (1 - eps) D[k*] >= (1 - eps) D[j] >= (1 - eps) / (1 + eps) D~[j] for
+      // every j: the screen keeps k* as long as its margin exceeds 2 eps = 1.8e-5.  Margin 4e-5 (rounds 2-3 used 2e-4 with one
+      // accumulator per sample: 1.7 fp64 evaluations per timestep on random-normal values, 0.6 now).
+      const float thr = mx * (1.f - 4e-5f);
+      // pass 2: fp64 densities of the candidates, in ascending sample order (the first maximum is kept); of every sample if
+      // pass 1 produced no candidate (a bandwidth so small that its reciprocal leaves the fp32 range makes the screen NaN).
+      // A wave pays for a sequential sum as if all 64 lanes ran it, so a candidate's sum is NOT given to one lane with its
+      // exponentials: the lanes compute a candidate's cnt exponentials side by side into LDS (two per lane at window 100), four
+      // candidates per batch, then lane c adds candidate c's terms in index order -- the same additions in the same order as
+      // the one-lane loop, hence the same bits, at 1/20 of its cycles.
+      double best = -1.0;
+      int besti = 0x7fffffff;
+      double* tm = terms[wave];
+      {
+        // one candidate only: the screen has decided (its margin is far above the fp32 pass's error), no fp64 sum is needed
+        int ncand = 0, first = 0x7fffffff;
+#pragma unroll
+        for (int u = 0; u < KPL; ++u) {
+          const unsigned long long mk = __ballot(lane + 64 * u < cnt && d32[u] >= thr);
+          ncand += __builtin_popcountll(mk);
+          if (mk && first == 0x7fffffff) first = __builtin_ctzll(mk) + 64 * u;
+        }
+        if (ncand == 1) besti = first;
+      }
+      double inv = 0.0;
+      if (__builtin_amdgcn_readfirstlane(besti) == 0x7fffffff) inv = 0.5 / cov;          // (only the fp64 pass needs it)
+      for (int round = 0; round < (HYPAD_KDE_EXP == 2 ? 0 : 2) && besti == 0x7fffffff; ++round) {
+        // First the candidates' fp64 densities as TREE sums (a lane's own terms, then the wave's butterfly: no LDS, no sequential add):
+        // either order of adding <= 256 positive terms is within 3e-14 of the exact sum, so a candidate more than 1e-12 below the
+        // largest tree sum cannot be the arg-max of the ordered sums either.  One survivor (the usual case): it is the arg-max, and
+        // the ordered sums -- a lane adding 100 terms one after the other: half of this pass's time -- are not taken at all; several
+        // (equal samples, true near-ties): only those go through the ordered sums below, which decide as before.
+        bool keep[KPL];
+        {
+          double dq[KPL];
+#pragma unroll
+          for (int u = 0; u < KPL; ++u) dq[u] = -1.0;
+#pragma unroll
+          for (int u = 0; u < KPL; ++u) {
+            unsigned long long mask = __ballot(lane + 64 * u < cnt && (round == 1 || d32[u] >= thr));
+            while (mask) {                                                        // wave-uniform
+              const int k = __builtin_ctzll(mask) + 64 * u;
+              mask &= mask - 1;
+              const double xk = v[k];
+              double loc = 0.0;
+              for (int m = lane; m < cnt; m += 64) { const double d = xk - v[m]; loc += exp(-d * d * inv); }
+              const double dp = wave_sum(loc);
+              if (lane == (k & 63)) dq[u] = dp;
+            }
+          }
+          double mx2 = -1.0;
+#pragma unroll
+          for (int u = 0; u < KPL; ++u) mx2 = fmax(mx2, dq[u]);
+#pragma unroll
+          for (int off = 32; off > 0; off >>= 1) mx2 = fmax(mx2, __shfl_xor(mx2, off, WAVE));
+          const double thr2 = mx2 * (1.0 - 1e-12);
+          int nkeep = 0, first = 0x7fffffff;
+#pragma unroll
+          for (int u = 0; u < KPL; ++u) {
+            keep[u] = dq[u] >= thr2 && dq[u] > 0.0;
+            const unsigned long long mk = __ballot(keep[u]);
+            nkeep += __builtin_popcountll(mk);
+            if (mk && first == 0x7fffffff) first = __builtin_ctzll(mk) + 64 * u;
+          }
+          if (nkeep == 1) { besti = first; break; }
+        }
+#pragma unroll
+        for (int u = 0; u < KPL; ++u) {
+          unsigned long long mask = __ballot(keep[u]);
+          while (mask) {                                                          // wave-uniform
+            int kc[KDE_CB];
+            int nb = 0;
+#pragma unroll
+            for (int c = 0; c < KDE_CB; ++c) {
+              kc[c] = -1;
+              if (mask) { kc[c] = __builtin_ctzll(mask) + 64 * u; mask &= mask - 1; nb = c + 1; }
+            }
+#pragma unroll
+            for (int c = 0; c < KDE_CB; ++c) {
+              if (kc[c] < 0) continue;
+              const double xk = v[kc[c]];
+              for (int m = lane; m < cnt; m += 64) { const double d = xk - v[m]; tm[c * WMAX + m] = exp(-d * d * inv); }
+            }
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_s_waitcnt(0xc07f);
+            double dens = -1.0;
+            if (lane < nb) {
+              dens = 0.0;
+              const double* tp = tm + lane * WMAX;
+              int m = 0;
+              for (; m + 8 <= cnt; m += 8) {                 // (the terms of eight steps requested together; added in index order)
+                double t8[8];
+#pragma unroll
+                for (int x = 0; x < 8; ++x) t8[x] = tp[m + x];
+#pragma unroll
+                for (int x = 0; x < 8; ++x) dens += t8[x];
+              }
+              for (; m < cnt; ++m) dens += tp[m];
+            }
+#pragma unroll
+            for (int c = 0; c < KDE_CB; ++c) {
+              const double dc = __shfl(dens, c, WAVE);
+              if (c < nb && dc > best) { best = dc; besti = kc[c]; }
+            }
+            __builtin_amdgcn_wave_barrier();
+          }
+        }
+      }
+      out = v[besti < cnt ? besti : 0];                    // (all densities NaN -- a covariance whose reciprocal overflows: scipy's arg-max of NaNs is 0)
+    } else {
+      // median by rank counting (cnt <= 256)
+      double lo = 0.0, hi = 0.0;
+      for (int k = lane; k < cnt; k += 64) {
+        const double xk = v[k];
+        int rank = 0;
+        for (int m = 0; m < cnt; ++m) rank += (v[m] < xk) || (v[m] == xk && m < k);
+        if (rank == (cnt - 1) / 2) lo = xk;
+        if (rank == cnt / 2) hi = xk;
+      }
+      out = 0.5 * (wave_sum(lo) + wave_sum(hi));
+    }
+    if (lane == 0) modes[t] = out;
+    __builtin_amdgcn_wave_barrier();
+  }
+}
+
+// ---- np.quantile of every segment at once: the radix selection above with one workspace slice per segment of the launch.  Histogram
+// counts are integers and the result an exact order statistic: the grid shape cannot change it.  Workspace of a call (slices = the
+// segments of one launch, at most SEG_CHUNK; the chunks of a larger group run one after the other through the same slices):
+// [slices x (histograms of the QS_PRE global levels | 128 bytes: NaN count, list lengths, list extremes)]  -- zeroed by qs_zero_kernel,
+// [slices x (QsState table | candidate lists)].
+constexpr size_t QSS_HIST_BYTES = (size_t)QS_PRE * QS_SEL * QS_BINS * sizeof(unsigned int);
+constexpr size_t QSS_ZERO_BYTES = QSS_HIST_BYTES + 128;
+constexpr size_t QSS_REST_BYTES = QS_STATE_BYTES + (size_t)QS_SEL * QS_CAND * sizeof(unsigned long long);
+static_assert(QSS_ZERO_BYTES % 8 == 0 && QSS_REST_BYTES % 8 == 0, "slices keep 8-byte alignment");
+struct QsSegs { char* ws; int slices; int nsel; double q0, q1; };
+__device__ __forceinline__ QsWs qs_ws_seg(const QsSegs& a, int sl) {
+  QsWs w;
+  char* z = a.ws + (size_t)sl * QSS_ZERO_BYTES;
+  char* r = a.ws + (size_t)a.slices * QSS_ZERO_BYTES + (size_t)sl * QSS_REST_BYTES;
+  w.hist = (unsigned int*)z; w.nan_count = (unsigned int*)(z + QSS_HIST_BYTES); w.cand_count = (unsigned int*)(z + QSS_HIST_BYTES + 16);
+  w.kmax = (unsigned long long*)(z + QSS_HIST_BYTES + 32); w.kinv = (unsigned long long*)(z + QSS_HIST_BYTES + 64);
+  w.state = (QsState*)r; w.cand = (unsigned long long*)(r + QS_STATE_BYTES);
+  return w;
+}
+// qs_position on the device: the same fp64 operations, each rounded on its own (the product must not fuse into the subtraction)
+__device__ __forceinline__ void qs_position_dev(int64_t n, double q, long long* lo, long long* hi, double* frac) {
+#pragma clang fp contract(off)
+  const double pos = (double)(n - 1) * q;
+  const double f = floor(pos);
+  long long l = (long long)f;
+  *frac = pos - f;
+  if (pos >= (double)(n - 1)) { *lo = n - 1; *hi = n - 1; return; }
+  if (l < 0) l = 0;
+  *lo = l; *hi = l + 1 > n - 1 ? n - 1 : l + 1;
+}
+// qs_level_kernel per segment: grid (blocks of the longest segment, segments); a block with no value of its segment leaves (block 0
+// always has one and writes the level's state)
+__global__ __launch_bounds__(256) void qs_level_signals_kernel(const double* __restrict__ in_all, QsSegs a, SegTable tab, int window, int level) {
+  __shared__ unsigned int h[QS_SEL][QS_BINS];
+  __shared__ QsState cur[QS_SEL];
+  const int sl = blockIdx.y;
+  const int64_t n = tab.off[sl + 1] - tab.off[sl] + window - 1;
+  constexpr int PER = 4;                                  // values per thread and round: requested together, then filed
+  int64_t base = (int64_t)blockIdx.x * (256 * PER);
+  if (base >= n) return;                                  // (workgroup-uniform)
+  const double* __restrict__ in = in_all + seg_toff(tab, sl, window);
+  const QsWs ws = qs_ws_seg(a, sl);
+  const int nsel = a.nsel;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  double x[PER];
+#pragma unroll
+  for (int u = 0; u < PER; ++u) { const int64_t i = base + u * 256 + threadIdx.x; x[u] = i < n ? in[i] : 0.0; }
+  if (wave < nsel) {
+    QsState st;
+    if (level == 0) {
+      long long lo, hi; double fr;
+      qs_position_dev(n, wave < 2 ? a.q0 : a.q1, &lo, &hi, &fr);
+      st.prefix = 0; st.rank = (wave & 1) ? hi : lo;
+    }
+    else st = qs_descend(ws.hist + ((size_t)(level - 1) * QS_SEL + wave) * QS_BINS, level - 1, ws.state[(level - 1) * QS_SEL + wave], h[wave]);
+    if (lane == 0) { cur[wave] = st; if (blockIdx.x == 0) ws.state[level * QS_SEL + wave] = st; }
+  }
+  __syncthreads();                                                                  // (h doubled as the scan's staging rows)
+  for (int i = threadIdx.x; i < QS_SEL * QS_BINS; i += 256) (&h[0][0])[i] = 0u;
+  __syncthreads();
+  const int sh = qs_shift(level), bins = qs_bins(level);
+  const int hi_sh = sh + (level == QS_LEVELS - 1 ? 64 - QS_BITS * (QS_LEVELS - 1) : QS_BITS);     // bits above the digit
+  unsigned long long pre[QS_SEL];
+  for (int s2 = 0; s2 < QS_SEL; ++s2) pre[s2] = s2 < nsel ? cur[s2].prefix : 0;
+  unsigned int nans = 0;
+  for (; base < n; base += (int64_t)gridDim.x * (256 * PER)) {
+#pragma unroll
+    for (int u = 0; u < PER; ++u) {
+      if (base + u * 256 + threadIdx.x >= n) continue;
+      if (level == 0 && x[u] != x[u]) ++nans;
+      const unsigned long long k = qs_key(x[u]);
+      const unsigned int digit = (unsigned int)(k >> sh) & (unsigned int)(bins - 1);
+#pragma unroll
+      for (int s2 = 0; s2 < QS_SEL; ++s2)
+        if (s2 < nsel && (hi_sh >= 64 || ((k ^ pre[s2]) >> hi_sh) == 0)) atomicAdd(&h[s2][digit], 1u);
+    }
+    const int64_t nb = base + (int64_t)gridDim.x * (256 * PER);
+#pragma unroll
+    for (int u = 0; u < PER; ++u) { const int64_t i = nb + u * 256 + threadIdx.x; x[u] = i < n ? in[i] : 0.0; }
+  }
+  if (level == 0 && nans) atomicAdd(ws.nan_count, nans);
+  __syncthreads();
+  unsigned int* g = ws.hist + (size_t)level * QS_SEL * QS_BINS;
+  for (int i = threadIdx.x; i < nsel * QS_BINS; i += 256) {
+    const unsigned int c = (&h[0][0])[i];
+    if (c) atomicAdd(g + i, c);
+  }
+}
+// qs_compact_kernel per segment
+__global__ __launch_bounds__(256) void qs_compact_signals_kernel(const double* __restrict__ in_all, QsSegs a, SegTable tab, int window) {
+  __shared__ unsigned int h[QS_SEL][QS_BINS];
+  __shared__ QsState cur[QS_SEL];
+  const int sl = blockIdx.y;
+  const int64_t n = tab.off[sl + 1] - tab.off[sl] + window - 1;
+  constexpr int PER = 4;
+  int64_t base = (int64_t)blockIdx.x * (256 * PER);
+  if (base >= n) return;                                  // (workgroup-uniform)
+  const double* __restrict__ in = in_all + seg_toff(tab, sl, window);
+  const QsWs ws = qs_ws_seg(a, sl);
+  const int nsel = a.nsel;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  double x[PER];
+#pragma unroll
+  for (int u = 0; u < PER; ++u) { const int64_t i = base + u * 256 + threadIdx.x; x[u] = i < n ? in[i] : 0.0; }
+  if (wave < nsel) {
+    const QsState st = qs_descend(ws.hist + ((size_t)(QS_PRE - 1) * QS_SEL + wave) * QS_BINS, QS_PRE - 1, ws.state[(QS_PRE - 1) * QS_SEL + wave], h[wave]);
+    if (lane == 0) { cur[wave] = st; if (blockIdx.x == 0) ws.state[QS_PRE * QS_SEL + wave] = st; }
+  }
+  __syncthreads();
+  const int hi_sh = qs_shift(QS_PRE - 1);                 // the 33 bits fixed so far sit above it
+  unsigned long long pre[QS_SEL];
+  for (int s2 = 0; s2 < QS_SEL; ++s2) pre[s2] = s2 < nsel ? cur[s2].prefix : 0;
+  for (; base < n; base += (int64_t)gridDim.x * (256 * PER)) {
+#pragma unroll
+    for (int u = 0; u < PER; ++u) {
+      if (base + u * 256 + threadIdx.x >= n) continue;
+      const unsigned long long k = qs_key(x[u]);
+#pragma unroll
+      for (int s2 = 0; s2 < QS_SEL; ++s2)
+        if (s2 < nsel && ((k ^ pre[s2]) >> hi_sh) == 0) {
+          const unsigned int pos = atomicAdd(ws.cand_count + s2, 1u);
+          if (pos < (unsigned int)QS_CAND) ws.cand[(size_t)s2 * QS_CAND + pos] = k;
+          atomicMax(ws.kmax + s2, k);
+          atomicMax(ws.kinv + s2, ~k);
+        }
+    }
+    const int64_t nb = base + (int64_t)gridDim.x * (256 * PER);
+#pragma unroll
+    for (int u = 0; u < PER; ++u) { const int64_t i = nb + u * 256 + threadIdx.x; x[u] = i < n ? in[i] : 0.0; }
+  }
+}
+// qs_final_kernel, one workgroup of 1 024 threads per segment (blockIdx.x): segment s's quantiles go to out[(seg0 + s) * nq ..]; a list
+// longer than QS_CAND falls back to the segment's own input range
+__global__ __launch_bounds__(1024) void qs_final_signals_kernel(const double* __restrict__ in_all, QsSegs a, SegTable tab, int window,
+                                                                  double* __restrict__ out_all) {
+  __shared__ unsigned long long keys[QS_SEL];
+  __shared__ unsigned int stage[QS_SEL][QS_BINS];
+  __shared__ QsState cur[QS_SEL];
+  const int sl = blockIdx.x;
+  const int64_t n = tab.off[sl + 1] - tab.off[sl] + window - 1;
+  const double* __restrict__ in = in_all + seg_toff(tab, sl, window);
+  const QsWs ws = qs_ws_seg(a, sl);
+  const int nsel = a.nsel;
+  double* __restrict__ out = out_all + (size_t)(tab.seg0 + sl) * (nsel / 2);
+  const int grp = threadIdx.x >> 8, tg = threadIdx.x & 255, lane = threadIdx.x & 63;
+  const bool live = grp < nsel;
+  QsState st = ws.state[QS_PRE * QS_SEL + (live ? grp : 0)];
+  const unsigned int c = live ? ws.cand_count[grp] : 0u;
+  const unsigned long long kmx = live ? ws.kmax[grp] : 0ull, kmn = live ? ~ws.kinv[grp] : 0ull;
+  const bool decided = !live || kmx == kmn;                // (group-uniform) every candidate is the same key
+  const bool listed = c <= (unsigned int)QS_CAND;
+  const unsigned long long* cand = ws.cand + (size_t)(live ? grp : 0) * QS_CAND;
+  const int64_t m = decided ? 0 : (listed ? (int64_t)c : n);
+  unsigned int* hst = stage[live ? grp : 0];
+  for (int level = QS_PRE; level < QS_LEVELS; ++level) {   // (block-uniform trip count; a decided group only keeps the barriers)
+    const int bins = qs_bins(level), sh = qs_shift(level);
+    const int hi_sh = sh + (level == QS_LEVELS - 1 ? 64 - QS_BITS * (QS_LEVELS - 1) : QS_BITS);     // bits above the digit (<= 31)
+    for (int i = tg; i < bins; i += 256) hst[i] = 0u;
+    __syncthreads();
+    for (int64_t i0 = 0; i0 < m; i0 += 4 * 256) {          // four loads in flight per thread
+      unsigned long long k[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int64_t i = i0 + u * 256 + tg;
+        k[u] = i < m ? (listed ? cand[i] : qs_key(in[i])) : ~st.prefix;      // (~prefix never matches)
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (((k[u] ^ st.prefix) >> hi_sh) == 0) atomicAdd(hst + ((unsigned int)(k[u] >> sh) & (unsigned int)(bins - 1)), 1u);
+    }
+    __syncthreads();
+    if (tg < 64 && !decided) {                             // the group's first wave scans its histogram
+      const QsState nx = qs_descend_staged(hst, level, st);
+      if (lane == 0) cur[grp] = nx;
+    }
+    __syncthreads();
+    if (!decided) st = cur[grp];
+  }
+  if (live && tg == 0) keys[grp] = decided ? kmx : st.prefix;
+  __syncthreads();
+  if (threadIdx.x < nsel / 2) {
+    const int j = threadIdx.x;
+    long long lo, hi; double fr;
+    qs_position_dev(n, j == 0 ? a.q0 : a.q1, &lo, &hi, &fr);
+    double r = np_lerp64(qs_value(keys[2 * j]), qs_value(keys[2 * j + 1]), fr);
+    if (*ws.nan_count) r = __longlong_as_double(0x7ff8000000000000ll);
+    out[j] = r;
+  }
+}
+
+// stat_partials_kernel<true> per segment: the segment cut into stat_blocks(T_s) slices (grid.x = STAT_G: the blocks beyond them leave),
+// [lo, hi] = the segment's quantiles in the device table `range` ((seg0 + s) * 2), partials at [s][STAT_G]
+__global__ __launch_bounds__(256) void critic_partials_signals_kernel(const double* __restrict__ in_all, const double* __restrict__ range,
+                                                                        StatPart* __restrict__ parts_all, SegTable tab, int window) {
+  __shared__ double sh[4];
+  const int sl = blockIdx.y;
+  const int64_t T = tab.off[sl + 1] - tab.off[sl] + window - 1;
+  const int nb = stat_blocks_of(T);
+  if ((int)blockIdx.x >= nb) return;                                                  // (workgroup-uniform)
+  const double* __restrict__ in = in_all + seg_toff(tab, sl, window);
+  const double lo = range[2 * (tab.seg0 + sl)], hi = range[2 * (tab.seg0 + sl) + 1];
+  const int64_t len = (T + nb - 1) / nb;
+  const int64_t b = (int64_t)blockIdx.x * len, e = b + len < T ? b + len : T;
+  double s = 0.0, rs = 0.0, rc = 0.0;
+  for (int64_t i = b + threadIdx.x; i < e; i += 256) {
+    const double x = in[i];
+    s += x;
+    if (x >= lo && x <= hi) { rs += x; rc += 1.0; }
+  }
+  const double n = e > b ? (double)(e - b) : 0.0;
+  const double mean = n > 0.0 ? block_sum_256(s, sh) / n : 0.0;
+  double q = 0.0;
+  for (int64_t i = b + threadIdx.x; i < e; i += 256) { const double d = in[i] - mean; q += d * d; }
+  q = block_sum_256(q, sh);
+  rs = block_sum_256(rs, sh); rc = block_sum_256(rc, sh);
+  if (threadIdx.x == 0) { StatPart p; p.n = n; p.mean = mean; p.m2 = q; p.rsum = rs; p.rcnt = rc; parts_all[(size_t)sl * STAT_G + blockIdx.x] = p; }
+}
+// critic_apply_kernel per segment
+__global__ __launch_bounds__(256) void critic_apply_signals_kernel(const double* __restrict__ in_all, const StatPart* __restrict__ parts_all,
+                                                                     double* __restrict__ out_all, SegTable tab, int window) {
+  __shared__ StatPart sh[STAT_G];
+  const int sl = blockIdx.y;
+  const int64_t to = seg_toff(tab, sl, window), T = tab.off[sl + 1] - tab.off[sl] + window - 1;
+  if ((int64_t)blockIdx.x * 256 >= T) return;                                         // (workgroup-uniform)
+  const double* __restrict__ in = in_all + to;
+  double* __restrict__ out = out_all + to;
+  const StatPart st = stat_merge_all(parts_all + (size_t)sl * STAT_G, stat_blocks_of(T), sh);
+  const double mean = st.rsum / st.rcnt, sd = sqrt(st.m2 / st.n);
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < T; i += (int64_t)gridDim.x * 256)
+    out[i] = fabs((in[i] - mean) / sd) + 1.0;
+}
 inline SegTable seg_table(const int64_t* row_off, int c0, int n_signals) {
   SegTable t{};
   t.n = std::min(SEG_CHUNK, n_signals - c0); t.seg0 = c0;
@@ -1544,6 +2066,49 @@ inline int64_t seg_longest(const SegTable& t) {
   int64_t most = 0;
   for (int i = 0; i < t.n; ++i) most = std::max<int64_t>(most, t.off[i + 1] - t.off[i]);
   return most;
+}
+// workspace of hypad_quantiles_signals (the layout is written out at QSS_HIST_BYTES)
+inline int qs_slices(int n_signals) { return std::min(n_signals, SEG_CHUNK); }
+inline size_t qss_bytes(int n_signals) { return (size_t)qs_slices(n_signals) * (QSS_ZERO_BYTES + QSS_REST_BYTES); }
+// the six launches of launch_quantiles for the segments of one table (timestep layout), quantiles to out[(seg0 + s) * nq ..]
+int launch_quantiles_signals(const double* in, const SegTable& t, int slices, int window, const double* q, int nq, double* out, void* workspace,
+                             hipStream_t s) {
+  const QsSegs a{(char*)workspace, slices, 2 * nq, q[0], nq > 1 ? q[1] : 0.0};
+  // (a kernel, not a memset node: see launch_quantiles; the zeroed regions of the launch's slices are contiguous)
+  const int words = (int)((size_t)t.n * QSS_ZERO_BYTES / 4);
+  hipLaunchKernelGGL(qs_zero_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, s, (unsigned*)workspace, words);
+  HYPAD_CHECK_LAUNCH();
+  int64_t g = (seg_longest(t) + window - 1 + 1023) / 1024;
+  g = g < 1 ? 1 : (g > 1024 ? 1024 : g);
+  const dim3 grid((unsigned)g, (unsigned)t.n);
+  for (int level = 0; level < QS_PRE; ++level) {
+    hipLaunchKernelGGL(qs_level_signals_kernel, grid, dim3(256), 0, s, in, a, t, window, level);
+    HYPAD_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL(qs_compact_signals_kernel, grid, dim3(256), 0, s, in, a, t, window);
+  HYPAD_CHECK_LAUNCH();
+  hipLaunchKernelGGL(qs_final_signals_kernel, dim3((unsigned)t.n), dim3(1024), 0, s, in, a, t, window, out);
+  HYPAD_CHECK_LAUNCH();
+  return HYPAD_OK;
+}
+// workspace of hypad_critic_chain_signals: [quantile slices | [q25, q75] per segment | STAT_G partials per slice | the rolling mean's
+// 16- and 256-chunk sums, then their counts (slots as in RecKinds) | the unsmoothed scores | the modes when the caller keeps none]
+struct ChainWsLayout { int slices; int64_t total, cap1, cap2; size_t qs, range, parts, sums, counts, tmp, modes, bytes; };
+ChainWsLayout chain_ws_layout(int n_signals, const int64_t* row_off, int window) {
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  ChainWsLayout l;
+  l.slices = qs_slices(n_signals);
+  l.total = row_off[n_signals] + (int64_t)n_signals * (window - 1);
+  l.cap1 = (l.total >> 4) + 2 * (int64_t)n_signals + 2; l.cap2 = (l.total >> 8) + 2 * (int64_t)n_signals + 2;
+  l.qs = 0;
+  l.range = up(qss_bytes(n_signals));
+  l.parts = l.range + up((size_t)n_signals * 2 * sizeof(double));
+  l.sums = l.parts + up((size_t)l.slices * STAT_G * sizeof(StatPart));
+  l.counts = l.sums + (size_t)(l.cap1 + l.cap2) * sizeof(double);
+  l.tmp = up(l.counts + (size_t)(l.cap1 + l.cap2) * sizeof(int));
+  l.modes = l.tmp + up((size_t)l.total * sizeof(double));
+  l.bytes = l.modes + up((size_t)l.total * sizeof(double));
+  return l;
 }
 // workspace of hypad_rec_scores_signals: [area errors | dtw errors] (timestep layout) | per kind [16-chunk sums | 256-chunk sums] | their
 // counts | per kind and segment STAT_G partials
@@ -1888,6 +2453,73 @@ int hypad_rec_scores_signals(int kinds, const double* true_unrolled, const float
     hipLaunchKernelGGL(stat_partials_signals_kernel, dim3(STAT_G, (unsigned)t.n, (unsigned)nk), dim3(256), 0, st, kd, t, window);
     HYPAD_CHECK_LAUNCH();
     hipLaunchKernelGGL(zscore_apply_signals_kernel, dim3(grid_for(most, 1024), (unsigned)t.n, (unsigned)nk), dim3(256), 0, st, kd, t, window);
+    HYPAD_CHECK_LAUNCH();
+  }
+  return HYPAD_OK;
+}
+
+size_t hypad_quantiles_signals_workspace_bytes(int n_signals) { return n_signals < 1 ? 0 : qss_bytes(n_signals); }
+int hypad_quantiles_signals(const double* in, int n_signals, const int64_t* row_off, int window, const double* q, int nq, double* out,
+                            void* workspace, size_t workspace_bytes, hypad_stream_t s) {
+  const int rc = seg_check(n_signals, row_off);
+  if (rc) return rc;
+  if (!in || !q || !out || window <= 0 || nq < 1) return HYPAD_EINVAL;
+  if (nq > 2) return HYPAD_EUNSUPPORTED;
+  for (int i = 0; i < n_signals; ++i) if (row_off[i + 1] - row_off[i] + window - 1 > ((int64_t)1 << 31)) return HYPAD_EUNSUPPORTED;
+  for (int j = 0; j < nq; ++j) if (!(q[j] >= 0.0 && q[j] <= 1.0)) return HYPAD_EINVAL;
+  if (!workspace || workspace_bytes < qss_bytes(n_signals)) return HYPAD_EWORKSPACE;
+  for (int c0 = 0; c0 < n_signals; c0 += SEG_CHUNK) {
+    const int r = launch_quantiles_signals(in, seg_table(row_off, c0, n_signals), qs_slices(n_signals), window, q, nq, out, workspace, (hipStream_t)s);
+    if (r) return r;
+  }
+  return HYPAD_OK;
+}
+size_t hypad_critic_chain_signals_workspace_bytes(int n_signals, const int64_t* row_off, int window) {
+  if (seg_check(n_signals, row_off) || window <= 0) return 0;
+  return chain_ws_layout(n_signals, row_off, window).bytes;
+}
+int hypad_critic_chain_signals(const float* critic, double* modes_out, double* out, int n_signals, const int64_t* row_off, int window,
+                               void* workspace, size_t workspace_bytes, hypad_stream_t s) {
+  const int rc = seg_check(n_signals, row_off);
+  if (rc) return rc;
+  if (!critic || !out || window <= 0) return HYPAD_EINVAL;
+  if (window > MAX_WINDOW) return HYPAD_EUNSUPPORTED;
+  for (int i = 0; i < n_signals; ++i) if (row_off[i + 1] - row_off[i] + window - 1 > ((int64_t)1 << 31)) return HYPAD_EUNSUPPORTED;
+  const ChainWsLayout l = chain_ws_layout(n_signals, row_off, window);
+  if (!workspace || workspace_bytes < l.bytes) return HYPAD_EWORKSPACE;
+  char* ws = (char*)workspace;
+  double* modes = modes_out ? modes_out : (double*)(ws + l.modes);
+  double* range = (double*)(ws + l.range);
+  double* tmp = (double*)(ws + l.tmp);
+  StatPart* parts = (StatPart*)(ws + l.parts);
+  RecKinds kd{};                                               // one kind: the unsmoothed scores, no subtrahend
+  kd.src[0] = RollSrc{tmp, nullptr}; kd.out[0] = out;
+  kd.s1[0] = (double*)(ws + l.sums); kd.s2[0] = kd.s1[0] + l.cap1;
+  kd.c1[0] = (int*)(ws + l.counts); kd.c2[0] = kd.c1[0] + l.cap1;
+  const hipStream_t st = (hipStream_t)s;
+  const double q[2] = {0.25, 0.75};
+  for (int c0 = 0; c0 < n_signals; c0 += SEG_CHUNK) {          // eleven launches per SEG_CHUNK signals
+    const SegTable t = seg_table(row_off, c0, n_signals);
+    const int64_t most = seg_longest(t) + window - 1;
+    const dim3 gk(grid_for(most, THREADS / 64), (unsigned)t.n), b(THREADS);
+    switch ((window + 63) / 64) {
+      case 1: hipLaunchKernelGGL(kde_mode_signals_kernel<1>, gk, b, 0, st, critic, modes, t, window); break;
+      case 2: hipLaunchKernelGGL(kde_mode_signals_kernel<2>, gk, b, 0, st, critic, modes, t, window); break;
+      case 3: hipLaunchKernelGGL(kde_mode_signals_kernel<3>, gk, b, 0, st, critic, modes, t, window); break;
+      default: hipLaunchKernelGGL(kde_mode_signals_kernel<4>, gk, b, 0, st, critic, modes, t, window); break;
+    }
+    HYPAD_CHECK_LAUNCH();
+    const int r = launch_quantiles_signals(modes, t, l.slices, window, q, 2, range, ws + l.qs, st);
+    if (r) return r;
+    hipLaunchKernelGGL(critic_partials_signals_kernel, dim3(STAT_G, (unsigned)t.n), dim3(256), 0, st, modes, range, parts, t, window);
+    HYPAD_CHECK_LAUNCH();
+    hipLaunchKernelGGL(critic_apply_signals_kernel, dim3(grid_for(most, 1024), (unsigned)t.n), dim3(256), 0, st, modes, parts, tmp, t, window);
+    HYPAD_CHECK_LAUNCH();
+    // (the smoothing of hypad_rec_scores_signals with one kind: each segment's own window trunc(n_s * 0.01), NaN fill at 0)
+    const unsigned gc = (unsigned)((((most - 1) >> 8) + 1 + 15) / 16);
+    hipLaunchKernelGGL(roll_chunks_signals_kernel, dim3(gc, (unsigned)t.n, 1), b, 0, st, kd, t, window);
+    HYPAD_CHECK_LAUNCH();
+    hipLaunchKernelGGL(rolling_mean_signals_kernel, dim3(grid_for(most, THREADS), (unsigned)t.n, 1), b, 0, st, kd, t, window);
     HYPAD_CHECK_LAUNCH();
   }
   return HYPAD_OK;

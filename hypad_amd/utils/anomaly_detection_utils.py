@@ -434,10 +434,32 @@ def multivariate_anomaly_detection(recons_signal, true_signal, params, combinati
     return out
 
 
+def final_critic_scores_signals(critic, row_off, window, with_modes=False):
+    """final_critic_scores (:365-404) of every signal of a group in one C call (hypad_critic_chain_signals: at most eleven launches
+    per 64 signals): ``critic`` the (sum n_s,) window-critic values of all signals in row order on the device, ``row_off`` the host
+    offsets, ``window`` the signal shape.  Returns the scores in timestep layout, (sum (n_s + window - 1),) fp64 on the device --
+    signal s's are final_critic_scores' on it alone, bit for bit (all NaN where trunc(n_s * 0.01) is 0) -- and with ``with_modes``
+    also the KDE modes in the same layout.  Nothing passes through the host."""
+    row_off = [int(v) for v in row_off]
+    k, w = len(row_off) - 1, int(window)
+    entries = critic.numel() if isinstance(critic, torch.Tensor) else np.asarray(critic).size
+    if entries != row_off[-1]:
+        raise ValueError(f"critic has {entries} entries, the offsets say {row_off[-1]} windows")
+    c = _f32(critic).reshape(-1)
+    offs = _C.int64s(row_off)
+    out = torch.empty(row_off[-1] + k * (w - 1), device=c.device, dtype=torch.float64)
+    modes = torch.empty_like(out) if with_modes else None
+    nbytes = _C.lib.hypad_critic_chain_signals_workspace_bytes(k, offs, w)
+    ws = _scratch(c.device, nbytes, "critic_chain_signals")
+    _C.check(_C.lib.hypad_critic_chain_signals(_C.ptr(c), _C.ptr(modes), _C.ptr(out), k, offs, w, ws.data_ptr(), nbytes, _C.stream()),
+             "critic_chain_signals")
+    return (out, modes) if with_modes else out
+
+
 def hyperbolic_scores_signals(res, combination="mult"):
     """hyperbolic_scores for every signal of a score_signals result at once (no cache files): the row-wise Poincare distance over all
-    rows, per signal the KDE modes of its critic values (hypad_kde_mode_signals), its quantile-trimmed |z| + 1 and its own centred
-    rolling mean (hypad_critic_score_signals), then the combination (hypad_combine_scores_signals) -- each signal's numbers those of
+    rows, per signal the KDE modes of its critic values, its quantile-trimmed |z| + 1 and its own centred rolling mean
+    (final_critic_scores_signals: hypad_critic_chain_signals), then the combination (hypad_combine_scores_signals) -- each signal's numbers those of
     hyperbolic_scores on it alone, bit for bit, nothing through the host.
     Returns dict(final_scores (sum n_s,) fp64, critic_scores (sum (n_s + S - 1),) fp64 or None -- signal s's final_critic_scores at
     row_off[s] + s (S - 1) --, row_off) on the device."""
@@ -454,13 +476,7 @@ def hyperbolic_scores_signals(res, combination="mult"):
     rec = rec if rec.dtype == torch.float64 else rec.to(torch.float64)
     critic_scores = None
     if combination in ("mult", "uncertainty", "sum", "sum_uncertainty", "critic", "critic_uncertainty"):
-        modes = torch.empty(row_off[-1] + k * (w - 1), device=recons.device, dtype=torch.float64)
-        _C.check(_C.lib.hypad_kde_mode_signals(_C.ptr(_f32(res["critic"]).reshape(-1)), _C.ptr(modes), k, offs, w, _C.stream()), "kde_mode_signals")
-        critic_scores = torch.empty_like(modes)
-        nbytes = _C.lib.hypad_critic_score_signals_workspace_bytes(k, offs, w)
-        ws = _scratch(modes.device, nbytes, "critic_score_signals")
-        _C.check(_C.lib.hypad_critic_score_signals(_C.ptr(modes), _C.ptr(critic_scores), k, offs, w, ws.data_ptr(), nbytes, _C.stream()),
-                 "critic_score_signals")
+        critic_scores = final_critic_scores_signals(res["critic"], row_off, w)
     u = row_norms(recons) if "uncertainty" in combination else None
     out = torch.empty(row_off[-1], device=recons.device, dtype=torch.float64)
     _C.check(_C.lib.hypad_combine_scores_signals(_C.COMB[combination], _C.ptr(critic_scores), _C.ptr(rec), _C.ptr(u), _C.ptr(out), k, offs, w,
@@ -501,7 +517,7 @@ def euclidean_scores_signals(res, true_unrolled, rec_error_type="dtw", comb="mul
     """score_anomalies (:407-576, no cache files) for every signal of a Euclidean score_signals result at once, everything in
     timestep layout and nothing through the host: the anti-diagonal medians of all reconstructions (hypad_unroll_median_signals),
     the z-scored reconstruction scores of ``kinds`` (default: the requested one; hypad_rec_scores_signals), beside them the critic
-    chain of final_critic_scores (hypad_kde_mode_signals + hypad_critic_score_signals; ``with_critic``: default unless comb is
+    chain of final_critic_scores (final_critic_scores_signals: hypad_critic_chain_signals; ``with_critic``: default unless comb is
     "rec"), then the combination over the whole vector.  Each signal's numbers are score_anomalies' on it alone, bit for bit.
     ``true_unrolled``: unroll_true_signals of the group.
     Returns dict(final_scores, critic_scores (or None), rec_scores {kind: tensor}, row_off, t_off); tensors fp64 on the device."""
@@ -542,14 +558,7 @@ def euclidean_scores_signals(res, true_unrolled, rec_error_type="dtw", comb="mul
         return rec[kind]
 
     def critic_branch():
-        modes = torch.empty(total, device=recons.device, dtype=torch.float64)
-        _C.check(_C.lib.hypad_kde_mode_signals(_C.ptr(_f32(res["critic"]).reshape(-1)), _C.ptr(modes), k_sig, offs, w, _C.stream()), "kde_mode_signals")
-        out = torch.empty_like(modes)
-        nbytes = _C.lib.hypad_critic_score_signals_workspace_bytes(k_sig, offs, w)
-        ws = _scratch(modes.device, nbytes, "critic_score_signals")
-        _C.check(_C.lib.hypad_critic_score_signals(_C.ptr(modes), _C.ptr(out), k_sig, offs, w, ws.data_ptr(), nbytes, _C.stream()),
-                 "critic_score_signals")
-        return out
+        return final_critic_scores_signals(res["critic"], row_off, w)
 
     if with_critic:                  # (the critic chain on a side stream beside the reconstruction scores, as score_anomalies runs them)
         r, c = concurrently(rec_branch, critic_branch)

@@ -579,6 +579,23 @@ size_t hypad_rec_scores_signals_workspace_bytes(int n_signals, const int64_t* ro
 int hypad_rec_scores_signals(int kinds, const double* true_unrolled, const float* median, double* out_point, double* out_area,
                              double* out_dtw, int n_signals, const int64_t* row_off, int window, int score_window, void* workspace,
                              size_t workspace_bytes, hypad_stream_t stream);
+/* np.quantile(., q) (method "linear", nq <= 2) of every segment of `in` (fp64, timestep layout) at once: :319-320
+ * (`np.quantile(critics, 0.25)`, `np.quantile(critics, 0.75)`) for a group.  out: (n_signals, nq) fp64 ON THE DEVICE; segment s's row
+ * equals hypad_quantiles on that segment alone (exact order statistics; a NaN in a segment makes that segment's row NaN, no other's).
+ * Six launches per 64 signals.  Argument checks as hypad_quantiles', plus the offsets'.
+ * workspace: hypad_quantiles_signals_workspace_bytes(n_signals). */
+size_t hypad_quantiles_signals_workspace_bytes(int n_signals);
+int hypad_quantiles_signals(const double* in, int n_signals, const int64_t* row_off, int window, const double* q, int nq, double* out,
+                            void* workspace, size_t workspace_bytes, hypad_stream_t stream);
+/* final_critic_scores :365-404 per signal, whole (KDE step :374-400, _compute_critic_score :307-333): segment s of `out` (timestep
+ * layout, fp64) equals hypad_kde_mode -> hypad_critic_score -> hypad_rolling_mean with the signal's own window trunc(n_s * 0.01) (all
+ * NaN where that is 0) on critic[row_off[s] .. row_off[s + 1]) alone, bit for bit -- what hypad_kde_mode_signals followed by
+ * hypad_critic_score_signals give, in at most eleven launches per 64 signals instead of about eleven per signal.  modes_out: NULL, or
+ * the KDE modes (timestep layout, fp64; what hypad_kde_mode_signals writes).  No launch when an argument check fails.
+ * workspace: hypad_critic_chain_signals_workspace_bytes(n_signals, row_off, window). */
+size_t hypad_critic_chain_signals_workspace_bytes(int n_signals, const int64_t* row_off, int window);
+int hypad_critic_chain_signals(const float* critic, double* modes_out, double* out, int n_signals, const int64_t* row_off, int window,
+                               void* workspace, size_t workspace_bytes, hypad_stream_t stream);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

@@ -5,7 +5,9 @@ per-signal loop (score_windows + hyperbolic_scores per signal, as main._detect r
 score_anomalies per signal (what _detect_grouped ran before the grouped Euclidean detector), grouped = score_signals +
 euclidean_scores_signals and one copy back; --all-kinds scores point, area and dtw as a run with model directories does.
 Prints one JSON line per case: median wall ms of each path over --reps (after one warm-up) with the spread of the repetitions, and
-whether the final scores are equal bit for bit.  Launch counts: run one case under `rocprofv3 --kernel-trace --stats -- python scripts/time_score_signals.py --cases ragged
+whether the final scores are equal bit for bit.  ``--chain``: the critic-score chain alone on the same cases -- per_segment =
+hypad_kde_mode_signals + hypad_critic_score_signals (one set of launches per signal), segmented = hypad_critic_chain_signals; seeded
+critic values on the device, device tensors in and out, one synchronise at the end of each repetition.  Launch counts: run one case under `rocprofv3 --kernel-trace --stats -- python scripts/time_score_signals.py --cases ragged
 --reps 1 --only grouped` (and --only per_signal)."""
 import argparse
 import json
@@ -27,6 +29,54 @@ def _case(name, rng):
     return [int(name)] * 32
 
 
+def chain_alone(args):
+    """The critic-score chain of a group without the forward, the combination and the copy back."""
+    from hypad_amd import _C
+    rng = np.random.default_rng(0)
+    for case in args.cases.split(","):
+        counts = _case(case, rng)
+        row_off = [int(v) for v in np.cumsum([0] + counts)]
+        k = len(counts)
+        offs = _C.int64s(row_off)
+        critic = torch.randn(row_off[-1], device="cuda", generator=torch.Generator(device="cuda").manual_seed(0))
+        total = row_off[-1] + k * (S - 1)
+        modes, out = (torch.empty(total, device="cuda", dtype=torch.float64) for _ in range(2))
+        nb_old = _C.lib.hypad_critic_score_signals_workspace_bytes(k, offs, S)
+        nb_new = _C.lib.hypad_critic_chain_signals_workspace_bytes(k, offs, S)
+        ws = torch.empty(max(nb_old, nb_new), dtype=torch.uint8, device="cuda")
+
+        def per_segment():
+            _C.check(_C.lib.hypad_kde_mode_signals(_C.ptr(critic), _C.ptr(modes), k, offs, S, _C.stream()), "kde_mode_signals")
+            _C.check(_C.lib.hypad_critic_score_signals(_C.ptr(modes), _C.ptr(out), k, offs, S, ws.data_ptr(), nb_old, _C.stream()),
+                     "critic_score_signals")
+
+        def segmented():
+            _C.check(_C.lib.hypad_critic_chain_signals(_C.ptr(critic), _C.ptr(modes), _C.ptr(out), k, offs, S, ws.data_ptr(), nb_new, _C.stream()),
+                     "critic_chain_signals")
+
+        row = {"case": case, "chain_only": True, "signals": k, "windows": int(sum(counts))}
+        results = {}
+        for name, fn in (("per_segment", per_segment), ("segmented", segmented)):
+            if args.only and name != args.only:
+                continue
+            fn()
+            torch.cuda.synchronize()
+            results[name] = (modes.clone(), out.clone())
+            ts = []
+            for _ in range(args.reps):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                ts.append((time.perf_counter() - t0) * 1e3)
+            row[name + "_ms"] = round(float(np.median(ts)), 3)
+            row[name + "_min_max_ms"] = [round(float(min(ts)), 3), round(float(max(ts)), 3)]
+        if len(results) == 2:
+            row["bit_equal"] = all(torch.equal(a.view(torch.int64), b.view(torch.int64)) for a, b in zip(results["per_segment"], results["segmented"]))
+            row["speedup"] = round(row["per_segment_ms"] / row["segmented_ms"], 2)
+        print(json.dumps(row), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", default="1000,5000,20000,ragged")
@@ -35,7 +85,10 @@ def main():
     ap.add_argument("--euclidean", action="store_true")
     ap.add_argument("--rec-error", default="dtw")
     ap.add_argument("--all-kinds", action="store_true")
+    ap.add_argument("--chain", action="store_true")
     args = ap.parse_args()
+    if args.chain:
+        return chain_alone(args)
     from hypad_amd import anomaly_detection as ad
     from hypad_amd.models import tadgan
     from hypad_amd.utils import anomaly_detection_utils as adu
