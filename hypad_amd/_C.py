@@ -198,6 +198,9 @@ _SIGS = {
     "hypad_quantiles_signals": (c_int, [P, c_int, POINTER(c_int64), c_int, P, c_int, P, c_void_p, c_size_t, P]),
     "hypad_critic_chain_signals_workspace_bytes": (c_size_t, [c_int, POINTER(c_int64), c_int]),
     "hypad_critic_chain_signals": (c_int, [P, P, P, c_int, POINTER(c_int64), c_int, c_void_p, c_size_t, P]),
+    "hypad_find_anomalies_signals_workspace_bytes": (c_size_t, [c_int, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), c_int]),
+    "hypad_find_anomalies_signals": (c_int, [P, c_int, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), c_int64, c_double, c_int, P, P, P,
+                                             c_int, c_void_p, c_size_t, P]),
 }
 EXPORTS = tuple(_SIGS)
 for _name, (_res, _args) in _SIGS.items():

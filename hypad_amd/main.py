@@ -74,13 +74,14 @@ def _detect(params, test_dataset, read_path, encoder, decoder, critic_x, path, d
     return out
 
 
-def run_signals(params, names, config_path=None, data_dir="./data", log=print, grouped_scoring=True):
+def run_signals(params, names, config_path=None, data_dir="./data", log=print, grouped_scoring=True, device_intervals=False):
     """One model per signal for a list of signals (``--signals a,b,c``): datasets -> ``train.train_signals_resident`` (groups of up
     to 32 models per launch sequence; under ``torchrun`` the signals are sharded over the ranks, one process per GPU) -> the test
     loop and the detector on the rank that trained each signal -> the metrics of all signals gathered on every rank.
     ``grouped_scoring`` (default): the signals this rank trained are scored together (_detect_grouped: one grouped forward, the
     hyperbolic critic chain per segment, one copy back), with the same numbers and artefacts as the per-signal ``_detect`` loop
-    (``grouped_scoring=False``, ``--per-signal-scoring``)."""
+    (``grouped_scoring=False``, ``--per-signal-scoring``).  ``device_intervals`` (``--device-intervals``, grouped scoring only): the
+    anomalous intervals of the group come from the device as well (find_anomalies_signals) instead of one host find_anomalies per signal."""
     import copy
 
     from . import parallel as par
@@ -94,7 +95,9 @@ def run_signals(params, names, config_path=None, data_dir="./data", log=print, g
     trained = ht.train_signals_resident([t[1] for t in sets], params, names=names, log=log)
     local = {}
     group = [(t, name) for t, name in zip(sets, names) if trained[name].get("modules") is not None and _groupable(t, trained[name]["path"])]
-    outs = _detect_grouped(group, trained, data_dir, log) if grouped_scoring and group else {}
+    if device_intervals and not grouped_scoring:
+        raise ValueError("device_intervals needs grouped scoring")
+    outs = _detect_grouped(group, trained, data_dir, log, device_intervals=device_intervals) if grouped_scoring and group else {}
     for (p, train_ds, test_ds, read_path), name in zip(sets, names):
         mods = trained[name].get("modules")
         if mods is None:
@@ -125,13 +128,15 @@ def _groupable(t, path):
     return test_ds.series_windows("cpu") is not None and len(test_ds.X) > 0
 
 
-def _detect_grouped(group, trained, data_dir, log):
+def _detect_grouped(group, trained, data_dir, log, device_intervals=False):
     """_detect for several trained signals at once: one score_signals call (pack, critic and forward launches for all of them), for
     hyperbolic models hyperbolic_scores_signals, everything back in one page-locked copy and one wait; then per signal on the host
     the cache files test_tadgan writes, critic_scores.pickle, and detect_intervals (anomalies.csv, counts, metrics, results row) --
     the same contents as _detect's.  Euclidean models: euclidean_scores_signals (the un-roll, the reconstruction scores -- all three
     kinds when a model directory keeps score_anomalies' pickles -- and the critic chain of all signals, in timestep layout), one
-    copy back, then the pickles and detect_intervals per signal; the reconstruction matrix comes back only for recons_signal.pt."""
+    copy back, then the pickles and detect_intervals per signal; the reconstruction matrix comes back only for recons_signal.pt.
+    ``device_intervals``: find_anomalies_signals extracts every signal's intervals from the final scores before the copy back, and
+    detect_intervals takes them instead of running find_anomalies."""
     import pickle
 
     import pandas as pd
@@ -163,6 +168,11 @@ def _detect_grouped(group, trained, data_dir, log):
         if keep:
             want["critic_scores"] = comb["critic_scores"]
             want.update({kind: v for kind, v in comb["rec_scores"].items()})
+    found = [None] * len(group)
+    if device_intervals:                                      # (the detector's settings: univariate_anomaly_detection :89-95)
+        found = adu.find_anomalies_signals(comb["final_scores"], row_off if hyp else t_off,
+                                           index_list=[_true_index(t[2], t[0]) for t, _ in group], window_size_portion=0.33,
+                                           window_step_size_portion=0.1)
     host = anomaly_detection._to_host(want)
     outs = {}
     for k, ((p, _, test_ds, read_path), name) in enumerate(group):
@@ -189,13 +199,13 @@ def _detect_grouped(group, trained, data_dir, log):
             if raw and "critic_scores" in host:                # (compute_critic_scores' cache, the signal's whole segment)
                 with open(raw + "critic_scores.pickle", "wb") as f:
                     pickle.dump(host["critic_scores"][a + k * (S - 1): b + (k + 1) * (S - 1)], f, protocol=pickle.HIGHEST_PROTOCOL)
-            out = adu.detect_intervals(host["final"][a:b], p, raw, _true_index(test_ds, p), known, p.signal)
+            out = adu.detect_intervals(host["final"][a:b], p, raw, _true_index(test_ds, p), known, p.signal, intervals=found[k])
         else:
             ta, tb = t_off[k], t_off[k + 1]
             if raw:                                            # (score_anomalies' caches: the arrays and the protocol it writes)
                 for f in ("critic_scores", "point", "area", "dtw"):
                     adu._dump_pickle(host[f][ta:tb].copy(), raw + f + ".pickle")
-            out = adu.detect_intervals(host["final"][ta:tb], p, raw, _true_index(test_ds, p), known, p.signal)
+            out = adu.detect_intervals(host["final"][ta:tb], p, raw, _true_index(test_ds, p), known, p.signal, intervals=found[k])
         log("predicted intervals:\n{}".format(out["intervals"]))
         log("tn, fp, fn, tp: {}".format(out["confusion"]))
         if out["metrics"]:
@@ -224,7 +234,12 @@ def main(argv=None):
                                                                "signals are sharded over the ranks")
     ap.add_argument("--per-signal-scoring", action="store_true", help="with --signals: score the trained signals one by one (the test loop "
                                                                          "and the detector per signal) instead of as one group")
+    ap.add_argument("--device-intervals", action="store_true", help="with --signals and grouped scoring: extract the anomalous intervals of "
+                                                                     "the group on the device (find_anomalies_signals) instead of "
+                                                                     "one host find_anomalies per signal")
     args = ap.parse_args(argv)
+    if args.device_intervals and (not args.signals or args.per_signal_scoring):
+        ap.error("--device-intervals needs --signals and grouped scoring (no --per-signal-scoring)")
     params = SimpleNamespace(**yaml.load(open(args.config), Loader=yaml.FullLoader))
     if args.signals:
         import os
@@ -237,7 +252,7 @@ def main(argv=None):
             own_group = True
         try:
             res = run_signals(params, [n.strip() for n in args.signals.split(",") if n.strip()], args.config, args.data_dir,
-                              grouped_scoring=not args.per_signal_scoring)
+                              grouped_scoring=not args.per_signal_scoring, device_intervals=args.device_intervals)
         finally:
             if own_group:
                 dist.destroy_process_group()

@@ -380,14 +380,16 @@ def univariate_anomaly_detection(recons_signal, true_signal, params, combination
     return detect_intervals(final_scores, params, path, true_index, known_anomalies, signal)
 
 
-def detect_intervals(final_scores, params, path=None, true_index=None, known_anomalies=None, signal=None):
+def detect_intervals(final_scores, params, path=None, true_index=None, known_anomalies=None, signal=None, intervals=None):
     """The host tail of univariate_anomaly_detection (:87-127) from the final scores on: intervals, ``anomalies.csv``, the
-    overlap-segment counts and metrics, the results table row."""
+    overlap-segment counts and metrics, the results table row.  ``intervals``: the signal's (n, 3) rows when they were already
+    extracted (find_anomalies_signals on the device); find_anomalies is skipped then."""
     final_scores = np.asarray(final_scores, dtype=np.float64).reshape(-1)
     if true_index is None:
         true_index = np.arange(final_scores.size)
-    intervals = find_anomalies(final_scores, true_index, window_size_portion=0.33, window_step_size_portion=0.1,
-                               fixed_threshold=True)
+    if intervals is None:
+        intervals = find_anomalies(final_scores, true_index, window_size_portion=0.33, window_step_size_portion=0.1,
+                                   fixed_threshold=True)
     out = dict(final_scores=final_scores, intervals=np.asarray(intervals, dtype=np.float64).reshape(-1, 3), confusion=[0, 0, 0, 0],
                metrics=None)
     if path:
@@ -567,3 +569,86 @@ def euclidean_scores_signals(res, true_unrolled, rec_error_type="dtw", comb="mul
     final = torch.empty(total, device=recons.device, dtype=torch.float64)
     _C.check(_C.lib.hypad_combine_scores(_C.COMB[mode], _C.ptr(c), _C.ptr(r), None, _C.ptr(final), total, _C.stream()), "combine")
     return {"final_scores": final, "critic_scores": c, "rec_scores": rec, "row_off": row_off, "t_off": t_off}
+
+
+FA_ZERO_WEIGHT, FA_OVERFLOW, FA_INTERNAL = 1, 2, 4         # HYPAD_FA_* (include/hypad.h)
+
+
+def _per_signal(value, k, name):
+    if value is None or np.isscalar(value):
+        return [value] * k
+    value = list(value)
+    if len(value) != k:
+        raise ValueError(f"{name}: {len(value)} entries for {k} signals")
+    return value
+
+
+def find_anomalies_signals(scores, seg_off, index_list=None, window_size_portion=None, window_step_size_portion=None, window_size=None,
+                           window_step_size=None, min_percent=0.1, anomaly_padding=50, lower_threshold=False, fixed_threshold=True,
+                           capacity=64):
+    """find_anomalies (:1363-1472, fixed threshold) of every signal of a group in one C call (hypad_find_anomalies_signals: four
+    launches per 64 signals, five with ``lower_threshold``) and one copy back.  ``scores``: the fp64 score vector of all signals on the
+    device; ``seg_off``: the host offsets of the signals' segments in it -- ``row_off`` for hyperbolic results, ``t_off`` for Euclidean
+    ones.  ``window_size`` / ``window_step_size``: one value or one per signal; the portions give each signal's own
+    int(np.ceil(n * portion)) as find_anomalies computes them.  ``index_list``: per signal the index its positions are looked up in
+    (None: the positions themselves).  ``capacity``: table rows per signal of the first attempt; a signal with more intervals makes
+    the call run once more with room for the largest count.
+    Returns a list of (n_i, 3) float64 arrays [index[start], index[stop], score], one per signal: interval bounds equal
+    find_anomalies', scores up to the order of the fp64 sums.  Raises ZeroDivisionError where find_anomalies does (touching
+    zero-length sequences, :1302) and ValueError for ``fixed_threshold=False`` (the Nelder-Mead threshold stays on the host)."""
+    if not fixed_threshold:
+        raise ValueError("find_anomalies_signals computes the fixed threshold only (fixed_threshold=True); the dynamic threshold is "
+                         "intervals.find_anomalies on the host")
+    seg_off = [int(v) for v in seg_off]
+    k = len(seg_off) - 1
+    if k < 1:
+        raise ValueError("seg_off needs at least two entries")
+    if not isinstance(scores, torch.Tensor):
+        scores = _upload(np.asarray(scores, dtype=np.float64).reshape(-1))
+    scores = _C.require_cuda(scores.reshape(-1), "scores", torch.float64)
+    if scores.numel() != seg_off[-1]:
+        raise ValueError(f"scores has {scores.numel()} entries, the offsets say {seg_off[-1]}")
+    sizes, steps = [], []
+    for s, (ws, st) in enumerate(zip(_per_signal(window_size, k, "window_size"), _per_signal(window_step_size, k, "window_step_size"))):
+        n = seg_off[s + 1] - seg_off[s]
+        ws = ws or n                                         # (the arithmetic of find_anomalies :1420-1428)
+        if window_size_portion:
+            ws = int(np.ceil(n * window_size_portion))
+        st = st or ws
+        if window_step_size_portion:
+            st = int(np.ceil(ws * window_step_size_portion))
+        sizes.append(int(ws))
+        steps.append(int(st))
+    offs, wsz, wst = _C.int64s(seg_off), _C.int64s(sizes), _C.int64s(steps)
+    nbytes = _C.lib.hypad_find_anomalies_signals_workspace_bytes(k, offs, wsz, wst, int(bool(lower_threshold)))
+    ws_buf = _scratch(scores.device, nbytes, "find_anomalies_signals")
+    capacity = max(int(capacity), 1)
+    while True:
+        # one buffer, one copy: [tables (k, capacity, 3) fp64 | counts (k,) int32 | status (k,) int32]
+        buf = torch.empty(k * capacity * 24 + k * 8, dtype=torch.uint8, device=scores.device)
+        base = buf.data_ptr()
+        p_counts = base + k * capacity * 24
+        _C.check(_C.lib.hypad_find_anomalies_signals(_C.ptr(scores), k, offs, wsz, wst, int(anomaly_padding), float(min_percent),
+                                                     int(bool(lower_threshold)), ctypes.c_void_p(base), ctypes.c_void_p(p_counts),
+                                                     ctypes.c_void_p(p_counts + k * 4), capacity, ws_buf.data_ptr(), nbytes, _C.stream()),
+                 "find_anomalies_signals")
+        host = buf.cpu().numpy()
+        tables = host[: k * capacity * 24].view(np.float64).reshape(k, capacity, 3)
+        counts = host[k * capacity * 24: k * capacity * 24 + k * 4].view(np.int32)
+        status = host[k * capacity * 24 + k * 4:].view(np.int32)
+        if (status & FA_INTERNAL).any():
+            raise _C.HypadError("find_anomalies_signals: a window holds more values above its threshold than the workspace plans for")
+        if (status & FA_ZERO_WEIGHT).any():
+            raise ZeroDivisionError("Weights sum to zero, can't be normalized")
+        if not (status & FA_OVERFLOW).any():
+            break
+        capacity = int(counts.max())
+    out = []
+    for s in range(k):
+        rows = tables[s, : int(counts[s])].copy()
+        if index_list is not None and index_list[s] is not None and rows.shape[0]:
+            index = np.asarray(index_list[s])
+            rows[:, 0] = index[rows[:, 0].astype(np.int64)]
+            rows[:, 1] = index[rows[:, 1].astype(np.int64)]
+        out.append(rows)
+    return out

@@ -596,6 +596,29 @@ int hypad_quantiles_signals(const double* in, int n_signals, const int64_t* row_
 size_t hypad_critic_chain_signals_workspace_bytes(int n_signals, const int64_t* row_off, int window);
 int hypad_critic_chain_signals(const float* critic, double* modes_out, double* out, int n_signals, const int64_t* row_off, int window,
                                void* workspace, size_t workspace_bytes, hypad_stream_t stream);
+/* find_anomalies :1363-1472 with fixed_threshold=True (_fixed_threshold :1098-1114, _find_sequences / _get_max_errors /
+ * _prune_anomalies / _compute_scores / _merge_sequences :1117-1313) of every segment of `scores` (fp64, on the device) at once.
+ * seg_off (n_signals + 1, HOST): any ascending offsets from 0 -- row_off for window-layout scores, the timestep-layout offsets for
+ * Euclidean ones.  window_size / window_step (n_signals, HOST): each signal's integer window and step, as the caller's
+ * int(np.ceil(n * portion)) gives them; window k of a signal is [k step, min(k step + size, n)) while the previous window ended before n.
+ * Per window: mean and population standard deviation by two-pass fp64 reductions (a constant window has std 0), threshold
+ * mean + 4 std, the runs of `x > threshold` dilated by anomaly_padding, each run's maximum and the maximum outside the runs, the
+ * prune by min_percent (a NaN ratio keeps), the scores (max - threshold) / (mean + std); with lower_threshold the same again on
+ * 2 mean - x.  A window that holds a NaN yields nothing.  Per signal the kept runs are merged by start (touching or overlapping
+ * runs join; score = sum w s / sum w, w = stop - start).
+ * out: (n_signals, capacity, 3) fp64 rows (start, stop, score), positions relative to the segment; counts[s]: the signal's merged
+ * intervals (all of them, also beyond capacity); status[s]: HYPAD_FA_* bits.  Rows from min(counts[s], capacity) on are not written.
+ * All three ON THE DEVICE.  No floating-point atomics; a signal's rows do not depend on the group it is scored in.  Four launches
+ * per 64 signals (five with lower_threshold), whatever the number of windows.  No launch when an argument check fails.
+ * workspace: hypad_find_anomalies_signals_workspace_bytes(n_signals, seg_off, window_size, window_step, lower_threshold) (0: bad arguments). */
+#define HYPAD_FA_ZERO_WEIGHT 1   /* a merged group's first two weights are 0: np.average raises ZeroDivisionError there (:1302) */
+#define HYPAD_FA_OVERFLOW 2      /* counts[s] > capacity */
+#define HYPAD_FA_INTERNAL 4      /* more values above mean + 4 std than window / 16 + 2 (impossible by Chebyshev's bound) */
+size_t hypad_find_anomalies_signals_workspace_bytes(int n_signals, const int64_t* seg_off, const int64_t* window_size,
+                                                    const int64_t* window_step, int lower_threshold);
+int hypad_find_anomalies_signals(const double* scores, int n_signals, const int64_t* seg_off, const int64_t* window_size,
+                                 const int64_t* window_step, int64_t anomaly_padding, double min_percent, int lower_threshold, double* out,
+                                 int* counts, int* status, int capacity, void* workspace, size_t workspace_bytes, hypad_stream_t stream);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop
