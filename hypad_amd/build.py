@@ -17,6 +17,7 @@ LIB = os.path.join(LIB_DIR, "libhypad_hip.so")
 DEV_LIB = os.path.join(LIB_DIR, "libhypad_hip_dev.so")
 SOURCES = ["api_misc.hip", "ops_hyper.hip", "ops_dense.hip", "lstm_seq.hip", "train_iters.hip", "critic_fused.hip", "scoring.hip", "intervals.hip", "host_rng.cpp"]
 DEV_SOURCES = SOURCES + ["diag.hip"]
+LLVM_BIN = os.environ.get("HYPAD_LLVM_BIN", "/opt/rocm/lib/llvm/bin")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-fvisibility=hidden", "-std=c++17", "-Wno-pass-failed", "-Wno-unused-result"]
 
 
@@ -92,21 +93,29 @@ def _build_locked(verbose, dev):
     return lib
 
 
+def gfx950_code_object(obj, dst):
+    """Un-bundle the gfx950 code object of a host object file built above (its .hip_fatbin section, with the ROCm LLVM tools)
+    into the file `dst`; False if the object holds no device code."""
+    fat = dst + ".fatbin"
+    subprocess.check_call(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", obj, fat])
+    if not os.path.exists(fat) or os.path.getsize(fat) == 0:
+        return False
+    subprocess.check_call([os.path.join(LLVM_BIN, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + fat,
+                           "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + dst], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    return True
+
+
 def kernel_metadata(obj):
     """[{name, vgpr_count, vgpr_spill_count, sgpr_count, sgpr_spill_count, private_segment_fixed_size, group_segment_fixed_size, ...}]
-    of the gfx950 code object inside a host object file built above (the .hip_fatbin section, un-bundled with the ROCm LLVM tools;
-    names demangled): what tests/test_cabi_and_host.py holds the compile-time instantiations to."""
+    of the gfx950 code object inside a host object file built above (names demangled): what tests/test_cabi_and_host.py holds the
+    compile-time instantiations to."""
     import re
     import tempfile
-    llvm = os.environ.get("HYPAD_LLVM_BIN", "/opt/rocm/lib/llvm/bin")
     with tempfile.TemporaryDirectory() as d:
-        fat, co = os.path.join(d, "fat.bin"), os.path.join(d, "gfx950.co")
-        subprocess.check_call(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", obj, fat])
-        if not os.path.exists(fat) or os.path.getsize(fat) == 0:
+        co = os.path.join(d, "gfx950.co")
+        if not gfx950_code_object(obj, co):
             return []
-        subprocess.check_call([os.path.join(llvm, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + fat,
-                               "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-        notes = subprocess.run([os.path.join(llvm, "llvm-readelf"), "--notes", co], capture_output=True, text=True, check=True).stdout
+        notes = subprocess.run([os.path.join(LLVM_BIN, "llvm-readelf"), "--notes", co], capture_output=True, text=True, check=True).stdout
     out, cur = [], None
     for line in notes.splitlines():                          # (kernel entries: "  - .agpr_count: 0" then "    .key: value" lines; nested lists sit deeper)
         m = re.match(r"^  ([- ]) \.(\w+):\s*(.*)$", line)

@@ -338,18 +338,16 @@ __device__ __forceinline__ void precompute_body(const IterArgs& ax, const IterAr
                          __HIP_MEMORY_SCOPE_AGENT);
   }
 }
-#ifndef HYPAD_PRE_WPE
-#define HYPAD_PRE_WPE 4
-#endif
+constexpr int PRE_WPE = 4;
 template <int SC, int LC>
-__global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(HYPAD_PRE_WPE, HYPAD_PRE_WPE))) void critic_phase_precompute_kernel(IterArgs ax, IterArgs az, PhaseArgs ph) {
+__global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(PRE_WPE, PRE_WPE))) void critic_phase_precompute_kernel(IterArgs ax, IterArgs az, PhaseArgs ph) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   precompute_body<false, SC, LC>(ax, az, ph, smem, blockIdx.x, blockIdx.y, ph.only < 0 ? blockIdx.z >> 1 : blockIdx.z, ph.only < 0 ? blockIdx.z & 1 : ph.only,
                                  gridDim.y);
 }
 // encoder(x) of every window row of every model -> hypad_epoch_io.enc_table (PhaseArgs.enc_table): one workgroup per 16 rows
 template <int SC, int LC>
-__global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(HYPAD_PRE_WPE, HYPAD_PRE_WPE))) void encoder_table_kernel(IterArgs az, float* table, int64_t rows) {
+__global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(PRE_WPE, PRE_WPE))) void encoder_table_kernel(IterArgs az, float* table, int64_t rows) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int S = SC ? SC : az.S, L = LC ? LC : az.L;
   const PreLds lp = pre_lds(S);
@@ -955,27 +953,6 @@ __global__ __launch_bounds__(FT) void critic_iteration_kernel(IterArgs ax, IterA
 #else
 #define PSTAMP(k) do { } while (0)
 #endif
-#ifndef HYPAD_R6_BATCH
-#define HYPAD_R6_BATCH 1
-#endif
-#ifndef HYPAD_R6_G
-#define HYPAD_R6_G 1
-#endif
-#ifndef HYPAD_R6_STAGE
-#define HYPAD_R6_STAGE 1
-#endif
-#ifndef HYPAD_R6_EOFF
-#define HYPAD_R6_EOFF 1
-#endif
-#ifndef HYPAD_R6_TOFF
-#define HYPAD_R6_TOFF 1
-#endif
-#ifndef HYPAD_R6_HOIST
-#define HYPAD_R6_HOIST 1
-#endif
-#ifndef HYPAD_R6_FWD0P
-#define HYPAD_R6_FWD0P 1
-#endif
 constexpr int PSLOT = 4;                     // Adam-state quads per thread
 constexpr int MAXCH = 21;                    // chunks whose granules one wave sweeps in one pass (3 x 21 <= 64 lanes)
 constexpr unsigned SPIN_LIMIT = 1u << 21;    // bounded waits: ~1 s of polling
@@ -1197,7 +1174,6 @@ __device__ __forceinline__ void critic_persistent_body(const IterArgs& a, const 
     request_record(0);
   }
 
-#if HYPAD_R6_EOFF
   // Byte offset of this lane's quad of every tile it owns inside a merged share (or an offset past the descriptor's range: the hardware
   // drops that store -- lanes outside the tile's valid quads, tiles past the list, wave 2).  Once per launch: inside the loop the tile
   // arithmetic, its exec masks and the spilled scalars behind them cost ~400 cycles per tile and iteration (round 6, shader-clock stamps).
@@ -1212,11 +1188,10 @@ __device__ __forceinline__ void critic_persistent_body(const IterArgs& a, const 
     const int e = li == 0 ? qq * C0 + k : (li < nh ? I0 + (li - 1) * Ih + qq * Ch + k : I0 + (nh - 1) * Ih + k);
     eoff[i] = (t < g.ntiles && wave != 2 && n < N && k <= K) ? e * 16 : (int)0x80000000u;      // (past the 2 GB range whatever is added)
   }
-#endif
   // ... and the LDS offsets (floats from `smem`) of its operand rows in every tile: left = the layer's deltas at column n0 + j, right = the
   // layer's input rows at column k0 + j (row 0 of the tile; the k-steps add row strides).  Windows up to 100 only: eight more registers
   // make the window-123 build spill 4 (it is 1.3 % faster with them all the same) and cost the window-150 build 5 % (41 spilled).
-  constexpr bool TOFF = HYPAD_R6_TOFF && SC != 0 && SC <= 100;
+  constexpr bool TOFF = SC != 0 && SC <= 100;
   int lofs[TOFF ? TPW : 1], rofs[TOFF ? TPW : 1];
 #pragma unroll
   for (int i = 0; i < (TOFF ? TPW : 0); ++i) {
@@ -1340,18 +1315,14 @@ __device__ __forceinline__ void critic_persistent_body(const IterArgs& a, const 
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         if (n + r >= N) continue;
-#if HYPAD_R6_HOIST
         if (it > 0) adam_update_hoisted(pv[u][r], mv[u][r], vv[u][r], gsum[r], co, isb2, lrb1);
-#else
-        if (it > 0) adam_update(pv[u][r], mv[u][r], vv[u][r], gsum[r], co);
-#endif
         const float pw = pv[u][r];
         float* wdst = li == 0 ? w0 + (n + r) * ldin + k : (li < nh ? wh + ((li - 1) * L + n + r) * LQ + k : wl + k);
         *wdst = pw;
         if (li > 0 && li < nh && k < L) whT[((li - 1) * Lp + k) * LQ + n + r] = pw;
       }
     };
-    if (HYPAD_R6_HOIST && it > 0) { isb2 = __builtin_amdgcn_rcpf(co.sqrt_bc2); lrb1 = co.lr * __builtin_amdgcn_rcpf(co.bc1); }
+    if (it > 0) { isb2 = __builtin_amdgcn_rcpf(co.sqrt_bc2); lrb1 = co.lr * __builtin_amdgcn_rcpf(co.bc1); }
 #pragma unroll
     for (int u = 0; u < PS; ++u)
       if (u < NA_BODY) finish(u);
@@ -1395,7 +1366,7 @@ __device__ __forceinline__ void critic_persistent_body(const IterArgs& a, const 
       }
       if (threadIdx.x < 48) { const int p = threadIdx.x >> 4; dl[(nh * 48 + threadIdx.x) * LQ] = p == 0 ? -invB : p == 1 ? invB : 1.f; }
     };
-    if (!HYPAD_R6_STAGE || it == 0) stage_record();
+    if (it == 0) stage_record();
     int* bdone = reinterpret_cast<int*>(red + 40);
     if (threadIdx.x == 0) *bdone = 0;
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -1409,7 +1380,7 @@ __device__ __forceinline__ void critic_persistent_body(const IterArgs& a, const 
     auto as4 = [](const f32x4& v) __attribute__((always_inline)) { return make_float4(v[0], v[1], v[2], v[3]); };
     if constexpr (CHAIN) {
       f32x4 T[MF];
-      constexpr bool FWD0P = HYPAD_R6_FWD0P && SC != 0 && SC <= 100;
+      constexpr bool FWD0P = SC != 0 && SC <= 100;
       auto load_dd = [&]() __attribute__((always_inline)) {
 #pragma unroll
         for (int li = 0; li < MAXNH; ++li)
@@ -1653,9 +1624,7 @@ __device__ __forceinline__ void critic_persistent_body(const IterArgs& a, const 
           float la[8], rb[8];
 #pragma unroll
           for (int u = 0; u < 8; ++u) { la[u] = left[krow(0, u) * LQ]; rb[u] = right[krow(0, u) * ldr]; }
-#if HYPAD_R6_BATCH
           __builtin_amdgcn_sched_barrier(0);               // all operands requested before the first product: ONE exposed LDS latency per tile
-#endif
 #pragma unroll
           for (int u = 0; u < 8; ++u) acc_rf[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(la[u], rb[u], acc_rf[i], 0, 0, 0);
         }
@@ -1663,9 +1632,7 @@ __device__ __forceinline__ void critic_persistent_body(const IterArgs& a, const 
           float la[4], rb[4];
 #pragma unroll
           for (int u = 0; u < 4; ++u) { la[u] = left[krow(32, u) * LQ]; rb[u] = right[krow(32, u) * ldr]; }
-#if HYPAD_R6_BATCH
           __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
           for (int u = 0; u < 4; ++u) acc_gp[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(la[u], rb[u], acc_gp[i], 0, 0, 0);
         }
@@ -1712,7 +1679,6 @@ __device__ __forceinline__ void critic_persistent_body(const IterArgs& a, const 
       for (int ct = slot; ct < CT; ct += NW - 1) {
         int c = ct * 16 + j; c = c < in_dim ? c : in_dim - 1;
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#if HYPAD_R6_G
         if (Lp == 32) {                                     // (latent 17 .. 32: both k-groups' operands requested before the first product)
           float4 bv[2], avv[2];
 #pragma unroll
@@ -1728,7 +1694,6 @@ __device__ __forceinline__ void critic_persistent_body(const IterArgs& a, const 
           acc = mfma4(avv[0], bv[0], acc);
           acc = mfma4(avv[1], bv[1], acc);
         } else
-#endif
 #pragma unroll 2
         for (int g16 = 0; g16 < Lp; g16 += 16) {
           const int o = g16 + 4 * q;
@@ -1828,7 +1793,6 @@ __device__ __forceinline__ void critic_persistent_body(const IterArgs& a, const 
     // stores and loads cost more than the shorter dependency saves, 2.86 -> 3.03 ms per epoch)
     {
       const int obase = ((it & 1) * nchunks + chunk) * slabf;
-#if HYPAD_R6_EOFF
 #pragma unroll
       for (int i = 0; i < TPW; ++i) {
         f32x4 v;
@@ -1839,30 +1803,8 @@ __device__ __forceinline__ void critic_persistent_body(const IterArgs& a, const 
         else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), xrs, eoff[i] + obase * 4, 0, 16);
         PSTAMP(18 + (i < 4 ? i : 3));
       }
-#else
-#pragma unroll
-      for (int i = 0; i < TPW; ++i) {
-        const int t = tslot + (NW - 1) * i;
-        if (t < g.ntiles && !(CHAIN && wave == 2)) {
-          int li, n0, k0;
-          tile_desc(t, li, n0, k0);
-          const int N = li == nh ? 1 : L, K = li == 0 ? in_dim : L;
-          const int n = n0 + 4 * q, k = k0 + j;
-          if (n < N && k <= K) {
-            const int qq = n >> 2;
-            const int e = li == 0 ? qq * C0 + k : (li < nh ? I0 + (li - 1) * Ih + qq * Ch + k : I0 + (nh - 1) * Ih + k);
-            f32x4 v;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] = acc_rf[i][r] + coef * acc_gp[i][r];
-            if (same_xcd) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), xrs, (obase + e * 4) * 4, 0, 0);
-            else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), xrs, (obase + e * 4) * 4, 0, 16);
-          }
-        }
-        PSTAMP(18 + (i < 4 ? i : 3));
-      }
-#endif
     }
-    if (HYPAD_R6_STAGE && it + 1 < n_iters) stage_record();
+    if (it + 1 < n_iters) stage_record();
     PSTAMP(22);      // the next iteration's record (requested behind barrier 2), under the stores' drain
     PSTAMP(14);                                                          // share stored
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // every storing wave drains its write-through stores ...

@@ -883,10 +883,7 @@ int hypad_lstm_bidir_fwd(const float* x, const float* wf, const float* bif, cons
   if (lds_form && rows >= 2048 && ((H == 50 && K == 100) || (H == 64 && (K == 128 || K == 50)))) {
     // the reference's three layer shapes (encoder 100 -> 2 x 50; decoder 50 -> 2 x 64 and 128 -> 2 x 64): lstm_fwd_lds2_kernel
     const int64_t ntiles = (rows + 15) >> 4;
-#ifndef HYPAD_LSTM_NW
-#define HYPAD_LSTM_NW 16
-#endif
-    constexpr int nw = HYPAD_LSTM_NW;
+    constexpr int nw = 16;
     // one workgroup per CU and direction slice; NWC waves each (16, except 50 -> 2 x 64 with saved gates: eight waves, 132 -> 117 us per
     // 200 000 rows -- round 6 sweep of waves x slices, scripts/time_lstm.py; every other shape is fastest at sixteen)
     auto slices = [&](int nwc) { int n = (int)((ntiles + nwc - 1) / nwc); return n > 128 ? 128 : n; };

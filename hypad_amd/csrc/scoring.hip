@@ -14,10 +14,8 @@ using namespace hypad;
 
 namespace {
 
-// Build-time occupancy switches (waves per SIMD the register allocator is asked to fit).
-#ifndef HYPAD_UNROLL_WPE
-#define HYPAD_UNROLL_WPE 4
-#endif
+// Occupancy (waves per SIMD the register allocator is asked to fit).
+constexpr int UNROLL_WPE = 4;
 
 constexpr int THREADS = 256;
 constexpr int MAX_WINDOW = 256;
@@ -65,11 +63,8 @@ long long* g_unroll_stamps = nullptr;        // development aid (dev library): [
 #endif
 // UT: timesteps per workgroup tile, one wave per 16 of them (UT = 64: 256 threads, 128: 512).  A longer tile reads longer runs
 // of every source row (fewer partly used 128-byte lines at the runs' ends: the tile's triangle rows) for twice the LDS.
-#ifndef HYPAD_R6_UWAVE
-#define HYPAD_R6_UWAVE 1
-#endif
 template <int EPL, bool FILTER, int UT>
-__global__ __launch_bounds__(UT * 4) __attribute__((amdgpu_waves_per_eu(HYPAD_UNROLL_WPE, HYPAD_UNROLL_WPE))) void unroll_median_kernel(const float* __restrict__ y_hat, float* __restrict__ median,
+__global__ __launch_bounds__(UT * 4) __attribute__((amdgpu_waves_per_eu(UNROLL_WPE, UNROLL_WPE))) void unroll_median_kernel(const float* __restrict__ y_hat, float* __restrict__ median,
                                                                 double* __restrict__ summary, int64_t n, int W, long long* stamps) {
   constexpr int THREADS = UT * 4;                           // (shadows the file's 256: this kernel's block size follows its tile)
   constexpr int RUN = UT / 64;                               // elements per lane of one source row's run
@@ -81,7 +76,7 @@ __global__ __launch_bounds__(UT * 4) __attribute__((amdgpu_waves_per_eu(HYPAD_UN
   const int wave_s = __builtin_amdgcn_readfirstlane(wave);
   constexpr int NWV = THREADS / 64;
   const int64_t T = n + W - 1;
-  float* s = sorted + (HYPAD_R6_UWAVE ? wave_s : wave) * MAX_WINDOW;
+  float* s = sorted + wave_s * MAX_WINDOW;
   const float INF = __int_as_float(0x7f800000);
 #if HYPAD_DIAG
   const bool ucount = stamps && stamps[14] != 0;             // (counting costs one contended atomic per timestep: a run of its own)
@@ -150,7 +145,7 @@ __global__ __launch_bounds__(UT * 4) __attribute__((amdgpu_waves_per_eu(HYPAD_UN
     USTAMP(2);
     // (round 6: the timestep a wave works on is a scalar -- as a vector value every count, address and "wave-uniform" branch below was
     // vector arithmetic and exec-mask code)
-    for (int tt = HYPAD_R6_UWAVE ? wave_s : wave; tt < UT; tt += NWV) {
+    for (int tt = wave_s; tt < UT; tt += NWV) {
       const int64_t t = t0 + tt;
       if (t >= T) break;
       const int j0 = (int)(t - n + 1 > 0 ? t - n + 1 : 0);
@@ -501,19 +496,8 @@ __global__ __launch_bounds__(256) void zscore_apply_kernel(const double* __restr
 // windows covering it, critic[t - j] for the valid j (each window's score repeated along the window, un-rolled along
 // anti-diagonals).  Its score is the sample at which a Scott-bandwidth Gaussian KDE of those values is largest
 // (scipy.stats.gaussian_kde(v)(v), first arg-max), the median when fewer than two values or a singular covariance.
-#ifndef HYPAD_KDE_CB
-#define HYPAD_KDE_CB 2
-#endif
-#ifndef HYPAD_KDE_EXP
-#define HYPAD_KDE_EXP 0        // development what-ifs: 1 skips the fp32 screen's pair loop (and leaves one candidate), 2 the fp64 pass (wrong results, timing only)
-#endif
-#ifndef HYPAD_KDE_FACTORED
-#define HYPAD_KDE_FACTORED 1
-#endif
-#ifndef HYPAD_KDE_WPE
-#define HYPAD_KDE_WPE 7        // (round 6, re-swept on the final kernel: 5 -> 0.233, 6 -> 0.229, 7 -> 0.224 ms per 125 000 windows at 70 registers, none spilled; 8 spills 4)
-#endif
-constexpr int KDE_CB = HYPAD_KDE_CB;         // candidates per pass-2 batch.  Its term buffer is the kernel's largest LDS array (4 KB per wave at 2): with 2
+constexpr int KDE_WPE = 7;     // (round 6, re-swept on the final kernel: 5 -> 0.233, 6 -> 0.229, 7 -> 0.224 ms per 125 000 windows at 70 registers, none spilled; 8 spills 4)
+constexpr int KDE_CB = 2;                    // candidates per pass-2 batch.  Its term buffer is the kernel's largest LDS array (4 KB per wave at 2): with 2
                                              // and five waves per SIMD (96 registers) the kernel takes 0.354 ms per 125 000 windows; 0.438 at 4 / three waves
 //
 // Selection in two passes.  The result is a SAMPLE (the arg-max's value), so only the arg-max must be exact, not the densities:
@@ -523,7 +507,7 @@ constexpr int KDE_CB = HYPAD_KDE_CB;         // candidates per pass-2 batch.  It
 // below 7.1e-6: the budget is written out at the threshold below) -- with the same first-maximum tie rule.  Clustered samples (many near-equal densities) simply put more candidates into pass 2.
 // KPL: sample slots of 64 per lane = ceil(window / 64), a template parameter: the fp32 pass keeps four partial sums per slot.
 template <int KPL>
-__global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(HYPAD_KDE_WPE, HYPAD_KDE_WPE))) void kde_mode_kernel(const float* __restrict__ critic, double* __restrict__ modes,
+__global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(KDE_WPE, KDE_WPE))) void kde_mode_kernel(const float* __restrict__ critic, double* __restrict__ modes,
                                                             int64_t n, int W) {
   constexpr int WMAX = 64 * KPL;                            // the window class: 9 KB of LDS per workgroup and slot, 18 KB at window 100
   __shared__ double vals[THREADS / 64][WMAX];
@@ -594,7 +578,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(HYPAD_K
       // quarter-rate exponential they save; the broadcast form below reads each value once for all 64 lanes.)
       const bool factored = amax <= 8.f;                   // (wave-uniform; NaN -> the direct form)
       if (lane < 4 && cnt + lane < ((cnt + 3) & ~3)) {      // padding to a multiple of four: a pair that contributes exp2(-inf) = 0 in either form
-        vf[cnt + lane] = factored && HYPAD_KDE_FACTORED ? 0.f : __int_as_float(0x7f800000);
+        vf[cnt + lane] = factored ? 0.f : __int_as_float(0x7f800000);
         nf[cnt + lane] = __int_as_float(0xff800000);
       }
       __builtin_amdgcn_wave_barrier();
@@ -613,7 +597,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(HYPAD_K
         for (int c = 0; c < 4; ++c) acc[u][c] = 0.f;
       }
       const int nu = (cnt + 63) >> 6;                                             // sample slots in use (wave-uniform)
-      if (factored && HYPAD_KDE_FACTORED) {
+      if (factored) {
         // exp2(-(x - v)^2) = exp2(-x^2) exp2(2 x v - v^2): the pair costs a fused multiply-add (2 x in a register, v and -v^2 from
         // LDS), an exp2 and an add -- three issue slots instead of four -- and exp2(-x^2) multiplies the finished sum once.
         // |x|, |v| <= 8 keeps 2 x v - v^2 <= x^2 <= 64 inside the fp32 exponent range and its rounding (the product's and
@@ -621,7 +605,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(HYPAD_K
         float x2[KPL];
 #pragma unroll
         for (int u = 0; u < KPL; ++u) x2[u] = 2.f * xs[u];
-        for (int m = 0; m < (HYPAD_KDE_EXP == 1 ? 0 : cnt); m += 4) {
+        for (int m = 0; m < cnt; m += 4) {
           const float4 q4 = *reinterpret_cast<const float4*>(vf + m);
           const float4 n4 = *reinterpret_cast<const float4*>(nf + m);
           const float vm[4] = {q4.x, q4.y, q4.z, q4.w}, nm[4] = {n4.x, n4.y, n4.z, n4.w};
@@ -640,7 +624,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(HYPAD_K
 #pragma unroll
         for (int u = 0; u < KPL; ++u) d32[u] = ((acc[u][0] + acc[u][1]) + (acc[u][2] + acc[u][3])) * __builtin_amdgcn_exp2f(-(xs[u] * xs[u]));
       } else {
-        for (int m = 0; m < (HYPAD_KDE_EXP == 1 ? 0 : cnt); m += 4) {
+        for (int m = 0; m < cnt; m += 4) {
           const float4 q4 = *reinterpret_cast<const float4*>(vf + m);
           const float vm[4] = {q4.x, q4.y, q4.z, q4.w};
 #pragma unroll
@@ -653,7 +637,6 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(HYPAD_K
 #pragma unroll
         for (int u = 0; u < KPL; ++u) d32[u] = (acc[u][0] + acc[u][1]) + (acc[u][2] + acc[u][3]);
       }
-      if (HYPAD_KDE_EXP == 1) d32[0] = lane == 0 ? 1.f : 0.f;
       float mx = -1.f;
 #pragma unroll
       for (int u = 0; u < KPL; ++u) {
@@ -701,7 +684,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(HYPAD_K
       }
       double inv = 0.0;
       if (__builtin_amdgcn_readfirstlane(besti) == 0x7fffffff) inv = 0.5 / cov;          // (only the fp64 pass needs it)
-      for (int round = 0; round < (HYPAD_KDE_EXP == 2 ? 0 : 2) && besti == 0x7fffffff; ++round) {
+      for (int round = 0; round < 2 && besti == 0x7fffffff; ++round) {
         // First the candidates' fp64 densities as TREE sums (a lane's own terms, then the wave's butterfly: no LDS, no sequential add):
         // either order of adding <= 256 positive terms is within 3e-14 of the exact sum, so a candidate more than 1e-12 below the
         // largest tree sum cannot be the arg-max of the ordered sums either.  One survivor (the usual case): it is the arg-max, and
@@ -1156,7 +1139,7 @@ __device__ __forceinline__ int64_t seg_toff(const SegTable& t, int sl, int windo
 // (The tile loop is a copy, not a shared function: with the loop moved into one the single-signal kernels' register allocation
 // changed -- their code objects are held identical.)
 template <int EPL, int UT>
-__global__ __launch_bounds__(UT * 4) __attribute__((amdgpu_waves_per_eu(HYPAD_UNROLL_WPE, HYPAD_UNROLL_WPE))) void unroll_median_signals_kernel(
+__global__ __launch_bounds__(UT * 4) __attribute__((amdgpu_waves_per_eu(UNROLL_WPE, UNROLL_WPE))) void unroll_median_signals_kernel(
     const float* __restrict__ y_all, float* __restrict__ median_all, SegTable tab, int W) {
   const int sl = blockIdx.y;
   const int64_t n = tab.off[sl + 1] - tab.off[sl];
@@ -1542,7 +1525,7 @@ __global__ __launch_bounds__(256) void zscore_apply_signals_kernel(RecKinds kd, 
 // segment's (scalars out of the kernel arguments); a timestep's mode depends on its own segment's values only, so the partition of
 // the timesteps over workgroups does not matter.
 template <int KPL>
-__global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(HYPAD_KDE_WPE, HYPAD_KDE_WPE))) void kde_mode_signals_kernel(
+__global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(KDE_WPE, KDE_WPE))) void kde_mode_signals_kernel(
     const float* __restrict__ critic_all, double* __restrict__ modes_all, SegTable tab, int W) {
   const int sl = blockIdx.y;
   const int64_t n = tab.off[sl + 1] - tab.off[sl];
@@ -1618,7 +1601,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(HYPAD_K
       // quarter-rate exponential they save; the broadcast form below reads each value once for all 64 lanes.)
       const bool factored = amax <= 8.f;                   // (wave-uniform; NaN -> the direct form)
       if (lane < 4 && cnt + lane < ((cnt + 3) & ~3)) {      // padding to a multiple of four: a pair that contributes exp2(-inf) = 0 in either form
-        vf[cnt + lane] = factored && HYPAD_KDE_FACTORED ? 0.f : __int_as_float(0x7f800000);
+        vf[cnt + lane] = factored ? 0.f : __int_as_float(0x7f800000);
         nf[cnt + lane] = __int_as_float(0xff800000);
       }
       __builtin_amdgcn_wave_barrier();
@@ -1637,7 +1620,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(HYPAD_K
         for (int c = 0; c < 4; ++c) acc[u][c] = 0.f;
       }
       const int nu = (cnt + 63) >> 6;                                             // sample slots in use (wave-uniform)
-      if (factored && HYPAD_KDE_FACTORED) {
+      if (factored) {
         // exp2(-(x - v)^2) = exp2(-x^2) exp2(2 x v - v^2): the pair costs a fused multiply-add (2 x in a register, v and -v^2 from
         // LDS), an exp2 and an add -- three issue slots instead of four -- and exp2(-x^2) multiplies the finished sum once.
         // |x|, |v| <= 8 keeps 2 x v - v^2 <= x^2 <= 64 inside the fp32 exponent range and its rounding (the product's and
@@ -1645,7 +1628,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(HYPAD_K
         float x2[KPL];
 #pragma unroll
         for (int u = 0; u < KPL; ++u) x2[u] = 2.f * xs[u];
-        for (int m = 0; m < (HYPAD_KDE_EXP == 1 ? 0 : cnt); m += 4) {
+        for (int m = 0; m < cnt; m += 4) {
           const float4 q4 = *reinterpret_cast<const float4*>(vf + m);
           const float4 n4 = *reinterpret_cast<const float4*>(nf + m);
           const float vm[4] = {q4.x, q4.y, q4.z, q4.w}, nm[4] = {n4.x, n4.y, n4.z, n4.w};
@@ -1664,7 +1647,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(HYPAD_K
 #pragma unroll
         for (int u = 0; u < KPL; ++u) d32[u] = ((acc[u][0] + acc[u][1]) + (acc[u][2] + acc[u][3])) * __builtin_amdgcn_exp2f(-(xs[u] * xs[u]));
       } else {
-        for (int m = 0; m < (HYPAD_KDE_EXP == 1 ? 0 : cnt); m += 4) {
+        for (int m = 0; m < cnt; m += 4) {
           const float4 q4 = *reinterpret_cast<const float4*>(vf + m);
           const float vm[4] = {q4.x, q4.y, q4.z, q4.w};
 #pragma unroll
@@ -1677,7 +1660,6 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(HYPAD_K
 #pragma unroll
         for (int u = 0; u < KPL; ++u) d32[u] = (acc[u][0] + acc[u][1]) + (acc[u][2] + acc[u][3]);
       }
-      if (HYPAD_KDE_EXP == 1) d32[0] = lane == 0 ? 1.f : 0.f;
       float mx = -1.f;
 #pragma unroll
       for (int u = 0; u < KPL; ++u) {
@@ -1725,7 +1707,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(HYPAD_K
       }
       double inv = 0.0;
       if (__builtin_amdgcn_readfirstlane(besti) == 0x7fffffff) inv = 0.5 / cov;          // (only the fp64 pass needs it)
-      for (int round = 0; round < (HYPAD_KDE_EXP == 2 ? 0 : 2) && besti == 0x7fffffff; ++round) {
+      for (int round = 0; round < 2 && besti == 0x7fffffff; ++round) {
         // First the candidates' fp64 densities as TREE sums (a lane's own terms, then the wave's butterfly: no LDS, no sequential add):
         // either order of adding <= 256 positive terms is within 3e-14 of the exact sum, so a candidate more than 1e-12 below the
         // largest tree sum cannot be the arg-max of the ordered sums either.  One survivor (the usual case): it is the arg-max, and
@@ -2243,7 +2225,7 @@ int hypad_zscore_clip(const double* in, double* out, int64_t t, void* workspace,
 int hypad_kde_mode(const float* critic, double* modes, int64_t n, int window, hypad_stream_t s) {
   if (!critic || !modes || n <= 0 || window <= 0) return HYPAD_EINVAL;
   if (window > MAX_WINDOW) return HYPAD_EUNSUPPORTED;
-  // (A resident grid -- 256 x HYPAD_KDE_WPE workgroups whose waves stride over ~100 timesteps each -- was measured and dropped: 0.33 ms
+  // (A resident grid -- 256 x KDE_WPE workgroups whose waves stride over ~100 timesteps each -- was measured and dropped: 0.33 ms
   // against 0.30 ms for 8 192 workgroups of ~4 timesteps per wave at 125 000 windows; HYPAD_KDE_GRID caps the grid for such trials.)
   static const int kde_grid = HYPAD_TUNE_INT("HYPAD_KDE_GRID", 8192);
   int gw = grid_for(n + window - 1, THREADS / 64);

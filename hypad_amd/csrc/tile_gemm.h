@@ -202,9 +202,6 @@ __device__ __forceinline__ void gemm_nt(const float* __restrict__ Xs, int ldx, c
 // The first batch of a wave's first tile can be requested ahead of time (weights do not depend on activations): issue
 // gemm_nt_prefetch() before the previous stage's work and pass the result with PRE = true; the product then starts with its
 // B operands in registers instead of an L2 round trip (~2 k cycles on a chain that runs every product once).
-#ifndef HYPAD_R6_ABATCH
-#define HYPAD_R6_ABATCH 1
-#endif
 struct PackedPre { float4 w[8]; };
 // Packed weights through one of two doors.  SC1 = false: plain global loads (throughput callers).  SC1 = true: `sc1` buffer loads
 // on a descriptor built from the (wave-uniform) matrix pointer -- 1 KB blocks at scalar offsets, the lane's 16 bytes at a
@@ -285,8 +282,7 @@ __device__ __forceinline__ void gemm_nt_packed_epi(const float* __restrict__ Xs,
 #pragma unroll
     for (int m = 0; m < MT; ++m) { acc[m] = f32x4{0.f, 0.f, 0.f, 0.f}; acc2[m] = f32x4{0.f, 0.f, 0.f, 0.f}; }
     auto consume = [&](const float4 (&w)[8], int g0) __attribute__((always_inline)) {
-#if HYPAD_R6_ABATCH
-      if constexpr (SC1 && MT <= HYPAD_R6_ABATCH) {    // (the latency-chain callers: all A fragments of the batch requested before its first product)
+      if constexpr (SC1 && MT <= 1) {    // (the latency-chain callers: all A fragments of the batch requested before its first product)
         float4 av[8][MT];
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
@@ -313,7 +309,6 @@ __device__ __forceinline__ void gemm_nt_packed_epi(const float* __restrict__ Xs,
         }
         return;
       }
-#endif
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
         if (g0 + u < kg) {                             // wave-uniform

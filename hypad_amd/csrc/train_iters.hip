@@ -743,13 +743,11 @@ __device__ __forceinline__ ShadowRef shadow_ref(int net, int p_off, int S, int L
 // KS: k-steps (groups of four reduction rows) a weight item keeps in flight: 48 covers B <= 64 in one memory round trip.
 // (16 halves the registers and doubles the waves per SIMD; measured with 8 and 32 signals per GPU it changes nothing --
 // with many signals the launch moves ~9 MB per signal and sits at ~3.5 TB/s of HBM traffic.)
-#ifndef HYPAD_DW_KS_MANY
-#define HYPAD_DW_KS_MANY 16                  // k-steps in flight in the many-signal (co-located) form of the dW + Adam launch: 61 registers, seven waves
+constexpr int DW_KS_MANY = 16;               // k-steps in flight in the many-signal (co-located) form of the dW + Adam launch: 61 registers, seven waves
                                              // per SIMD instead of three (126 registers at 48).  Round 3, same box, launch time at 8 / 16 / 32 signals
                                              // per GPU: 48 -> 30.5 / 49.0 / 86.4 us, 32 -> 29.4 / 45.2 / 77.7, 24 -> 27.2 / 41.7 / 70.3, 16 -> 26.7 / 41.1 /
                                              // 68.1 (same accumulation order: same bits).  The one-signal launch keeps 48: it is as long as its slowest
                                              // item, and an item with all its operand rows in flight makes ONE memory round trip
-#endif
 template <class Table, int SC = 0, int LC = 0, int BC = 0, int KS = 48>
 __device__ __forceinline__ void dw_adam_body(const IterArgs& a, const Table& tab, const int bx = (int)blockIdx.x) {      // bx: the workgroup's index in the launch's work (dw_adam_kernel: co-location)
   const int S_ = SC ? SC : a.S, L_ = LC ? LC : a.L, B_ = BC ? BC : a.B;
@@ -1683,9 +1681,7 @@ struct ScoreArgs {
   int64_t rows; int S, L, hyperbolic;
 };
 struct ScoreLds { int xs, zs, bufA, bufB, total, ldS; };
-#ifndef HYPAD_SCORE_WPE
-#define HYPAD_SCORE_WPE 4
-#endif
+constexpr int SCORE_WPE = 4;
 HD ScoreLds score_lds(int S, int L, int MT) {
   ScoreLds p; int o = 0;
   p.ldS = lds_stride(S);
@@ -1703,7 +1699,7 @@ HD ScoreLds score_lds(int S, int L, int MT) {
 // MT = 1: 16 windows per workgroup (small calls: more workgroups).  MT = 2: 32 windows -- every weight block a wave fetches feeds two
 // row tiles, the stages' barriers and per-tile set-up are paid once per 32 windows.  Same products in the same order per row: same bits.
 template <int SC, int LC, int MT>
-__global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(HYPAD_SCORE_WPE, HYPAD_SCORE_WPE))) void score_forward_packed_kernel(ScoreArgs a) {
+__global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(SCORE_WPE, SCORE_WPE))) void score_forward_packed_kernel(ScoreArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int ROWS = 16 * MT;
   const int S = SC ? SC : a.S, L = LC ? LC : a.L;
@@ -1772,7 +1768,7 @@ struct SigTable {
   int64_t x_off[SIG_CHUNK];       // its first float in x
 };
 template <int SC, int LC, int MT>
-__global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(HYPAD_SCORE_WPE, HYPAD_SCORE_WPE))) void score_forward_signals_kernel(ScoreArgs g, SigTable t,
+__global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(SCORE_WPE, SCORE_WPE))) void score_forward_signals_kernel(ScoreArgs g, SigTable t,
                                                                                                                                   int64_t ws_stride, int pd) {
   int sl = 0;
   for (int k = 1; k < t.n; ++k) sl += (int)blockIdx.x >= t.tile_off[k];
@@ -2124,9 +2120,9 @@ int run_gen(const hypad_dims* d, const hypad_train_state* st, const IterCall& io
   const dim3 dgrid = coloc ? dim3(8 * dw_blocks(tab.total_items) * ((nsig + 7) / 8)) : dim3(8 * (dw_chunk / 4), nsig);
   for (int r = 0; r < reps; ++r) {
     if (coloc) {
-      if (ref_cfg) hipLaunchKernelGGL((dw_adam_kernel<100, 20, 64, HYPAD_DW_KS_MANY, true>), dgrid, dim3(THREADS), 0, s, a, items, total_items, coloc ? nsig : dw_chunk, tsig);
-      else if (mv_cfg) hipLaunchKernelGGL((dw_adam_kernel<150, 20, 256, HYPAD_DW_KS_MANY, true>), dgrid, dim3(THREADS), 0, s, a, items, total_items, coloc ? nsig : dw_chunk, tsig);
-      else hipLaunchKernelGGL((dw_adam_kernel<0, 0, 0, HYPAD_DW_KS_MANY, true>), dgrid, dim3(THREADS), 0, s, a, items, total_items, coloc ? nsig : dw_chunk, tsig);
+      if (ref_cfg) hipLaunchKernelGGL((dw_adam_kernel<100, 20, 64, DW_KS_MANY, true>), dgrid, dim3(THREADS), 0, s, a, items, total_items, coloc ? nsig : dw_chunk, tsig);
+      else if (mv_cfg) hipLaunchKernelGGL((dw_adam_kernel<150, 20, 256, DW_KS_MANY, true>), dgrid, dim3(THREADS), 0, s, a, items, total_items, coloc ? nsig : dw_chunk, tsig);
+      else hipLaunchKernelGGL((dw_adam_kernel<0, 0, 0, DW_KS_MANY, true>), dgrid, dim3(THREADS), 0, s, a, items, total_items, coloc ? nsig : dw_chunk, tsig);
     } else if (ref_cfg) hipLaunchKernelGGL((dw_adam_kernel<100, 20, 64, 48>), dgrid, dim3(THREADS), 0, s, a, items, total_items, coloc ? nsig : dw_chunk, tsig);
     else if (mv_cfg) hipLaunchKernelGGL((dw_adam_kernel<150, 20, 256, 48>), dgrid, dim3(THREADS), 0, s, a, items, total_items, coloc ? nsig : dw_chunk, tsig);
     else if (wadi_cfg) hipLaunchKernelGGL((dw_adam_kernel<123, 20, 64, 48>), dgrid, dim3(THREADS), 0, s, a, items, total_items, coloc ? nsig : dw_chunk, tsig);

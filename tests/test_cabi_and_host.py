@@ -195,12 +195,29 @@ def test_product_library_reads_no_environment_variable():
     assert "getenv" not in und
 
 
+def test_product_sources_carry_no_overridable_default_and_no_round_switch():
+    """tuning knobs exist in the development library only.  No kernel source holds a default that a -D on the compiler's
+    command line can change (`#ifndef HYPAD_X` / `#define HYPAD_X value`: a measured decision is a constexpr, an experiment brings its own
+    switch on its own branch through scripts/ab_variants.sh), nor a round's A/B switch (HYPAD_R<n>_...).  A header's include guard defines
+    its name to nothing and is not meant."""
+    import glob
+    default = re.compile(r"^[ \t]*#[ \t]*(?:ifndef[ \t]+|if[ \t]+![ \t]*defined[ \t]*\(?[ \t]*)(HYPAD_\w+)[^\n]*\n(?:[ \t]*\n)*[ \t]*#[ \t]*define[ \t]+\1[ \t]+(?!/[/*])\S", re.M)
+    paths = [p for p in glob.glob(os.path.join(ROOT, "hypad_amd", "csrc", "*")) if not p.endswith("diag.hip")]
+    assert len(paths) >= 15
+    for path in paths:
+        src = open(path).read()
+        assert not [m.group(1) for m in default.finditer(src)], os.path.basename(path)
+        assert not re.findall(r"\bHYPAD_R\d+_\w*", src), os.path.basename(path)
+    guard = "#ifndef HYPAD_TILE_GEMM_H\n#define HYPAD_TILE_GEMM_H   // include guard\n#endif\n"
+    assert not default.search(guard) and default.search("#ifndef HYPAD_KNOB\n#define HYPAD_KNOB 4\n#endif\n") and default.search("  #if !defined(HYPAD_KNOB)\n\n  # define HYPAD_KNOB (2)\n")
+
+
 def test_no_scratch_in_the_kernels_the_baseline_configs_run():
     """Code-object metadata of the built gfx950 objects (hypad_amd.build.kernel_metadata: the notes hipcc wrote): the kernels the BASELINE
     configs launch -- every compile-time instantiation of configs[0..2]'s shape (window 100, latent 20, batch 64), the generator / dW / scoring
     kernels of configs[3] and [4] -- spill no vector register and use no scratch memory.  Known gap, held to its current size so that it
-    can only shrink: critic_persistent_kernel<150, 20, 256> (configs[3]'s resident critic launch; 89 spilled registers and 384 bytes in
-    round 4).  Run-time-shape fallbacks (<0, 0, 0>) are not held to anything here."""
+    can only shrink: critic_persistent_kernel<150, 20, 256> (configs[3]'s resident critic launch: at most 29 spilled registers and 120 bytes
+    of scratch).  Run-time-shape fallbacks (<0, 0, 0>) are not held to anything here."""
     from hypad_amd import build
     build.build()
     ks = []
