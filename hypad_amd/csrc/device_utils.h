@@ -151,3 +151,11 @@ __device__ __forceinline__ float rng_dropout(uint64_t seed, uint32_t tick, uint3
     hipError_t e__ = hipGetLastError();               \
     if (e__ != hipSuccess) return (int)e__;           \
   } while (0)
+
+namespace hypad {
+// dynamic LDS above the 64 KiB a kernel may use without asking
+inline hipError_t allow_lds(const void* fn, size_t bytes) {
+  if (bytes <= 64 * 1024) return hipSuccess;
+  return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+}
+}  // namespace hypad

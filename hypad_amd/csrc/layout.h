@@ -127,6 +127,8 @@ HD GenPack gen_pack(int S, int L, int hyperbolic) {
   g.total = o;
   return g;
 }
+// where the scoring kernel's padded critic_x image sits in its workspace: behind the packed generator weights, 16-byte aligned
+HD int score_critic_offset(int S, int L, int hyperbolic) { return (gen_pack(S, L, hyperbolic).total + 3) & ~3; }
 
 // Critics: nh hidden Linear(.,L)+LeakyReLU+Dropout blocks, then Linear(L,1).
 struct CriticLayout {

@@ -1,9 +1,11 @@
 // Network forwards and the dense building blocks, as row-tile kernels:
 // one workgroup = 16 (or 32) window rows carried through every layer with activations in LDS.
+// Also the stand-alone optimiser steps (hypad_adam_step, hypad_radam_step).
 #include <hip/hip_runtime.h>
 
 #include "../../include/hypad.h"
 #include "nets.h"
+#include "train_common.h"
 
 using namespace hypad;
 
@@ -13,11 +15,6 @@ constexpr int THREADS = 256;
 constexpr int WST = (THREADS / 64) * WSTAGE_FLOATS;     // wave-private weight slabs of gemm_nt
 
 __host__ __device__ inline int ld_of(int n) { return pad4(n) + 4; }
-
-hipError_t allow_lds(const void* fn, size_t bytes) {
-  if (bytes <= 64 * 1024) return hipSuccess;
-  return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
 
 __device__ __forceinline__ DropSrc make_drop(const hypad_dropout& d, int batch, uint32_t stream, float p) {
   DropSrc s;
@@ -831,6 +828,27 @@ __global__ __launch_bounds__(THREADS) void score_forward_kernel(const float* __r
 
 inline int tiles16(int64_t rows) { return (int)((rows + 15) / 16); }
 
+// ---- stand-alone optimizers (the update rules of the training kernels: train_common.h)
+using train::AdamCoef; using train::adam_coef; using train::adam_update; using train::radam_ball_wave;
+__global__ __launch_bounds__(THREADS) void adam_flat_kernel(float* p, const float* g, float* m, float* v, int64_t n, int step,
+                                                             float lr, float b1, float b2, float eps, float wd, int riem,
+                                                             int64_t ball_off, int ball_dim) {
+  const AdamCoef co = adam_coef(lr, b1, b2, eps, wd, riem, 0, step);
+  for (int64_t i = (int64_t)blockIdx.x * THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * THREADS) {
+    if (ball_dim > 0 && i >= ball_off && i < ball_off + ball_dim) continue;
+    float pp = p[i], mm = m[i], vv = v[i];
+    float gg = g[i];
+    if (!riem) gg += wd * pp;     // torch.optim.Adam weight_decay: L2 into the gradient
+    adam_update(pp, mm, vv, gg, co);
+    p[i] = pp; m[i] = mm; v[i] = vv;
+  }
+}
+__global__ __launch_bounds__(64) void radam_ball_kernel(float* p, const float* g, float* m, float* v, int dim, int step, float lr,
+                                                         float b1, float b2, float eps, float wd, int stabilize) {
+  const AdamCoef co = adam_coef(lr, b1, b2, eps, wd, 1, stabilize, step);
+  radam_ball_wave(p, m, v, row_load(g, dim, threadIdx.x), dim, threadIdx.x, co);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1087,6 +1105,35 @@ int hypad_score_forward(const float* enc, const float* dec, const float* cx, con
   hipLaunchKernelGGL(score_forward_kernel, dim3(tiles16(rows)), dim3(THREADS), lds, (hipStream_t)s, enc, dec, cx, x, hyper,
                      eucl, hyper_real, critic, rowdist, rows, S, L, hyperbolic);
   HYPAD_CHECK_LAUNCH();
+  return HYPAD_OK;
+}
+
+int hypad_adam_step(float* p, const float* g, float* m, float* v, int64_t n, int step, float lr, float b1, float b2, float eps,
+                    float wd, hypad_stream_t s) {
+  if (!p || !g || !m || !v || n < 0 || step < 1) return HYPAD_EINVAL;
+  if (n == 0) return HYPAD_OK;
+  int blocks = (int)((n + THREADS - 1) / THREADS);
+  if (blocks > 2048) blocks = 2048;
+  hipLaunchKernelGGL(adam_flat_kernel, dim3(blocks), dim3(THREADS), 0, (hipStream_t)s, p, g, m, v, n, step, lr, b1, b2, eps, wd, 0,
+                     (int64_t)0, 0);
+  HYPAD_CHECK_LAUNCH();
+  return HYPAD_OK;
+}
+int hypad_radam_step(float* p, const float* g, float* m, float* v, int64_t n, int64_t ball_off, int ball_dim, int step, float lr,
+                     float b1, float b2, float eps, float wd, int stabilize, hypad_stream_t s) {
+  if (!p || !g || !m || !v || n < 0 || step < 1 || ball_dim < 0 || ball_dim > 64 * MAX_EPL) return HYPAD_EINVAL;
+  if (ball_dim > 0 && (ball_off < 0 || ball_off + ball_dim > n)) return HYPAD_EINVAL;
+  if (n == 0) return HYPAD_OK;
+  int blocks = (int)((n + THREADS - 1) / THREADS);
+  if (blocks > 2048) blocks = 2048;
+  hipLaunchKernelGGL(adam_flat_kernel, dim3(blocks), dim3(THREADS), 0, (hipStream_t)s, p, g, m, v, n, step, lr, b1, b2, eps, wd, 1,
+                     ball_off, ball_dim);
+  HYPAD_CHECK_LAUNCH();
+  if (ball_dim > 0) {
+    hipLaunchKernelGGL(radam_ball_kernel, dim3(1), dim3(64), 0, (hipStream_t)s, p + ball_off, g + ball_off, m + ball_off,
+                       v + ball_off, ball_dim, step, lr, b1, b2, eps, wd, stabilize);
+    HYPAD_CHECK_LAUNCH();
+  }
   return HYPAD_OK;
 }
 

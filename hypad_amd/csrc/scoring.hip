@@ -1403,7 +1403,7 @@ __global__ __launch_bounds__(THREADS) void dtw_error_signals_kernel(const double
 // (segments need at most T_s / 16 + 1 resp. T_s / 256 + 1 slots: no overlap), its partials at [(kind, s)][STAT_G].
 struct RecKinds { RollSrc src[3]; double* out[3]; double* s1[3]; double* s2[3]; int* c1[3]; int* c2[3]; StatPart* parts[3]; };
 __host__ __device__ inline int seg_smooth_window(int64_t n) { return (int)((double)n * 0.01); }        // math.trunc(n * 0.01), n > 0
-__host__ __device__ inline int stat_blocks_of(int64_t t) { int64_t g = (t + 1023) / 1024; return (int)(g < 1 ? 1 : (g > STAT_G ? STAT_G : g)); }
+__host__ __device__ inline int stat_blocks(int64_t t) { int64_t g = (t + 1023) / 1024; return (int)(g < 1 ? 1 : (g > STAT_G ? STAT_G : g)); }
 struct SegRoll {                                   // one segment of one kind, as the single-signal kernels see it
   RollSrc src; RollWs ws; double* out; StatPart* parts; int64_t T; int w;
 };
@@ -1487,7 +1487,7 @@ __global__ __launch_bounds__(256) void stat_partials_signals_kernel(RecKinds kd,
   __shared__ double sh[4];
   const SegRoll g = seg_roll(kd, tab, window);
   const int64_t T = g.T;
-  const int nb = stat_blocks_of(T);
+  const int nb = stat_blocks(T);
   if ((int)blockIdx.x >= nb) return;                                                  // (workgroup-uniform)
   const double* __restrict__ in = g.out;
   const int64_t len = (T + nb - 1) / nb;
@@ -1509,7 +1509,7 @@ __global__ __launch_bounds__(256) void zscore_apply_signals_kernel(RecKinds kd, 
   __shared__ StatPart sh[STAT_G];
   const SegRoll g = seg_roll(kd, tab, window);
   const int64_t T = g.T;
-  const StatPart st = stat_merge_all(g.parts, stat_blocks_of(T), sh);
+  const StatPart st = stat_merge_all(g.parts, stat_blocks(T), sh);
   const double mean = st.mean, sd = sqrt(st.m2 / st.n);
   double* io = g.out;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < T; i += (int64_t)gridDim.x * 256) {
@@ -2004,7 +2004,7 @@ __global__ __launch_bounds__(256) void critic_partials_signals_kernel(const doub
   __shared__ double sh[4];
   const int sl = blockIdx.y;
   const int64_t T = tab.off[sl + 1] - tab.off[sl] + window - 1;
-  const int nb = stat_blocks_of(T);
+  const int nb = stat_blocks(T);
   if ((int)blockIdx.x >= nb) return;                                                  // (workgroup-uniform)
   const double* __restrict__ in = in_all + seg_toff(tab, sl, window);
   const double lo = range[2 * (tab.seg0 + sl)], hi = range[2 * (tab.seg0 + sl) + 1];
@@ -2033,7 +2033,7 @@ __global__ __launch_bounds__(256) void critic_apply_signals_kernel(const double*
   if ((int64_t)blockIdx.x * 256 >= T) return;                                         // (workgroup-uniform)
   const double* __restrict__ in = in_all + to;
   double* __restrict__ out = out_all + to;
-  const StatPart st = stat_merge_all(parts_all + (size_t)sl * STAT_G, stat_blocks_of(T), sh);
+  const StatPart st = stat_merge_all(parts_all + (size_t)sl * STAT_G, stat_blocks(T), sh);
   const double mean = st.rsum / st.rcnt, sd = sqrt(st.m2 / st.n);
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < T; i += (int64_t)gridDim.x * 256)
     out[i] = fabs((in[i] - mean) / sd) + 1.0;
@@ -2048,6 +2048,46 @@ inline int64_t seg_longest(const SegTable& t) {
   int64_t most = 0;
   for (int i = 0; i < t.n; ++i) most = std::max<int64_t>(most, t.off[i + 1] - t.off[i]);
   return most;
+}
+inline bool segs_fit_2_31(int n_signals, const int64_t* row_off, int window) {      // every segment's timesteps within what a quantile launch indexes
+  for (int i = 0; i < n_signals; ++i) if (row_off[i + 1] - row_off[i] + window - 1 > ((int64_t)1 << 31)) return false;
+  return true;
+}
+// The template families: f(std::integral_constant<int, N>) launches the instantiation the run-time value picks, single or segmented.
+template <int N> using IntC = std::integral_constant<int, N>;
+template <class F> bool dtw_len_dispatch(int len, F&& f) {          // false: no instantiation for this length
+  switch (len) {
+    case 3: f(IntC<3>{}); return true;
+    case 5: f(IntC<5>{}); return true;
+    case 7: f(IntC<7>{}); return true;
+    case 9: f(IntC<9>{}); return true;
+    case 11: f(IntC<11>{}); return true;   // reference default
+    case 21: f(IntC<21>{}); return true;
+    default: return false;
+  }
+}
+template <class F> void kde_kpl_dispatch(int window, F&& f) {       // (window <= MAX_WINDOW)
+  switch ((window + 63) / 64) {
+    case 1: f(IntC<1>{}); break;
+    case 2: f(IntC<2>{}); break;
+    case 3: f(IntC<3>{}); break;
+    default: f(IntC<4>{}); break;
+  }
+}
+template <class F> auto unroll_epl_dispatch(int window, F&& f) {    // (returns what f does)
+  if (window <= 64) return f(IntC<1>{}); else if (window <= 128) return f(IntC<2>{}); else return f(IntC<4>{});
+}
+inline size_t unroll_lds_bytes(int ut, int window) { return (size_t)(ut * ((window + 3) & ~3) + (ut / 16) * MAX_WINDOW) * sizeof(float); }      // tile 128: 59 KB at window 100, 139 KB at 256
+struct GroupTotals { int64_t total, cap1, cap2; };      // timesteps of a group (timestep layout), slots of its rolling mean's 16- and 256-chunk sums
+inline GroupTotals group_totals(int n_signals, const int64_t* row_off, int window) {
+  const int64_t total = row_off[n_signals] + (int64_t)n_signals * (window - 1);
+  return {total, (total >> 4) + 2 * (int64_t)n_signals + 2, (total >> 8) + 2 * (int64_t)n_signals + 2};
+}
+// kind k of a RecKinds: its chunk sums and counts are slot k of the arrays at `sums` / `counts`
+inline void rec_kind(RecKinds& kd, int k, RollSrc src, double* out, char* sums, char* counts, const GroupTotals& g) {
+  kd.src[k] = src; kd.out[k] = out;
+  kd.s1[k] = (double*)sums + (size_t)k * (g.cap1 + g.cap2); kd.s2[k] = kd.s1[k] + g.cap1;
+  kd.c1[k] = (int*)counts + (size_t)k * (g.cap1 + g.cap2); kd.c2[k] = kd.c1[k] + g.cap1;
 }
 // workspace of hypad_quantiles_signals (the layout is written out at QSS_HIST_BYTES)
 inline int qs_slices(int n_signals) { return std::min(n_signals, SEG_CHUNK); }
@@ -2075,13 +2115,12 @@ int launch_quantiles_signals(const double* in, const SegTable& t, int slices, in
 }
 // workspace of hypad_critic_chain_signals: [quantile slices | [q25, q75] per segment | STAT_G partials per slice | the rolling mean's
 // 16- and 256-chunk sums, then their counts (slots as in RecKinds) | the unsmoothed scores | the modes when the caller keeps none]
-struct ChainWsLayout { int slices; int64_t total, cap1, cap2; size_t qs, range, parts, sums, counts, tmp, modes, bytes; };
+struct ChainWsLayout : GroupTotals { int slices; size_t qs, range, parts, sums, counts, tmp, modes, bytes; };
 ChainWsLayout chain_ws_layout(int n_signals, const int64_t* row_off, int window) {
   auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
   ChainWsLayout l;
+  static_cast<GroupTotals&>(l) = group_totals(n_signals, row_off, window);
   l.slices = qs_slices(n_signals);
-  l.total = row_off[n_signals] + (int64_t)n_signals * (window - 1);
-  l.cap1 = (l.total >> 4) + 2 * (int64_t)n_signals + 2; l.cap2 = (l.total >> 8) + 2 * (int64_t)n_signals + 2;
   l.qs = 0;
   l.range = up(qss_bytes(n_signals));
   l.parts = l.range + up((size_t)n_signals * 2 * sizeof(double));
@@ -2094,11 +2133,10 @@ ChainWsLayout chain_ws_layout(int n_signals, const int64_t* row_off, int window)
 }
 // workspace of hypad_rec_scores_signals: [area errors | dtw errors] (timestep layout) | per kind [16-chunk sums | 256-chunk sums] | their
 // counts | per kind and segment STAT_G partials
-struct RecWsLayout { int64_t total, cap1, cap2; size_t err, sums, counts, parts, bytes; };
+struct RecWsLayout : GroupTotals { size_t err, sums, counts, parts, bytes; };
 RecWsLayout rec_ws_layout(int n_signals, const int64_t* row_off, int window) {
   RecWsLayout l;
-  l.total = row_off[n_signals] + (int64_t)n_signals * (window - 1);
-  l.cap1 = (l.total >> 4) + 2 * (int64_t)n_signals + 2; l.cap2 = (l.total >> 8) + 2 * (int64_t)n_signals + 2;
+  static_cast<GroupTotals&>(l) = group_totals(n_signals, row_off, window);
   l.err = 0;
   l.sums = l.err + 2 * (size_t)l.total * sizeof(double);
   l.counts = l.sums + 3 * (size_t)(l.cap1 + l.cap2) * sizeof(double);
@@ -2117,27 +2155,25 @@ int hypad_unroll_median(const float* y_hat, float* median, double* summary, int6
   const int64_t T = n + window - 1;
   const bool filter = HYPAD_TUNE_INT("HYPAD_UNROLL_FILTER", 1) != 0;
   const int ut = HYPAD_TUNE_INT("HYPAD_UNROLL_TILE", 128) == 64 ? 64 : 128;
-  const size_t lds = (size_t)(ut * ((window + 3) & ~3) + (ut / 16) * MAX_WINDOW) * sizeof(float);      // 59 KB at window 100, 139 KB at 256
+  const size_t lds = unroll_lds_bytes(ut, window);
   const dim3 grid(grid_for(T, ut)), block(ut * 4);
   long long* stamps = nullptr;
 #if HYPAD_DIAG
   stamps = g_unroll_stamps;
 #endif
-#define HYPAD_UNROLL2(EPL, F, U)                                                                                               \
-  do {                                                                                                                        \
-    auto kf = unroll_median_kernel<EPL, F, U>;                                                                                 \
-    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) \
-      return HYPAD_EUNSUPPORTED;                                                                                               \
-    hipLaunchKernelGGL(kf, grid, block, lds, (hipStream_t)s, y_hat, median, summary, n, window, stamps);                       \
-  } while (0)
-#define HYPAD_UNROLL(EPL)                                                                                                      \
-  do {                                                                                                                        \
-    if (HYPAD_DIAG && ut == 64) { if constexpr (HYPAD_DIAG != 0) { if (filter) HYPAD_UNROLL2(EPL, true, 64); else HYPAD_UNROLL2(EPL, false, 64); } }   \
-    else { if (filter) HYPAD_UNROLL2(EPL, true, 128); else if constexpr (HYPAD_DIAG != 0) HYPAD_UNROLL2(EPL, false, 128); }      \
-  } while (0)
-  if (window <= 64) HYPAD_UNROLL(1); else if (window <= 128) HYPAD_UNROLL(2); else HYPAD_UNROLL(4);
-#undef HYPAD_UNROLL
-#undef HYPAD_UNROLL2
+  auto launch = [&](auto kf) -> int {
+    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return HYPAD_EUNSUPPORTED;
+    hipLaunchKernelGGL(kf, grid, block, lds, (hipStream_t)s, y_hat, median, summary, n, window, stamps);
+    return HYPAD_OK;
+  };
+  const int rc = unroll_epl_dispatch(window, [&](auto epl) -> int {
+    constexpr int EPL = decltype(epl)::value;
+    if constexpr (HYPAD_DIAG != 0) {       // (the unfiltered form and the 64-timestep tile exist in the development library only)
+      if (ut == 64) return filter ? launch(unroll_median_kernel<EPL, true, 64>) : launch(unroll_median_kernel<EPL, false, 64>);
+      return filter ? launch(unroll_median_kernel<EPL, true, 128>) : launch(unroll_median_kernel<EPL, false, 128>);
+    } else return launch(unroll_median_kernel<EPL, true, 128>);
+  });
+  if (rc) return rc;
   HYPAD_CHECK_LAUNCH();
   return HYPAD_OK;
 }
@@ -2172,15 +2208,7 @@ int hypad_dtw_error(const double* y, const float* yh, double* out, int64_t t, in
   if (t == 0) return HYPAD_OK;
   const int len = (score_window / 2) * 2 + 1;
   dim3 g(grid_for(t, THREADS)), b(THREADS);
-  switch (len) {
-    case 3: hipLaunchKernelGGL(dtw_error_kernel<3>, g, b, 0, (hipStream_t)s, y, yh, out, t); break;
-    case 5: hipLaunchKernelGGL(dtw_error_kernel<5>, g, b, 0, (hipStream_t)s, y, yh, out, t); break;
-    case 7: hipLaunchKernelGGL(dtw_error_kernel<7>, g, b, 0, (hipStream_t)s, y, yh, out, t); break;
-    case 9: hipLaunchKernelGGL(dtw_error_kernel<9>, g, b, 0, (hipStream_t)s, y, yh, out, t); break;
-    case 11: hipLaunchKernelGGL(dtw_error_kernel<11>, g, b, 0, (hipStream_t)s, y, yh, out, t); break;   // reference default
-    case 21: hipLaunchKernelGGL(dtw_error_kernel<21>, g, b, 0, (hipStream_t)s, y, yh, out, t); break;
-    default: return HYPAD_EUNSUPPORTED;
-  }
+  if (!dtw_len_dispatch(len, [&](auto L) { hipLaunchKernelGGL(dtw_error_kernel<decltype(L)::value>, g, b, 0, (hipStream_t)s, y, yh, out, t); })) return HYPAD_EUNSUPPORTED;
   HYPAD_CHECK_LAUNCH();
   return HYPAD_OK;
 }
@@ -2211,7 +2239,6 @@ int hypad_rolling_mean(const double* in, const float* sub, double* out, int64_t 
   HYPAD_CHECK_LAUNCH();
   return HYPAD_OK;
 }
-static int stat_blocks(int64_t t) { int64_t g = (t + 1023) / 1024; return (int)(g < 1 ? 1 : (g > STAT_G ? STAT_G : g)); }
 int hypad_zscore_clip(const double* in, double* out, int64_t t, void* workspace, size_t workspace_bytes, hypad_stream_t s) {
   if (!in || !out || t <= 0) return HYPAD_EINVAL;
   if (!workspace || workspace_bytes < HYPAD_STATS_WORKSPACE_BYTES) return HYPAD_EWORKSPACE;
@@ -2231,12 +2258,7 @@ int hypad_kde_mode(const float* critic, double* modes, int64_t n, int window, hy
   int gw = grid_for(n + window - 1, THREADS / 64);
   if (gw > kde_grid) gw = kde_grid;
   const dim3 grid(gw);
-  switch ((window + 63) / 64) {
-    case 1: hipLaunchKernelGGL(kde_mode_kernel<1>, grid, dim3(THREADS), 0, (hipStream_t)s, critic, modes, n, window); break;
-    case 2: hipLaunchKernelGGL(kde_mode_kernel<2>, grid, dim3(THREADS), 0, (hipStream_t)s, critic, modes, n, window); break;
-    case 3: hipLaunchKernelGGL(kde_mode_kernel<3>, grid, dim3(THREADS), 0, (hipStream_t)s, critic, modes, n, window); break;
-    default: hipLaunchKernelGGL(kde_mode_kernel<4>, grid, dim3(THREADS), 0, (hipStream_t)s, critic, modes, n, window); break;
-  }
+  kde_kpl_dispatch(window, [&](auto K) { hipLaunchKernelGGL(kde_mode_kernel<decltype(K)::value>, grid, dim3(THREADS), 0, (hipStream_t)s, critic, modes, n, window); });
   HYPAD_CHECK_LAUNCH();
   return HYPAD_OK;
 }
@@ -2341,12 +2363,8 @@ int hypad_combine_scores_signals(int mode, const double* c, const double* r, con
   if (rc) return rc;
   if (!out || window <= 0 || mode < 0 || mode > HYPAD_COMB_EUCL_SUM) return HYPAD_EINVAL;
   for (int c0 = 0; c0 < n_signals; c0 += SEG_CHUNK) {        // (SEG_CHUNK segments per launch: the table is a kernel argument)
-    SegTable t{};
-    t.n = std::min(SEG_CHUNK, n_signals - c0); t.seg0 = c0;
-    int64_t most = 0;
-    for (int i = 0; i <= t.n; ++i) t.off[i] = row_off[c0 + i];
-    for (int i = 0; i < t.n; ++i) most = std::max<int64_t>(most, t.off[i + 1] - t.off[i]);
-    hipLaunchKernelGGL(combine_signals_kernel, dim3(grid_for(most, THREADS), (unsigned)t.n), dim3(THREADS), 0, (hipStream_t)s, mode, c, r, u, out, t, window);
+    const SegTable t = seg_table(row_off, c0, n_signals);
+    hipLaunchKernelGGL(combine_signals_kernel, dim3(grid_for(seg_longest(t), THREADS), (unsigned)t.n), dim3(THREADS), 0, (hipStream_t)s, mode, c, r, u, out, t, window);
     HYPAD_CHECK_LAUNCH();
   }
   return HYPAD_OK;
@@ -2358,19 +2376,16 @@ int hypad_unroll_median_signals(const float* y_hat, float* median, int n_signals
   if (!y_hat || !median || window <= 0) return HYPAD_EINVAL;
   if (window > MAX_WINDOW) return HYPAD_EUNSUPPORTED;
   constexpr int UT = 128;
-  const size_t lds = (size_t)(UT * ((window + 3) & ~3) + (UT / 16) * MAX_WINDOW) * sizeof(float);      // hypad_unroll_median's: 59 KB at window 100
-  const void* kf = window <= 64 ? (const void*)unroll_median_signals_kernel<1, UT>
-                 : window <= 128 ? (const void*)unroll_median_signals_kernel<2, UT> : (const void*)unroll_median_signals_kernel<4, UT>;
-  if (lds > 64 * 1024 && hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+  const size_t lds = unroll_lds_bytes(UT, window);          // hypad_unroll_median's
+  const auto kf = unroll_epl_dispatch(window, [](auto epl) { return &unroll_median_signals_kernel<decltype(epl)::value, UT>; });
+  if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
     (void)hipGetLastError();                                  // (the refusal is reported by the status, not left behind)
     return HYPAD_EUNSUPPORTED;
   }
   for (int c0 = 0; c0 < n_signals; c0 += SEG_CHUNK) {
     const SegTable t = seg_table(row_off, c0, n_signals);
     const dim3 grid(grid_for(seg_longest(t) + window - 1, UT), (unsigned)t.n), block(UT * 4);
-    if (window <= 64) hipLaunchKernelGGL((unroll_median_signals_kernel<1, UT>), grid, block, lds, (hipStream_t)s, y_hat, median, t, window);
-    else if (window <= 128) hipLaunchKernelGGL((unroll_median_signals_kernel<2, UT>), grid, block, lds, (hipStream_t)s, y_hat, median, t, window);
-    else hipLaunchKernelGGL((unroll_median_signals_kernel<4, UT>), grid, block, lds, (hipStream_t)s, y_hat, median, t, window);
+    hipLaunchKernelGGL(kf, grid, block, lds, (hipStream_t)s, y_hat, median, t, window);
     HYPAD_CHECK_LAUNCH();
   }
   return HYPAD_OK;
@@ -2388,7 +2403,7 @@ int hypad_rec_scores_signals(int kinds, const double* true_unrolled, const float
   if (((kinds & HYPAD_REC_POINT) && !out_point) || ((kinds & HYPAD_REC_AREA) && !out_area) || ((kinds & HYPAD_REC_DTW) && !out_dtw)) return HYPAD_EINVAL;
   if ((kinds & (HYPAD_REC_AREA | HYPAD_REC_DTW)) && score_window < 2) return HYPAD_EINVAL;
   const int len = (score_window / 2) * 2 + 1;
-  if ((kinds & HYPAD_REC_DTW) && len != 3 && len != 5 && len != 7 && len != 9 && len != 11 && len != 21) return HYPAD_EUNSUPPORTED;
+  if ((kinds & HYPAD_REC_DTW) && !dtw_len_dispatch(len, [](auto) {})) return HYPAD_EUNSUPPORTED;
   const RecWsLayout l = rec_ws_layout(n_signals, row_off, window);
   if (!workspace || workspace_bytes < l.bytes) return HYPAD_EWORKSPACE;
   char* ws = (char*)workspace;
@@ -2397,9 +2412,7 @@ int hypad_rec_scores_signals(int kinds, const double* true_unrolled, const float
   RecKinds kd{};
   int nk = 0;
   auto add = [&](const double* in, const float* sub, double* out) {
-    kd.src[nk] = RollSrc{in, sub}; kd.out[nk] = out;
-    kd.s1[nk] = (double*)(ws + l.sums) + (size_t)nk * (l.cap1 + l.cap2); kd.s2[nk] = kd.s1[nk] + l.cap1;
-    kd.c1[nk] = (int*)(ws + l.counts) + (size_t)nk * (l.cap1 + l.cap2); kd.c2[nk] = kd.c1[nk] + l.cap1;
+    rec_kind(kd, nk, RollSrc{in, sub}, out, ws + l.sums, ws + l.counts, l);
     kd.parts[nk] = (StatPart*)(ws + l.parts) + (size_t)nk * n_signals * STAT_G;
     ++nk;
   };
@@ -2416,14 +2429,7 @@ int hypad_rec_scores_signals(int kinds, const double* true_unrolled, const float
       HYPAD_CHECK_LAUNCH();
     }
     if (kinds & HYPAD_REC_DTW) {
-      switch (len) {
-        case 3: hipLaunchKernelGGL(dtw_error_signals_kernel<3>, ge, b, 0, st, true_unrolled, median, err_dtw, t, window); break;
-        case 5: hipLaunchKernelGGL(dtw_error_signals_kernel<5>, ge, b, 0, st, true_unrolled, median, err_dtw, t, window); break;
-        case 7: hipLaunchKernelGGL(dtw_error_signals_kernel<7>, ge, b, 0, st, true_unrolled, median, err_dtw, t, window); break;
-        case 9: hipLaunchKernelGGL(dtw_error_signals_kernel<9>, ge, b, 0, st, true_unrolled, median, err_dtw, t, window); break;
-        case 11: hipLaunchKernelGGL(dtw_error_signals_kernel<11>, ge, b, 0, st, true_unrolled, median, err_dtw, t, window); break;   // reference default
-        default: hipLaunchKernelGGL(dtw_error_signals_kernel<21>, ge, b, 0, st, true_unrolled, median, err_dtw, t, window); break;
-      }
+      dtw_len_dispatch(len, [&](auto L) { hipLaunchKernelGGL(dtw_error_signals_kernel<decltype(L)::value>, ge, b, 0, st, true_unrolled, median, err_dtw, t, window); });
       HYPAD_CHECK_LAUNCH();
     }
     // (always the same launches, whatever the segments' windows: a segment that does not take the chunked path leaves at once)
@@ -2447,7 +2453,7 @@ int hypad_quantiles_signals(const double* in, int n_signals, const int64_t* row_
   if (rc) return rc;
   if (!in || !q || !out || window <= 0 || nq < 1) return HYPAD_EINVAL;
   if (nq > 2) return HYPAD_EUNSUPPORTED;
-  for (int i = 0; i < n_signals; ++i) if (row_off[i + 1] - row_off[i] + window - 1 > ((int64_t)1 << 31)) return HYPAD_EUNSUPPORTED;
+  if (!segs_fit_2_31(n_signals, row_off, window)) return HYPAD_EUNSUPPORTED;
   for (int j = 0; j < nq; ++j) if (!(q[j] >= 0.0 && q[j] <= 1.0)) return HYPAD_EINVAL;
   if (!workspace || workspace_bytes < qss_bytes(n_signals)) return HYPAD_EWORKSPACE;
   for (int c0 = 0; c0 < n_signals; c0 += SEG_CHUNK) {
@@ -2466,7 +2472,7 @@ int hypad_critic_chain_signals(const float* critic, double* modes_out, double* o
   if (rc) return rc;
   if (!critic || !out || window <= 0) return HYPAD_EINVAL;
   if (window > MAX_WINDOW) return HYPAD_EUNSUPPORTED;
-  for (int i = 0; i < n_signals; ++i) if (row_off[i + 1] - row_off[i] + window - 1 > ((int64_t)1 << 31)) return HYPAD_EUNSUPPORTED;
+  if (!segs_fit_2_31(n_signals, row_off, window)) return HYPAD_EUNSUPPORTED;
   const ChainWsLayout l = chain_ws_layout(n_signals, row_off, window);
   if (!workspace || workspace_bytes < l.bytes) return HYPAD_EWORKSPACE;
   char* ws = (char*)workspace;
@@ -2475,21 +2481,14 @@ int hypad_critic_chain_signals(const float* critic, double* modes_out, double* o
   double* tmp = (double*)(ws + l.tmp);
   StatPart* parts = (StatPart*)(ws + l.parts);
   RecKinds kd{};                                               // one kind: the unsmoothed scores, no subtrahend
-  kd.src[0] = RollSrc{tmp, nullptr}; kd.out[0] = out;
-  kd.s1[0] = (double*)(ws + l.sums); kd.s2[0] = kd.s1[0] + l.cap1;
-  kd.c1[0] = (int*)(ws + l.counts); kd.c2[0] = kd.c1[0] + l.cap1;
+  rec_kind(kd, 0, RollSrc{tmp, nullptr}, out, ws + l.sums, ws + l.counts, l);
   const hipStream_t st = (hipStream_t)s;
   const double q[2] = {0.25, 0.75};
   for (int c0 = 0; c0 < n_signals; c0 += SEG_CHUNK) {          // eleven launches per SEG_CHUNK signals
     const SegTable t = seg_table(row_off, c0, n_signals);
     const int64_t most = seg_longest(t) + window - 1;
     const dim3 gk(grid_for(most, THREADS / 64), (unsigned)t.n), b(THREADS);
-    switch ((window + 63) / 64) {
-      case 1: hipLaunchKernelGGL(kde_mode_signals_kernel<1>, gk, b, 0, st, critic, modes, t, window); break;
-      case 2: hipLaunchKernelGGL(kde_mode_signals_kernel<2>, gk, b, 0, st, critic, modes, t, window); break;
-      case 3: hipLaunchKernelGGL(kde_mode_signals_kernel<3>, gk, b, 0, st, critic, modes, t, window); break;
-      default: hipLaunchKernelGGL(kde_mode_signals_kernel<4>, gk, b, 0, st, critic, modes, t, window); break;
-    }
+    kde_kpl_dispatch(window, [&](auto K) { hipLaunchKernelGGL(kde_mode_signals_kernel<decltype(K)::value>, gk, b, 0, st, critic, modes, t, window); });
     HYPAD_CHECK_LAUNCH();
     const int r = launch_quantiles_signals(modes, t, l.slices, window, q, 2, range, ws + l.qs, st);
     if (r) return r;

@@ -252,5 +252,9 @@ bool critic_phase_producers(const hypad_dims& d, int n_iters);      // ... and t
 bool critic_phase_persistent(const hypad_dims& d, int flags = 0);   // the phase runs as ONE resident launch (critic_persistent_kernel)
 int critic_phase_record_info(const hypad_dims& d, int n_iters, int critic, hypad_record_info* out);
 
+// train_iters.hip: the pack launch (pack_generator_kernel) as the scoring forward pass uses it (score_forward.hip) -- the packed copies
+// of d.n_signals generators into a.ws + signal * a.ws_sig_stride + a.pk_off, with_critic: the padded critic_x image behind each
+int launch_pack_generator(const IterArgs& a, const hypad_dims& d, hipStream_t s, bool with_critic);
+
 }  // namespace train
 }  // namespace hypad
