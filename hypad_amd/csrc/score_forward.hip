@@ -42,66 +42,7 @@ __global__ __launch_bounds__(64 * CR_WAVES) void critic_rows_kernel(const float*
                                                                     float* __restrict__ out, int64_t rows, int S_, int L_) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int S = SC ? SC : S_, L = LC ? LC : L_;
-  const CriticPad cp = critic_pad(S, L, 4);
-  const int ldin = cp.ldin, LQ = cp.LQ, nh = 4;
-  const int lane = threadIdx.x & 63, wave = wave_id();
-  float* in = smem + cp.total + wave * (16 * ldin + 2 * 16 * LQ);
-  float* act = in + 16 * ldin;
-  stage_params(smem, cxpad, cp.total);
-  // the tile's constant part: the ones column behind the window (the layer's bias sits in that column of the image), zero padding
-  for (int i = lane; i < 16 * ldin; i += 64) { const int c = i % ldin; in[i] = c == S ? 1.f : 0.f; }
-  for (int i = lane; i < 2 * 16 * LQ; i += 64) act[i] = 0.f;
-  __syncthreads();
-  const float* w0 = smem + cp.w0; const float* wh = smem + cp.wh; const float* wl = smem + cp.wl;
-  const int nwaves = blockDim.x >> 6;
-  const int64_t tiles = (rows + 15) >> 4, stride = (int64_t)gridDim.x * nwaves;
-  constexpr int NV = SC ? (16 * SC + 63) / 64 : 1;     // floats of a tile per lane (compiled-in window; any other streams its rows)
-  float xr[NV];
-  auto fetch = [&](int64_t t) __attribute__((always_inline)) {
-    const int64_t r0 = t * 16;
-#pragma unroll
-    for (int u = 0; u < NV; ++u) {
-      const int i = lane + 64 * u, r = i / S, c = i - r * S;
-      const int64_t row = r0 + r < rows ? r0 + r : rows - 1;
-      xr[u] = i < 16 * S ? x[row * x_ld + c] : 0.f;
-    }
-  };
-  int64_t t = (int64_t)blockIdx.x * nwaves + wave;
-  if constexpr (SC != 0) { if (t < tiles) fetch(t); }
-  for (; t < tiles; t += stride) {
-    if constexpr (SC != 0) {
-#pragma unroll
-      for (int u = 0; u < NV; ++u) {
-        const int i = lane + 64 * u, r = i / S, c = i - r * S;
-        if (i < 16 * S) in[r * ldin + c] = xr[u];
-      }
-    } else {
-      for (int i = lane; i < 16 * S; i += 64) {
-        const int r = i / S, c = i - r * S;
-        const int64_t row = t * 16 + r < rows ? t * 16 + r : rows - 1;
-        in[r * ldin + c] = x[row * x_ld + c];
-      }
-    }
-    wave_lds_fence();
-    if constexpr (SC != 0) { if (t + stride < tiles) fetch(t + stride); }          // the next tile's rows arrive under this tile's layers
-    for (int li = 0; li < nh; ++li) {
-      const float* A = li == 0 ? in : act + ((li - 1) & 1) * 16 * LQ;
-      const float* Wl = li == 0 ? w0 : wh + (li - 1) * L * LQ;
-      float* ao = act + (li & 1) * 16 * LQ;
-      wave_gemm_nt(A, li == 0 ? ldin : LQ, Wl, li == 0 ? ldin : LQ, L, L + 1, li == 0 ? cp.Kin : cp.Lp, lane, [&](int r, int c, float pre) {
-        if (c < L) ao[r * LQ + c] = pre * leaky_slope(pre);
-        else if (c == L) ao[r * LQ + c] = 1.f;
-      });
-      wave_lds_fence();
-    }
-    if (lane < 16) {
-      const float* xa = act + ((nh - 1) & 1) * 16 * LQ + lane * LQ;
-      float o = 0.f;
-      for (int c = 0; c <= L; ++c) o += xa[c] * wl[c];
-      if (t * 16 + lane < rows) out[t * 16 + lane] = o;
-    }
-    wave_lds_fence();
-  }
+#include "critic_rows_body.inc"
 }
 int launch_critic_rows(const float* cxpad, const float* x, int64_t x_ld, float* out, int64_t rows, int S, int L, hipStream_t s) {
   int waves = CR_WAVES;
@@ -156,46 +97,7 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(SCORE_WPE, S
   const GenPack gp = gen_pack(S, L, a.hyperbolic);
   float* xs = smem + lp.xs; float* zs = smem + lp.zs; float* bufA = smem + lp.bufA; float* bufB = smem + lp.bufB;
   const int64_t r0 = (int64_t)blockIdx.x * ROWS;
-  const int valid = (int)(a.rows - r0 < ROWS ? a.rows - r0 : ROWS);
-  const int lane = threadIdx.x & 63, wave = wave_id();
-  tile_load_b(xs, ldS, a.x + r0 * a.x_ld, (int)a.x_ld, ROWS, S, valid);
-  __syncthreads();
-  encoder_fwd_tile_packed<false, false, MT>(xs, ldS, S, L, a.pk, gp, bufA, ENC_LDG, bufB, ENC_LDH, zs, nullptr, nullptr, valid);
-  DecSave none{16, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  decoder_trunk_fwd_tile_packed<MT>(zs, L, S, a.pk, gp, bufA, bufB, ldS, no_drop(), [](int r) { return r; }, none, valid);
-  if (a.eucl) tile_store_b(a.eucl + r0 * S, S, bufA, ldS, ROWS, S, valid);
-  if (a.hyperbolic) {
-    // the head on the reconstruction AND on the real windows (anomaly_detection.py:84-90): u rows of both, then the ball rows
-    float* urec; float* ureal;
-    if constexpr (MT == 1) {
-      for (int i = threadIdx.x; i < 16 * ldS; i += blockDim.x) bufA[16 * ldS + i] = xs[i];      // rows 16-31: the real windows
-      __syncthreads();
-      gemm_nt_packed<2>(bufA, ldS, S, S, a.pk + gp.head, nullptr, bufB, ldS, 0);
-      __syncthreads();
-      head_rows_tile(bufB, ldS, 32, S, a.head_b);
-      urec = bufB; ureal = bufB + 16 * ldS;
-    } else {
-      gemm_nt_packed<MT>(bufA, ldS, S, S, a.pk + gp.head, nullptr, bufB, ldS, 0);
-      __syncthreads();                                       // (e has been read -- by the product and by the store above)
-      gemm_nt_packed<MT>(xs, ldS, S, S, a.pk + gp.head, nullptr, bufA, ldS, 0);
-      __syncthreads();
-      head_rows_tile(bufB, ldS, ROWS, S, a.head_b);
-      head_rows_tile(bufA, ldS, ROWS, S, a.head_b);
-      urec = bufB; ureal = bufA;
-    }
-    __syncthreads();
-    if (a.hyper) tile_store_b(a.hyper + r0 * S, S, urec, ldS, ROWS, S, valid);
-    if (a.hyper_real) tile_store_b(a.hyper_real + r0 * S, S, ureal, ldS, ROWS, S, valid);
-    if (a.rowdist && wave < 4 * MT) {
-      // (pred = real window on the ball, true = reconstruction): anomaly_detection_utils.py:58-65; four rows per wave
-      epl16_dispatch(S, [&](auto tag) {
-        using R16 = RowT<16, decltype(tag)::value>;
-        const int r = wave * 4 + (lane >> 4);
-        const float d = rowdist_row(row_load<R16>(ureal + r * ldS, S, lane), row_load<R16>(urec + r * ldS, S, lane));
-        if ((lane & 15) == 0 && r < valid) a.rowdist[r0 + r] = d;
-      });
-    }
-  }
+#include "score_forward_body.inc"
 }
 
 
@@ -204,9 +106,12 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(SCORE_WPE, S
 // counts, outputs concatenated in row order.  The signal table travels in the kernel arguments, SIG_CHUNK signals per launch.  A
 // workgroup's signal is a scalar -- readfirstlane of a search over the table, or blockIdx.y: as a vector value it makes every buffer
 // descriptor divergent and the compiler wraps each buffer store in a waterfall loop (b117628).  A forward tile never straddles two
-// signals.  The per-tile code below is score_forward_packed_kernel's and critic_rows_kernel's line for line -- kept as copies because
-// moving those kernels' bodies into shared inline functions changed their register counts -- so every signal's rows are those of a
-// hypad_score_forward_packed call on that signal alone, bit for bit (tests/test_gpu_score_signals.py).
+// signals.  The per-tile code is score_forward_packed_kernel's and critic_rows_kernel's own: score_forward_body.inc and
+// critic_rows_body.inc, included by the single-signal kernel and by its twin below after their prologues.  Shared as text and not as
+// inline functions, which changed the single-signal kernels' scalar register counts (score_forward_packed_kernel 74 -> 75,
+// critic_rows_kernel 56 -> 54); an included text compiles to the bytes of the copies it replaced
+// (docs/history/scoring_shared_bodies.md).  So every signal's rows are those of a hypad_score_forward_packed call on that signal
+// alone, bit for bit (tests/test_gpu_score_signals.py).
 constexpr int SIG_CHUNK = 64;
 struct SigTable {
   int n, sig0;                    // signals in this launch; index of the first one in the group (its arenas and packed slot)
@@ -240,46 +145,7 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(SCORE_WPE, S
   const GenPack gp = gen_pack(S, L, a.hyperbolic);
   float* xs = smem + lp.xs; float* zs = smem + lp.zs; float* bufA = smem + lp.bufA; float* bufB = smem + lp.bufB;
   const int64_t r0 = (int64_t)((int)blockIdx.x - t.tile_off[sl]) * ROWS;         // (row 0 of this tile within its signal)
-  const int valid = (int)(a.rows - r0 < ROWS ? a.rows - r0 : ROWS);
-  const int lane = threadIdx.x & 63, wave = wave_id();
-  tile_load_b(xs, ldS, a.x + r0 * a.x_ld, (int)a.x_ld, ROWS, S, valid);
-  __syncthreads();
-  encoder_fwd_tile_packed<false, false, MT>(xs, ldS, S, L, a.pk, gp, bufA, ENC_LDG, bufB, ENC_LDH, zs, nullptr, nullptr, valid);
-  DecSave none{16, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  decoder_trunk_fwd_tile_packed<MT>(zs, L, S, a.pk, gp, bufA, bufB, ldS, no_drop(), [](int r) { return r; }, none, valid);
-  if (a.eucl) tile_store_b(a.eucl + r0 * S, S, bufA, ldS, ROWS, S, valid);
-  if (a.hyperbolic) {
-    // the head on the reconstruction AND on the real windows (anomaly_detection.py:84-90): u rows of both, then the ball rows
-    float* urec; float* ureal;
-    if constexpr (MT == 1) {
-      for (int i = threadIdx.x; i < 16 * ldS; i += blockDim.x) bufA[16 * ldS + i] = xs[i];      // rows 16-31: the real windows
-      __syncthreads();
-      gemm_nt_packed<2>(bufA, ldS, S, S, a.pk + gp.head, nullptr, bufB, ldS, 0);
-      __syncthreads();
-      head_rows_tile(bufB, ldS, 32, S, a.head_b);
-      urec = bufB; ureal = bufB + 16 * ldS;
-    } else {
-      gemm_nt_packed<MT>(bufA, ldS, S, S, a.pk + gp.head, nullptr, bufB, ldS, 0);
-      __syncthreads();                                       // (e has been read -- by the product and by the store above)
-      gemm_nt_packed<MT>(xs, ldS, S, S, a.pk + gp.head, nullptr, bufA, ldS, 0);
-      __syncthreads();
-      head_rows_tile(bufB, ldS, ROWS, S, a.head_b);
-      head_rows_tile(bufA, ldS, ROWS, S, a.head_b);
-      urec = bufB; ureal = bufA;
-    }
-    __syncthreads();
-    if (a.hyper) tile_store_b(a.hyper + r0 * S, S, urec, ldS, ROWS, S, valid);
-    if (a.hyper_real) tile_store_b(a.hyper_real + r0 * S, S, ureal, ldS, ROWS, S, valid);
-    if (a.rowdist && wave < 4 * MT) {
-      // (pred = real window on the ball, true = reconstruction): anomaly_detection_utils.py:58-65; four rows per wave
-      epl16_dispatch(S, [&](auto tag) {
-        using R16 = RowT<16, decltype(tag)::value>;
-        const int r = wave * 4 + (lane >> 4);
-        const float d = rowdist_row(row_load<R16>(ureal + r * ldS, S, lane), row_load<R16>(urec + r * ldS, S, lane));
-        if ((lane & 15) == 0 && r < valid) a.rowdist[r0 + r] = d;
-      });
-    }
-  }
+#include "score_forward_body.inc"
 }
 // grid (workgroups per signal, signals of the launch): the workgroups of signal blockIdx.y walk its 16-row tiles as critic_rows_kernel's do
 template <int SC, int LC>
@@ -294,66 +160,7 @@ __global__ __launch_bounds__(64 * CR_WAVES) void critic_rows_signals_kernel(cons
   const float* __restrict__ cxpad = ws + (tab.sig0 + sl) * ws_stride + cx_off;
   const float* __restrict__ x = x0 + tab.x_off[sl];
   float* __restrict__ out = out0 + tab.row_off[sl];
-  const CriticPad cp = critic_pad(S, L, 4);
-  const int ldin = cp.ldin, LQ = cp.LQ, nh = 4;
-  const int lane = threadIdx.x & 63, wave = wave_id();
-  float* in = smem + cp.total + wave * (16 * ldin + 2 * 16 * LQ);
-  float* act = in + 16 * ldin;
-  stage_params(smem, cxpad, cp.total);
-  // the tile's constant part: the ones column behind the window (the layer's bias sits in that column of the image), zero padding
-  for (int i = lane; i < 16 * ldin; i += 64) { const int c = i % ldin; in[i] = c == S ? 1.f : 0.f; }
-  for (int i = lane; i < 2 * 16 * LQ; i += 64) act[i] = 0.f;
-  __syncthreads();
-  const float* w0 = smem + cp.w0; const float* wh = smem + cp.wh; const float* wl = smem + cp.wl;
-  const int nwaves = blockDim.x >> 6;
-  const int64_t tiles = (rows + 15) >> 4, stride = (int64_t)gridDim.x * nwaves;
-  constexpr int NV = SC ? (16 * SC + 63) / 64 : 1;     // floats of a tile per lane (compiled-in window; any other streams its rows)
-  float xr[NV];
-  auto fetch = [&](int64_t t) __attribute__((always_inline)) {
-    const int64_t r0 = t * 16;
-#pragma unroll
-    for (int u = 0; u < NV; ++u) {
-      const int i = lane + 64 * u, r = i / S, c = i - r * S;
-      const int64_t row = r0 + r < rows ? r0 + r : rows - 1;
-      xr[u] = i < 16 * S ? x[row * x_ld + c] : 0.f;
-    }
-  };
-  int64_t t = (int64_t)blockIdx.x * nwaves + wave;
-  if constexpr (SC != 0) { if (t < tiles) fetch(t); }
-  for (; t < tiles; t += stride) {
-    if constexpr (SC != 0) {
-#pragma unroll
-      for (int u = 0; u < NV; ++u) {
-        const int i = lane + 64 * u, r = i / S, c = i - r * S;
-        if (i < 16 * S) in[r * ldin + c] = xr[u];
-      }
-    } else {
-      for (int i = lane; i < 16 * S; i += 64) {
-        const int r = i / S, c = i - r * S;
-        const int64_t row = t * 16 + r < rows ? t * 16 + r : rows - 1;
-        in[r * ldin + c] = x[row * x_ld + c];
-      }
-    }
-    wave_lds_fence();
-    if constexpr (SC != 0) { if (t + stride < tiles) fetch(t + stride); }          // the next tile's rows arrive under this tile's layers
-    for (int li = 0; li < nh; ++li) {
-      const float* A = li == 0 ? in : act + ((li - 1) & 1) * 16 * LQ;
-      const float* Wl = li == 0 ? w0 : wh + (li - 1) * L * LQ;
-      float* ao = act + (li & 1) * 16 * LQ;
-      wave_gemm_nt(A, li == 0 ? ldin : LQ, Wl, li == 0 ? ldin : LQ, L, L + 1, li == 0 ? cp.Kin : cp.Lp, lane, [&](int r, int c, float pre) {
-        if (c < L) ao[r * LQ + c] = pre * leaky_slope(pre);
-        else if (c == L) ao[r * LQ + c] = 1.f;
-      });
-      wave_lds_fence();
-    }
-    if (lane < 16) {
-      const float* xa = act + ((nh - 1) & 1) * 16 * LQ + lane * LQ;
-      float o = 0.f;
-      for (int c = 0; c <= L; ++c) o += xa[c] * wl[c];
-      if (t * 16 + lane < rows) out[t * 16 + lane] = o;
-    }
-    wave_lds_fence();
-  }
+#include "critic_rows_body.inc"
 }
 
 }  // namespace

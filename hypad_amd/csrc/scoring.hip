@@ -66,213 +66,7 @@ long long* g_unroll_stamps = nullptr;        // development aid (dev library): [
 template <int EPL, bool FILTER, int UT>
 __global__ __launch_bounds__(UT * 4) __attribute__((amdgpu_waves_per_eu(UNROLL_WPE, UNROLL_WPE))) void unroll_median_kernel(const float* __restrict__ y_hat, float* __restrict__ median,
                                                                 double* __restrict__ summary, int64_t n, int W, long long* stamps) {
-  constexpr int THREADS = UT * 4;                           // (shadows the file's 256: this kernel's block size follows its tile)
-  constexpr int RUN = UT / 64;                               // elements per lane of one source row's run
-  extern __shared__ __attribute__((aligned(16))) float usm[];
-  const int WS = (W + 3) & ~3;                              // tile row stride (floats)
-  float* tile = usm;                                        // [UT][WS]
-  float* sorted = usm + UT * WS;                            // [waves][MAX_WINDOW]   (summary / candidates)
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int wave_s = __builtin_amdgcn_readfirstlane(wave);
-  constexpr int NWV = THREADS / 64;
-  const int64_t T = n + W - 1;
-  float* s = sorted + wave_s * MAX_WINDOW;
-  const float INF = __int_as_float(0x7f800000);
-#if HYPAD_DIAG
-  const bool ucount = stamps && stamps[14] != 0;             // (counting costs one contended atomic per timestep: a run of its own)
-#endif
-  for (int64_t t0 = (int64_t)blockIdx.x * UT; t0 < T; t0 += (int64_t)gridDim.x * UT) {
-    USTAMP(0);
-    // ---- stage: rows r in [t0 - (W - 1), t0 + UT) (clipped to the matrix), their runs of this tile's timesteps
-    constexpr int RB = 8 / RUN;                              // rows in flight per wave (8 loads per lane either way)
-    if (t0 >= W - 1 && t0 + UT <= n) {
-      // interior tile (all but the first and last two of a long series): no clipping, j0 == 0, 32-bit indices relative to the
-      // tile's first row, the row number a scalar -- ~9 vector instructions per row and lane instead of ~30 of 64-bit arithmetic
-      const float* base = y_hat + (t0 - (W - 1)) * W;
-      const int nrows = W + UT - 1;
-      for (int kb = wave_s * RB; kb < nrows; kb += NWV * RB) {
-        float val[RB][RUN];
-        int dst[RB][RUN];
-#pragma unroll
-        for (int u = 0; u < RB; ++u) {
-          const int k = kb + u;                              // (scalar) row of the tile's parallelogram
-          const int jb = W - 1 - k > 0 ? W - 1 - k : 0;
-#pragma unroll
-          for (int h = 0; h < RUN; ++h) {
-            const int j = jb + lane + 64 * h, tt = k - (W - 1) + j;
-            const bool ok = k < nrows && j < W && tt < UT;
-            dst[u][h] = ok ? tt * WS + j : -1;
-            val[u][h] = ok ? base[k * W + j] : 0.f;
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < RB; ++u)
-#pragma unroll
-          for (int h = 0; h < RUN; ++h)
-            if (dst[u][h] >= 0) tile[dst[u][h]] = val[u][h];
-      }
-    } else {
-      const int64_t r_lo = t0 - (W - 1) > 0 ? t0 - (W - 1) : 0;
-      const int64_t r_hi = t0 + UT < n ? t0 + UT : n;         // exclusive
-      for (int64_t rb = r_lo + wave * RB; rb < r_hi; rb += NWV * RB) {
-        float val[RB][RUN];
-        int dst[RB][RUN];
-#pragma unroll
-        for (int u = 0; u < RB; ++u) {
-          const int64_t r = rb + u;
-          const int jb = (int)(t0 - r > 0 ? t0 - r : 0);       // first column of row r inside the tile
-#pragma unroll
-          for (int h = 0; h < RUN; ++h) {
-            const int j = jb + lane + 64 * h;                  // (a run is at most UT columns: RUN elements per lane)
-            const int64_t t = r + j;
-            dst[u][h] = -1; val[u][h] = 0.f;
-            if (r < r_hi && j < W && t < t0 + UT && t < T) {
-              const int j0 = (int)(t - n + 1 > 0 ? t - n + 1 : 0);
-              dst[u][h] = (int)(t - t0) * WS + (j - j0);
-              val[u][h] = y_hat[r * W + j];
-            }
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < RB; ++u)
-#pragma unroll
-          for (int h = 0; h < RUN; ++h)
-            if (dst[u][h] >= 0) tile[dst[u][h]] = val[u][h];
-      }
-    }
-    USTAMP(1);
-    __syncthreads();
-    USTAMP(2);
-    // (round 6: the timestep a wave works on is a scalar -- as a vector value every count, address and "wave-uniform" branch below was
-    // vector arithmetic and exec-mask code)
-    for (int tt = wave_s; tt < UT; tt += NWV) {
-      const int64_t t = t0 + tt;
-      if (t >= T) break;
-      const int j0 = (int)(t - n + 1 > 0 ? t - n + 1 : 0);
-      const int j1 = (int)(t + 1 < W ? t + 1 : W);
-      const int cnt = j1 - j0;
-      float* v = tile + tt * WS;
-      // pad the row to a multiple of 4 with +inf (never below or equal to a finite value)
-      if (lane < 4 && cnt + lane < ((cnt + 3) & ~3)) v[cnt + lane] = INF;
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): LDS writes of this wave landed
-      float mine[EPL];
-#pragma unroll
-      for (int e = 0; e < EPL; ++e) { const int i = lane + 64 * e; mine[e] = i < cnt ? v[i] : INF; }
-      const int m1 = (cnt - 1) >> 1, m2 = cnt >> 1;
-      float lo_med = 0.f, hi_med = 0.f;
-      bool done = false;
-      if (FILTER && !summary && cnt >= 64) {                 // wave-uniform
-        // ranks inside the sample v[0 .. 31] (lanes >= 32 idle along)
-        const float sv = v[lane & 31];
-        int less = 0;
-#pragma unroll
-        for (int k0 = 0; k0 < 32; k0 += 4) {
-          const float4 q = *reinterpret_cast<const float4*>(v + k0);
-          less += (q.x < sv ? 1 : 0) + (q.y < sv ? 1 : 0) + (q.z < sv ? 1 : 0) + (q.w < sv ? 1 : 0);
-        }
-        float plo = less <= 10 ? sv : -INF, phi = less >= 21 ? sv : INF;     // 11th smallest (largest with <= 10 below), 22nd smallest
-        plo = hypad::wave_max(plo); phi = hypad::wave_min(phi);                // (DPP butterflies: no LDS round trips on this chain)
-        int c_lt = 0, c_le = 0;
-        unsigned long long cm[EPL];
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) {
-          const bool in = lane + 64 * e < cnt;
-          c_lt += __builtin_popcountll(__ballot(in && mine[e] < plo));
-          c_le += __builtin_popcountll(__ballot(in && mine[e] <= phi));
-          cm[e] = __ballot(in && mine[e] >= plo && mine[e] <= phi);
-        }
-        const int nc = c_le - c_lt;
-        if (c_lt <= m1 && m2 < c_le && nc <= 64 && nc > 0) {
-          // compact the candidates into the wave's slab, rank them against each other
-          int base = 0;
-#pragma unroll
-          for (int e = 0; e < EPL; ++e) {
-            const int pos = base + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(cm[e] >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)cm[e], 0u));
-            if ((cm[e] >> lane) & 1ull) s[pos] = mine[e];
-            base += __builtin_popcountll(cm[e]);
-          }
-          if (lane < 4 && nc + lane < ((nc + 3) & ~3)) s[nc + lane] = INF;
-          __builtin_amdgcn_wave_barrier();
-          __builtin_amdgcn_s_waitcnt(0xc07f);
-          const float c = lane < nc ? s[lane] : INF;
-          int rk = 0;
-          for (int k0 = 0; k0 < nc; k0 += 4) {
-            const float4 q = *reinterpret_cast<const float4*>(s + k0);
-            rk += (q.x < c ? 1 : 0) + (q.y < c ? 1 : 0) + (q.z < c ? 1 : 0) + (q.w < c ? 1 : 0);
-          }
-          // without ties the "less" counts are a permutation of 0 .. nc - 1 (their sum tells): then the lanes holding local ranks
-          // m1 - c_lt and m2 - c_lt hold the two middle values
-          const float rsum = hypad::wave_sum(lane < nc ? (float)rk : 0.f);
-          if (rsum == 0.5f * (float)nc * (float)(nc - 1)) {
-            const unsigned long long k1 = __ballot(lane < nc && rk == m1 - c_lt), k2 = __ballot(lane < nc && rk == m2 - c_lt);
-            lo_med = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c), (int)__builtin_ctzll(k1)));
-            hi_med = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c), (int)__builtin_ctzll(k2)));
-            done = true;
-            UCOUNT(8);
-          }
-          __builtin_amdgcn_wave_barrier();
-        }
-      }
-      if (!done) {
-        UCOUNT(9);
-        // rank = #{k : v[k] < mine} + #{k < i : v[k] == mine}.  Fast pass: count "less" only (one compare + add-carry per value).
-        // Without ties those counts are a permutation of 0 .. cnt-1, with ties two values share a count and the counts' sum falls
-        // short of cnt (cnt - 1) / 2: only then is the ordered tie count needed.  (The sum is exact in fp32: < 2^15 at window 256.)
-        int rank[EPL];
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) rank[e] = 0;
-        for (int k0 = 0; k0 < cnt; k0 += 4) {
-          const float4 q = *reinterpret_cast<const float4*>(v + k0);
-          const float vk[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-          for (int u = 0; u < 4; ++u)
-#pragma unroll
-            for (int e = 0; e < EPL; ++e) rank[e] += vk[u] < mine[e] ? 1 : 0;
-        }
-        float rsum = 0.f;
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) rsum += lane + 64 * e < cnt ? (float)rank[e] : 0.f;
-        const bool ties = hypad::wave_sum(rsum) != 0.5f * (float)cnt * (float)(cnt - 1);
-        if (ties) {                                      // wave-uniform
-#pragma unroll
-          for (int e = 0; e < EPL; ++e) rank[e] = 0;
-          for (int k = 0; k < cnt; ++k) {
-            const float vk = v[k];
-#pragma unroll
-            for (int e = 0; e < EPL; ++e) {
-              const int i = lane + 64 * e;
-              rank[e] += (vk < mine[e]) || (vk == mine[e] && k < i);
-            }
-          }
-        }
-#pragma unroll
-        for (int e = 0; e < EPL; ++e)
-          if (lane + 64 * e < cnt) s[rank[e]] = mine[e];
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_s_waitcnt(0xc07f);
-        lo_med = s[m1]; hi_med = s[m2];
-      }
-      if (lane == 0) {
-        median[t] = (cnt & 1) ? lo_med : (lo_med + hi_med) * 0.5f;     // np.median of float32 stays float32
-        if (summary) {
-          double* o = summary + t * 5;
-          o[0] = (double)s[0];
-          const double qs[3] = {0.25, 0.5, 0.75};
-          for (int qi = 0; qi < 3; ++qi) {
-            double pos = qs[qi] * (double)(cnt - 1);
-            int a = (int)floor(pos);
-            int b = a + 1 < cnt ? a + 1 : cnt - 1;
-            o[1 + qi] = (double)np_lerp(s[a], s[b], (float)(pos - (double)a));
-          }
-          o[4] = (double)s[cnt - 1];
-        }
-      }
-      __builtin_amdgcn_wave_barrier();
-    }
-    USTAMP(3);
-    __syncthreads();
-  }
+#include "unroll_median_body.inc"
 }
 
 template <class TIn>
@@ -315,36 +109,7 @@ template <int LEN>
 __global__ __launch_bounds__(THREADS) void dtw_error_kernel(const double* __restrict__ y, const float* __restrict__ yh,
                                                              double* __restrict__ out, int64_t T) {
   constexpr int HALF = LEN / 2;
-  for (int64_t p = (int64_t)blockIdx.x * THREADS + threadIdx.x; p < T; p += (int64_t)gridDim.x * THREADS) {
-    const int64_t i = p - HALF;                 // window start in padded coordinates
-    if (i < 0 || i >= T - LEN) { out[p] = 0.0; continue; }
-    double a[LEN], b[LEN], row[LEN];
-#pragma unroll
-    for (int k = 0; k < LEN; ++k) {
-      int64_t src = i + k - HALF;               // y_pad[i + k] = y[i + k - HALF]
-      bool ok = src >= 0 && src < T;
-      a[k] = ok ? y[src] : 0.0;
-      b[k] = ok ? (double)yh[src] : 0.0;
-    }
-    double acc = 0.0;
-#pragma unroll
-    for (int j = 0; j < LEN; ++j) { double d = a[0] - b[j]; acc += d * d; row[j] = acc; }
-#pragma unroll
-    for (int r = 1; r < LEN; ++r) {
-      double diag = row[0];
-      double d0 = a[r] - b[0];
-      row[0] = row[0] + d0 * d0;
-#pragma unroll
-      for (int j = 1; j < LEN; ++j) {
-        double up = row[j];
-        double d = a[r] - b[j];
-        double m = fmin(fmin(up, row[j - 1]), diag);
-        row[j] = d * d + m;
-        diag = up;
-      }
-    }
-    out[p] = sqrt(row[LEN - 1]);
-  }
+#include "dtw_error_body.inc"
 }
 
 // ---- centred rolling mean (pandas rolling(w, center=True, min_periods=w/2).mean(), NaNs skipped).
@@ -509,279 +274,7 @@ constexpr int KDE_CB = 2;                    // candidates per pass-2 batch.  It
 template <int KPL>
 __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(KDE_WPE, KDE_WPE))) void kde_mode_kernel(const float* __restrict__ critic, double* __restrict__ modes,
                                                             int64_t n, int W) {
-  constexpr int WMAX = 64 * KPL;                            // the window class: 9 KB of LDS per workgroup and slot, 18 KB at window 100
-  __shared__ double vals[THREADS / 64][WMAX];
-  __shared__ __attribute__((aligned(16))) float vals32[THREADS / 64][WMAX + 4];      // + the padding the fp32 pass reads past the end
-  __shared__ __attribute__((aligned(16))) float nsq32[THREADS / 64][WMAX + 4];       // -(value^2) for the factored form of the fp32 pass
-  __shared__ double terms[THREADS / 64][KDE_CB * WMAX];
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int64_t T = n + W - 1;
-  double* v = vals[wave];
-  float* vf = vals32[wave];
-  float* nf = nsq32[wave];
-  // per-thread constants of the timestep loop, held in SCALAR registers (they are wave-uniform; as vector values the compiler kept them
-  // in scratch memory across the loop: 20 bytes of private segment per lane and two scratch loads per timestep)
-  auto uniform = [](double x) __attribute__((always_inline)) {
-    return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(x)), __builtin_amdgcn_readfirstlane(__double2loint(x)));
-  };
-  // Scott's factor n^(-2/5) for every sample count 1 .. W, one power per thread, once (the 2 (W - 1) edge timesteps have fewer than W
-  // samples; a double-precision pow inside the loop -- ~200 instructions, its 40 polynomial constants hoisted into vector registers
-  // across the loop -- was what this kernel spilled around)
-  __shared__ double scott[WMAX];
-  for (int c = threadIdx.x; c < W && c < WMAX; c += THREADS) scott[c] = pow((double)(c + 1), -0.4);
-  __syncthreads();
-  const double rW1 = uniform(W > 1 ? 1.0 / (double)(W - 1) : 0.0);
-  for (int64_t t = (int64_t)blockIdx.x * (THREADS / 64) + wave; t < T; t += (int64_t)gridDim.x * (THREADS / 64)) {
-    const int j0 = (int)(t - n + 1 > 0 ? t - n + 1 : 0);
-    const int j1 = (int)(t + 1 < W ? t + 1 : W);
-    const int cnt = __builtin_amdgcn_readfirstlane(j1 - j0);      // (wave-uniform: the pair loops below run on scalar counters)
-    double s = 0.0;
-    for (int k = lane; k < cnt; k += 64) {
-      const float xf = critic[t - (j0 + k)];
-      v[k] = (double)xf;
-      vf[k] = xf;
-      s += (double)xf;
-    }
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-    const double mean = wave_sum(s) / (double)cnt;
-    double q = 0.0;
-    for (int k = lane; k < cnt; k += 64) { const double d = v[k] - mean; q += d * d; }
-    const double var = cnt > 1 ? wave_sum(q) * (cnt == W ? rW1 : 1.0 / (double)(cnt - 1)) : 0.0;      // np.cov: ddof = 1, `c *= 1 / fact`
-    // Scott: factor = n^(-1/5), squared.  (All but the 2 (W - 1) edge timesteps have cnt == W: that power is taken once per
-    // thread, not once per timestep -- a double-precision pow is ~200 instructions.)
-    const double cov = var * uniform(scott[cnt - 1]);
-    double out;
-    if (cnt > 1 && cov > 0.0 && cov == cov) {
-      // pass 1: fp32 densities of this lane's samples.  exp(-d^2 inv) = exp2(-(c d)^2) with c = sqrt(inv log2 e): the samples are
-      // centred and rescaled once (pass 2 reads the fp64 copies), so a pair costs a subtract, a multiply, an exp2 and an add; the
-      // slab is padded with +inf to a multiple of four (a padded pair contributes exp2(-inf) = 0) and read four values at a
-      // time, every value once for all of the lane's samples.
-      // The samples are CENTRED first, in fp64 (densities depend on differences only): rescaling the raw values would leave the
-      // fp32 copies with an absolute error of |value| 2^-24 c, which at |mean| / bandwidth beyond ~1e4 exceeds the screen's margin.
-      // The scale itself only has to be good to fp32 (an error in it is a slightly different bandwidth for every sample alike: 2e-7
-      // relative in the densities): one v_rsq_f32 instead of an fp64 division and square root per timestep; the fp64 1 / (2 cov) that
-      // pass 2 uses is taken only when pass 2 runs.  (A covariance outside the fp32 range makes the screen all-NaN or all-equal: pass 2
-      // then sees every sample, as before.)
-      const double c64 = (double)__builtin_amdgcn_rsqf((float)cov * 1.3862943611198906f);     // sqrt(log2 e / (2 cov))
-      float amax = 0.f;
-      for (int k = lane; k < cnt; k += 64) {
-        const float y = (float)((v[k] - mean) * c64);
-        vf[k] = y; nf[k] = -(y * y);
-        amax = fmaxf(amax, fabsf(y));
-      }
-      amax = wave_max(amax);
-      // (Measured and dropped in round 3, twice: using the kernel matrix's symmetry -- each unordered pair evaluated once.  With the
-      // partner's share delivered by ds_add_f32: 3.28 ms against 0.42 ms for 125 000 windows (LDS float atomics).  With the values
-      // parked in a small LDS matrix in chunks of eight steps and collected by the partners after a wave barrier (no atomics,
-      // conflict-free strides, immediate offsets): 0.69 ms -- three per-lane LDS operations per pair cost more issue time than the
-      // quarter-rate exponential they save; the broadcast form below reads each value once for all 64 lanes.)
-      const bool factored = amax <= 8.f;                   // (wave-uniform; NaN -> the direct form)
-      if (lane < 4 && cnt + lane < ((cnt + 3) & ~3)) {      // padding to a multiple of four: a pair that contributes exp2(-inf) = 0 in either form
-        vf[cnt + lane] = factored ? 0.f : __int_as_float(0x7f800000);
-        nf[cnt + lane] = __int_as_float(0xff800000);
-      }
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_s_waitcnt(0xc07f);
-      // (Measured and dropped in round 3: giving the cnt % 64 samples of the last slot 64 / b lanes each -- groups of b = 32, 16, ..
-      // samples by the binary digits of the remainder, each lane a share of the values, shares added by xor shuffles: 25 + 13 + 2 steps
-      // of four values per lane at window 100 instead of 25 + 25, 20 % fewer exponentials by counter, and no faster: 0.292 against
-      // 0.287 ms.  Per-lane LDS addresses and the shuffles cost what the idle lanes did.)
-      float d32[KPL], xs[KPL];
-      float acc[KPL][4];                                   // one accumulator per position in the group of four: <= ceil(cnt / 4) terms each
-#pragma unroll
-      for (int u = 0; u < KPL; ++u) {
-        const int k = lane + 64 * u;
-        xs[u] = vf[k < cnt ? k : 0];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) acc[u][c] = 0.f;
-      }
-      const int nu = (cnt + 63) >> 6;                                             // sample slots in use (wave-uniform)
-      if (factored) {
-        // exp2(-(x - v)^2) = exp2(-x^2) exp2(2 x v - v^2): the pair costs a fused multiply-add (2 x in a register, v and -v^2 from
-        // LDS), an exp2 and an add -- three issue slots instead of four -- and exp2(-x^2) multiplies the finished sum once.
-        // |x|, |v| <= 8 keeps 2 x v - v^2 <= x^2 <= 64 inside the fp32 exponent range and its rounding (the product's and
-        // -v^2's: 2^-24 x 64 each at the very worst) inside the budget written out at the threshold below.
-        float x2[KPL];
-#pragma unroll
-        for (int u = 0; u < KPL; ++u) x2[u] = 2.f * xs[u];
-        for (int m = 0; m < cnt; m += 4) {
-          const float4 q4 = *reinterpret_cast<const float4*>(vf + m);
-          const float4 n4 = *reinterpret_cast<const float4*>(nf + m);
-          const float vm[4] = {q4.x, q4.y, q4.z, q4.w}, nm[4] = {n4.x, n4.y, n4.z, n4.w};
-#pragma unroll
-          for (int u = 0; u < KPL; ++u) {
-            if (u >= nu) continue;
-            // (two fused multiply-adds per instruction: v_pk_fma_f32 -- the same roundings)
-            typedef float v2f __attribute__((ext_vector_type(2)));
-            const v2f xx = {x2[u], x2[u]};
-            const v2f a01 = __builtin_elementwise_fma(xx, v2f{vm[0], vm[1]}, v2f{nm[0], nm[1]});
-            const v2f a23 = __builtin_elementwise_fma(xx, v2f{vm[2], vm[3]}, v2f{nm[2], nm[3]});
-            acc[u][0] += __builtin_amdgcn_exp2f(a01.x); acc[u][1] += __builtin_amdgcn_exp2f(a01.y);
-            acc[u][2] += __builtin_amdgcn_exp2f(a23.x); acc[u][3] += __builtin_amdgcn_exp2f(a23.y);
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < KPL; ++u) d32[u] = ((acc[u][0] + acc[u][1]) + (acc[u][2] + acc[u][3])) * __builtin_amdgcn_exp2f(-(xs[u] * xs[u]));
-      } else {
-        for (int m = 0; m < cnt; m += 4) {
-          const float4 q4 = *reinterpret_cast<const float4*>(vf + m);
-          const float vm[4] = {q4.x, q4.y, q4.z, q4.w};
-#pragma unroll
-          for (int u = 0; u < KPL; ++u) {
-            if (u >= nu) continue;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) { const float d = xs[u] - vm[c]; acc[u][c] += __builtin_amdgcn_exp2f(-(d * d)); }
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < KPL; ++u) d32[u] = (acc[u][0] + acc[u][1]) + (acc[u][2] + acc[u][3]);
-      }
-      float mx = -1.f;
-#pragma unroll
-      for (int u = 0; u < KPL; ++u) {
-        if (lane + 64 * u >= cnt) d32[u] = -1.f;
-        mx = fmaxf(mx, d32[u]);
-      }
-      mx = wave_max(mx);
-      // Relative error of an fp32 density D~ against the exact D, all terms positive.  Direct form, exp2(-(x - v)^2):
-      //  * arguments: a centred, rescaled sample y carries 2^-24 |y| <= 1e-6 (|y| < 32 for every pair that contributes: two of <= 256
-      //    samples within a few units of each other lie at most 2.6 sqrt(255 / 2) = 29 units from the mean; a lone outlier beyond that
-      //    sees only its own term, exactly 1), a difference d twice that, d^2 an absolute 2 |d| 2e-6 (+ 2^-24 d^2 from the product);
-      //    a term's relative error is ln 2 times that, and weighted by the terms themselves (|d| 2^(-d^2) <= 0.52, the self term is 1)
-      //    the sum's is <= 3e-6;
-      //  * v_exp_f32: 1 ulp = 1.2e-7;
-      //  * accumulation: four partial sums of <= 64 terms, each add 2^-24 of a partial sum that never exceeds the result: 3.8e-6, + 1.2e-7
-      //    for the two combining adds
-      // -> eps <= 7.1e-6 at window 256 (4.8e-6 at 100).  Factored form (all |y| <= 8), exp2(-x^2) exp2(2 x v - v^2):
-      //  * the samples' own rounding (|y| <= 8: 2^-24 x 8): 0.7e-6 by the same weighting;
-      //  * the argument 2 x v - v^2 (|.| <= 64): -v^2 rounded once, the fused multiply-add once, 2^-24 x 64 = 3.8e-6 absolute together
-      //    at the very worst -> ln 2 x 3.8e-6 = 2.6e-6;  exp2(-x^2): x^2 rounded (1.9e-6 absolute -> 1.3e-6) + 1 ulp;
-      //  * v_exp_f32 1.2e-7, accumulation 3.9e-6 as above, the closing product 6e-8
-      // -> eps <= 8.8e-6.  If k* is the true arg-max, D~[k*] >= (1 - eps) D[k*] >= (1 - eps) D[j] >= (1 - eps) / (1 + eps) D~[j] for
-      // every j: the screen keeps k* as long as its margin exceeds 2 eps = 1.8e-5.  Margin 4e-5 (rounds 2-3 used 2e-4 with one
-      // accumulator per sample: 1.7 fp64 evaluations per timestep on random-normal values, 0.6 now).
-      const float thr = mx * (1.f - 4e-5f);
-      // pass 2: fp64 densities of the candidates, in ascending sample order (the first maximum is kept); of every sample if
-      // pass 1 produced no candidate (a bandwidth so small that its reciprocal leaves the fp32 range makes the screen NaN).
-      // A wave pays for a sequential sum as if all 64 lanes ran it, so a candidate's sum is NOT given to one lane with its
-      // exponentials: the lanes compute a candidate's cnt exponentials side by side into LDS (two per lane at window 100), four
-      // candidates per batch, then lane c adds candidate c's terms in index order -- the same additions in the same order as
-      // the one-lane loop, hence the same bits, at 1/20 of its cycles.
-      double best = -1.0;
-      int besti = 0x7fffffff;
-      double* tm = terms[wave];
-      {
-        // one candidate only: the screen has decided (its margin is far above the fp32 pass's error), no fp64 sum is needed
-        int ncand = 0, first = 0x7fffffff;
-#pragma unroll
-        for (int u = 0; u < KPL; ++u) {
-          const unsigned long long mk = __ballot(lane + 64 * u < cnt && d32[u] >= thr);
-          ncand += __builtin_popcountll(mk);
-          if (mk && first == 0x7fffffff) first = __builtin_ctzll(mk) + 64 * u;
-        }
-        if (ncand == 1) besti = first;
-      }
-      double inv = 0.0;
-      if (__builtin_amdgcn_readfirstlane(besti) == 0x7fffffff) inv = 0.5 / cov;          // (only the fp64 pass needs it)
-      for (int round = 0; round < 2 && besti == 0x7fffffff; ++round) {
-        // First the candidates' fp64 densities as TREE sums (a lane's own terms, then the wave's butterfly: no LDS, no sequential add):
-        // either order of adding <= 256 positive terms is within 3e-14 of the exact sum, so a candidate more than 1e-12 below the
-        // largest tree sum cannot be the arg-max of the ordered sums either.  One survivor (the usual case): it is the arg-max, and
-        // the ordered sums -- a lane adding 100 terms one after the other: half of this pass's time -- are not taken at all; several
-        // (equal samples, true near-ties): only those go through the ordered sums below, which decide as before.
-        bool keep[KPL];
-        {
-          double dq[KPL];
-#pragma unroll
-          for (int u = 0; u < KPL; ++u) dq[u] = -1.0;
-#pragma unroll
-          for (int u = 0; u < KPL; ++u) {
-            unsigned long long mask = __ballot(lane + 64 * u < cnt && (round == 1 || d32[u] >= thr));
-            while (mask) {                                                        // wave-uniform
-              const int k = __builtin_ctzll(mask) + 64 * u;
-              mask &= mask - 1;
-              const double xk = v[k];
-              double loc = 0.0;
-              for (int m = lane; m < cnt; m += 64) { const double d = xk - v[m]; loc += exp(-d * d * inv); }
-              const double dp = wave_sum(loc);
-              if (lane == (k & 63)) dq[u] = dp;
-            }
-          }
-          double mx2 = -1.0;
-#pragma unroll
-          for (int u = 0; u < KPL; ++u) mx2 = fmax(mx2, dq[u]);
-#pragma unroll
-          for (int off = 32; off > 0; off >>= 1) mx2 = fmax(mx2, __shfl_xor(mx2, off, WAVE));
-          const double thr2 = mx2 * (1.0 - 1e-12);
-          int nkeep = 0, first = 0x7fffffff;
-#pragma unroll
-          for (int u = 0; u < KPL; ++u) {
-            keep[u] = dq[u] >= thr2 && dq[u] > 0.0;
-            const unsigned long long mk = __ballot(keep[u]);
-            nkeep += __builtin_popcountll(mk);
-            if (mk && first == 0x7fffffff) first = __builtin_ctzll(mk) + 64 * u;
-          }
-          if (nkeep == 1) { besti = first; break; }
-        }
-#pragma unroll
-        for (int u = 0; u < KPL; ++u) {
-          unsigned long long mask = __ballot(keep[u]);
-          while (mask) {                                                          // wave-uniform
-            int kc[KDE_CB];
-            int nb = 0;
-#pragma unroll
-            for (int c = 0; c < KDE_CB; ++c) {
-              kc[c] = -1;
-              if (mask) { kc[c] = __builtin_ctzll(mask) + 64 * u; mask &= mask - 1; nb = c + 1; }
-            }
-#pragma unroll
-            for (int c = 0; c < KDE_CB; ++c) {
-              if (kc[c] < 0) continue;
-              const double xk = v[kc[c]];
-              for (int m = lane; m < cnt; m += 64) { const double d = xk - v[m]; tm[c * WMAX + m] = exp(-d * d * inv); }
-            }
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_s_waitcnt(0xc07f);
-            double dens = -1.0;
-            if (lane < nb) {
-              dens = 0.0;
-              const double* tp = tm + lane * WMAX;
-              int m = 0;
-              for (; m + 8 <= cnt; m += 8) {                 // (the terms of eight steps requested together; added in index order)
-                double t8[8];
-#pragma unroll
-                for (int x = 0; x < 8; ++x) t8[x] = tp[m + x];
-#pragma unroll
-                for (int x = 0; x < 8; ++x) dens += t8[x];
-              }
-              for (; m < cnt; ++m) dens += tp[m];
-            }
-#pragma unroll
-            for (int c = 0; c < KDE_CB; ++c) {
-              const double dc = __shfl(dens, c, WAVE);
-              if (c < nb && dc > best) { best = dc; besti = kc[c]; }
-            }
-            __builtin_amdgcn_wave_barrier();
-          }
-        }
-      }
-      out = v[besti < cnt ? besti : 0];                    // (all densities NaN -- a covariance whose reciprocal overflows: scipy's arg-max of NaNs is 0)
-    } else {
-      // median by rank counting (cnt <= 256)
-      double lo = 0.0, hi = 0.0;
-      for (int k = lane; k < cnt; k += 64) {
-        const double xk = v[k];
-        int rank = 0;
-        for (int m = 0; m < cnt; ++m) rank += (v[m] < xk) || (v[m] == xk && m < k);
-        if (rank == (cnt - 1) / 2) lo = xk;
-        if (rank == cnt / 2) hi = xk;
-      }
-      out = 0.5 * (wave_sum(lo) + wave_sum(hi));
-    }
-    if (lane == 0) modes[t] = out;
-    __builtin_amdgcn_wave_barrier();
-  }
+#include "kde_mode_body.inc"
 }
 
 // _compute_critic_score :307-333 without the rolling mean: out = |x - mean of the values inside [lo, hi]| / population std of all
@@ -889,36 +382,7 @@ __global__ __launch_bounds__(256) void qs_level_kernel(const double* __restrict_
     else st = qs_descend(ws.hist + ((size_t)(level - 1) * QS_SEL + wave) * QS_BINS, level - 1, ws.state[(level - 1) * QS_SEL + wave], h[wave]);
     if (lane == 0) { cur[wave] = st; if (blockIdx.x == 0) ws.state[level * QS_SEL + wave] = st; }
   }
-  __syncthreads();                                                                  // (h doubled as the scan's staging rows)
-  for (int i = threadIdx.x; i < QS_SEL * QS_BINS; i += 256) (&h[0][0])[i] = 0u;
-  __syncthreads();
-  const int sh = qs_shift(level), bins = qs_bins(level);
-  const int hi_sh = sh + (level == QS_LEVELS - 1 ? 64 - QS_BITS * (QS_LEVELS - 1) : QS_BITS);     // bits above the digit
-  unsigned long long pre[QS_SEL];
-  for (int s2 = 0; s2 < QS_SEL; ++s2) pre[s2] = s2 < nsel ? cur[s2].prefix : 0;
-  unsigned int nans = 0;
-  for (; base < n; base += (int64_t)gridDim.x * (256 * PER)) {
-#pragma unroll
-    for (int u = 0; u < PER; ++u) {
-      if (base + u * 256 + threadIdx.x >= n) continue;
-      if (level == 0 && x[u] != x[u]) ++nans;
-      const unsigned long long k = qs_key(x[u]);
-      const unsigned int digit = (unsigned int)(k >> sh) & (unsigned int)(bins - 1);
-#pragma unroll
-      for (int s2 = 0; s2 < QS_SEL; ++s2)
-        if (s2 < nsel && (hi_sh >= 64 || ((k ^ pre[s2]) >> hi_sh) == 0)) atomicAdd(&h[s2][digit], 1u);
-    }
-    const int64_t nb = base + (int64_t)gridDim.x * (256 * PER);
-#pragma unroll
-    for (int u = 0; u < PER; ++u) { const int64_t i = nb + u * 256 + threadIdx.x; x[u] = i < n ? in[i] : 0.0; }
-  }
-  if (level == 0 && nans) atomicAdd(ws.nan_count, nans);
-  __syncthreads();
-  unsigned int* g = ws.hist + (size_t)level * QS_SEL * QS_BINS;
-  for (int i = threadIdx.x; i < nsel * QS_BINS; i += 256) {
-    const unsigned int c = (&h[0][0])[i];
-    if (c) atomicAdd(g + i, c);
-  }
+#include "qs_level_body.inc"
 }
 // launch QS_PRE + 1: the keys that match a rank's 33-bit prefix -> that rank's candidate list (+ the list's extremes)
 __global__ __launch_bounds__(256) void qs_compact_kernel(const double* __restrict__ in, int64_t n, QsWs ws, int nsel) {
@@ -928,34 +392,7 @@ __global__ __launch_bounds__(256) void qs_compact_kernel(const double* __restric
   constexpr int PER = 4;
   double x[PER];
   int64_t base = (int64_t)blockIdx.x * (256 * PER);
-#pragma unroll
-  for (int u = 0; u < PER; ++u) { const int64_t i = base + u * 256 + threadIdx.x; x[u] = i < n ? in[i] : 0.0; }
-  if (wave < nsel) {
-    const QsState st = qs_descend(ws.hist + ((size_t)(QS_PRE - 1) * QS_SEL + wave) * QS_BINS, QS_PRE - 1, ws.state[(QS_PRE - 1) * QS_SEL + wave], h[wave]);
-    if (lane == 0) { cur[wave] = st; if (blockIdx.x == 0) ws.state[QS_PRE * QS_SEL + wave] = st; }
-  }
-  __syncthreads();
-  const int hi_sh = qs_shift(QS_PRE - 1);                 // the 33 bits fixed so far sit above it
-  unsigned long long pre[QS_SEL];
-  for (int s2 = 0; s2 < QS_SEL; ++s2) pre[s2] = s2 < nsel ? cur[s2].prefix : 0;
-  for (; base < n; base += (int64_t)gridDim.x * (256 * PER)) {
-#pragma unroll
-    for (int u = 0; u < PER; ++u) {
-      if (base + u * 256 + threadIdx.x >= n) continue;
-      const unsigned long long k = qs_key(x[u]);
-#pragma unroll
-      for (int s2 = 0; s2 < QS_SEL; ++s2)
-        if (s2 < nsel && ((k ^ pre[s2]) >> hi_sh) == 0) {
-          const unsigned int pos = atomicAdd(ws.cand_count + s2, 1u);
-          if (pos < (unsigned int)QS_CAND) ws.cand[(size_t)s2 * QS_CAND + pos] = k;
-          atomicMax(ws.kmax + s2, k);
-          atomicMax(ws.kinv + s2, ~k);
-        }
-    }
-    const int64_t nb = base + (int64_t)gridDim.x * (256 * PER);
-#pragma unroll
-    for (int u = 0; u < PER; ++u) { const int64_t i = nb + u * 256 + threadIdx.x; x[u] = i < n ? in[i] : 0.0; }
-  }
+#include "qs_compact_body.inc"
 }
 __device__ __forceinline__ double np_lerp64(double a, double b, double t) {     // numpy.lib._function_base_impl._lerp
 #pragma clang fp contract(off)                   // numpy rounds the product before the sum: no fused multiply-add here
@@ -971,42 +408,7 @@ __global__ __launch_bounds__(1024) void qs_final_kernel(const double* __restrict
   __shared__ unsigned long long keys[QS_SEL];
   __shared__ unsigned int stage[QS_SEL][QS_BINS];
   __shared__ QsState cur[QS_SEL];
-  const int grp = threadIdx.x >> 8, tg = threadIdx.x & 255, lane = threadIdx.x & 63;
-  const bool live = grp < nsel;
-  QsState st = ws.state[QS_PRE * QS_SEL + (live ? grp : 0)];
-  const unsigned int c = live ? ws.cand_count[grp] : 0u;
-  const unsigned long long kmx = live ? ws.kmax[grp] : 0ull, kmn = live ? ~ws.kinv[grp] : 0ull;
-  const bool decided = !live || kmx == kmn;                // (group-uniform) every candidate is the same key
-  const bool listed = c <= (unsigned int)QS_CAND;
-  const unsigned long long* cand = ws.cand + (size_t)(live ? grp : 0) * QS_CAND;
-  const int64_t m = decided ? 0 : (listed ? (int64_t)c : n);
-  unsigned int* hst = stage[live ? grp : 0];
-  for (int level = QS_PRE; level < QS_LEVELS; ++level) {   // (block-uniform trip count; a decided group only keeps the barriers)
-    const int bins = qs_bins(level), sh = qs_shift(level);
-    const int hi_sh = sh + (level == QS_LEVELS - 1 ? 64 - QS_BITS * (QS_LEVELS - 1) : QS_BITS);     // bits above the digit (<= 31)
-    for (int i = tg; i < bins; i += 256) hst[i] = 0u;
-    __syncthreads();
-    for (int64_t i0 = 0; i0 < m; i0 += 4 * 256) {          // four loads in flight per thread
-      unsigned long long k[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int64_t i = i0 + u * 256 + tg;
-        k[u] = i < m ? (listed ? cand[i] : qs_key(in[i])) : ~st.prefix;      // (~prefix never matches)
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        if (((k[u] ^ st.prefix) >> hi_sh) == 0) atomicAdd(hst + ((unsigned int)(k[u] >> sh) & (unsigned int)(bins - 1)), 1u);
-    }
-    __syncthreads();
-    if (tg < 64 && !decided) {                             // the group's first wave scans its histogram
-      const QsState nx = qs_descend_staged(hst, level, st);
-      if (lane == 0) cur[grp] = nx;
-    }
-    __syncthreads();
-    if (!decided) st = cur[grp];
-  }
-  if (live && tg == 0) keys[grp] = decided ? kmx : st.prefix;
-  __syncthreads();
+#include "qs_final_body.inc"
   if (threadIdx.x < nsel / 2) {
     const int j = threadIdx.x;
     double r = np_lerp64(qs_value(keys[2 * j]), qs_value(keys[2 * j + 1]), j == 0 ? t0 : t1);
@@ -1136,8 +538,11 @@ __device__ __forceinline__ int64_t seg_toff(const SegTable& t, int sl, int windo
 
 // unroll_median_kernel<EPL, true, UT> without the summary, per segment: grid (tiles, segments).  A tile lies inside one segment (the
 // tile loop runs over the segment's own timesteps), the interior fast path holds for tiles inside it, n / T are the segment's.
-// (The tile loop is a copy, not a shared function: with the loop moved into one the single-signal kernels' register allocation
-// changed -- their code objects are held identical.)
+// The tile loop is the single-signal kernel's, shared as TEXT: <name>_body.inc holds what a single-signal kernel and its segmented
+// twin both do after their prologues, and each of the two includes it.  Not a shared __device__ function: with the loop moved into
+// one the single-signal kernels' register allocation changed (unroll_median_kernel: 5 spilled scalar registers instead of 12; all
+// eight kde_mode kernels other bytes), and the code objects of the timed kernels are held identical.  An included text is compiled
+// in each kernel as if written there: same bytes as the copies it replaced (docs/history/scoring_shared_bodies.md).
 template <int EPL, int UT>
 __global__ __launch_bounds__(UT * 4) __attribute__((amdgpu_waves_per_eu(UNROLL_WPE, UNROLL_WPE))) void unroll_median_signals_kernel(
     const float* __restrict__ y_all, float* __restrict__ median_all, SegTable tab, int W) {
@@ -1145,192 +550,10 @@ __global__ __launch_bounds__(UT * 4) __attribute__((amdgpu_waves_per_eu(UNROLL_W
   const int64_t n = tab.off[sl + 1] - tab.off[sl];
   const float* __restrict__ y_hat = y_all + tab.off[sl] * W;
   float* __restrict__ median = median_all + seg_toff(tab, sl, W);
-  constexpr int THREADS = UT * 4;                           // (shadows the file's 256: this kernel's block size follows its tile)
-  constexpr int RUN = UT / 64;                               // elements per lane of one source row's run
-  extern __shared__ __attribute__((aligned(16))) float usm[];
-  const int WS = (W + 3) & ~3;                              // tile row stride (floats)
-  float* tile = usm;                                        // [UT][WS]
-  float* sorted = usm + UT * WS;                            // [waves][MAX_WINDOW]   (summary / candidates)
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int wave_s = __builtin_amdgcn_readfirstlane(wave);
-  constexpr int NWV = THREADS / 64;
-  const int64_t T = n + W - 1;
-  float* s = sorted + (wave_s) * MAX_WINDOW;
-  const float INF = __int_as_float(0x7f800000);
-  for (int64_t t0 = (int64_t)blockIdx.x * UT; t0 < T; t0 += (int64_t)gridDim.x * UT) {
-    // ---- stage: rows r in [t0 - (W - 1), t0 + UT) (clipped to the matrix), their runs of this tile's timesteps
-    constexpr int RB = 8 / RUN;                              // rows in flight per wave (8 loads per lane either way)
-    if (t0 >= W - 1 && t0 + UT <= n) {
-      // interior tile (all but the first and last two of a long series): no clipping, j0 == 0, 32-bit indices relative to the
-      // tile's first row, the row number a scalar -- ~9 vector instructions per row and lane instead of ~30 of 64-bit arithmetic
-      const float* base = y_hat + (t0 - (W - 1)) * W;
-      const int nrows = W + UT - 1;
-      for (int kb = wave_s * RB; kb < nrows; kb += NWV * RB) {
-        float val[RB][RUN];
-        int dst[RB][RUN];
-#pragma unroll
-        for (int u = 0; u < RB; ++u) {
-          const int k = kb + u;                              // (scalar) row of the tile's parallelogram
-          const int jb = W - 1 - k > 0 ? W - 1 - k : 0;
-#pragma unroll
-          for (int h = 0; h < RUN; ++h) {
-            const int j = jb + lane + 64 * h, tt = k - (W - 1) + j;
-            const bool ok = k < nrows && j < W && tt < UT;
-            dst[u][h] = ok ? tt * WS + j : -1;
-            val[u][h] = ok ? base[k * W + j] : 0.f;
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < RB; ++u)
-#pragma unroll
-          for (int h = 0; h < RUN; ++h)
-            if (dst[u][h] >= 0) tile[dst[u][h]] = val[u][h];
-      }
-    } else {
-      const int64_t r_lo = t0 - (W - 1) > 0 ? t0 - (W - 1) : 0;
-      const int64_t r_hi = t0 + UT < n ? t0 + UT : n;         // exclusive
-      for (int64_t rb = r_lo + wave * RB; rb < r_hi; rb += NWV * RB) {
-        float val[RB][RUN];
-        int dst[RB][RUN];
-#pragma unroll
-        for (int u = 0; u < RB; ++u) {
-          const int64_t r = rb + u;
-          const int jb = (int)(t0 - r > 0 ? t0 - r : 0);       // first column of row r inside the tile
-#pragma unroll
-          for (int h = 0; h < RUN; ++h) {
-            const int j = jb + lane + 64 * h;                  // (a run is at most UT columns: RUN elements per lane)
-            const int64_t t = r + j;
-            dst[u][h] = -1; val[u][h] = 0.f;
-            if (r < r_hi && j < W && t < t0 + UT && t < T) {
-              const int j0 = (int)(t - n + 1 > 0 ? t - n + 1 : 0);
-              dst[u][h] = (int)(t - t0) * WS + (j - j0);
-              val[u][h] = y_hat[r * W + j];
-            }
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < RB; ++u)
-#pragma unroll
-          for (int h = 0; h < RUN; ++h)
-            if (dst[u][h] >= 0) tile[dst[u][h]] = val[u][h];
-      }
-    }
-    __syncthreads();
-    // (round 6: the timestep a wave works on is a scalar -- as a vector value every count, address and "wave-uniform" branch below was
-    // vector arithmetic and exec-mask code)
-    for (int tt = wave_s; tt < UT; tt += NWV) {
-      const int64_t t = t0 + tt;
-      if (t >= T) break;
-      const int j0 = (int)(t - n + 1 > 0 ? t - n + 1 : 0);
-      const int j1 = (int)(t + 1 < W ? t + 1 : W);
-      const int cnt = j1 - j0;
-      float* v = tile + tt * WS;
-      // pad the row to a multiple of 4 with +inf (never below or equal to a finite value)
-      if (lane < 4 && cnt + lane < ((cnt + 3) & ~3)) v[cnt + lane] = INF;
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): LDS writes of this wave landed
-      float mine[EPL];
-#pragma unroll
-      for (int e = 0; e < EPL; ++e) { const int i = lane + 64 * e; mine[e] = i < cnt ? v[i] : INF; }
-      const int m1 = (cnt - 1) >> 1, m2 = cnt >> 1;
-      float lo_med = 0.f, hi_med = 0.f;
-      bool done = false;
-      if (cnt >= 64) {                                       // wave-uniform (FILTER: median only)
-        // ranks inside the sample v[0 .. 31] (lanes >= 32 idle along)
-        const float sv = v[lane & 31];
-        int less = 0;
-#pragma unroll
-        for (int k0 = 0; k0 < 32; k0 += 4) {
-          const float4 q = *reinterpret_cast<const float4*>(v + k0);
-          less += (q.x < sv ? 1 : 0) + (q.y < sv ? 1 : 0) + (q.z < sv ? 1 : 0) + (q.w < sv ? 1 : 0);
-        }
-        float plo = less <= 10 ? sv : -INF, phi = less >= 21 ? sv : INF;     // 11th smallest (largest with <= 10 below), 22nd smallest
-        plo = hypad::wave_max(plo); phi = hypad::wave_min(phi);                // (DPP butterflies: no LDS round trips on this chain)
-        int c_lt = 0, c_le = 0;
-        unsigned long long cm[EPL];
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) {
-          const bool in = lane + 64 * e < cnt;
-          c_lt += __builtin_popcountll(__ballot(in && mine[e] < plo));
-          c_le += __builtin_popcountll(__ballot(in && mine[e] <= phi));
-          cm[e] = __ballot(in && mine[e] >= plo && mine[e] <= phi);
-        }
-        const int nc = c_le - c_lt;
-        if (c_lt <= m1 && m2 < c_le && nc <= 64 && nc > 0) {
-          // compact the candidates into the wave's slab, rank them against each other
-          int base = 0;
-#pragma unroll
-          for (int e = 0; e < EPL; ++e) {
-            const int pos = base + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(cm[e] >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)cm[e], 0u));
-            if ((cm[e] >> lane) & 1ull) s[pos] = mine[e];
-            base += __builtin_popcountll(cm[e]);
-          }
-          if (lane < 4 && nc + lane < ((nc + 3) & ~3)) s[nc + lane] = INF;
-          __builtin_amdgcn_wave_barrier();
-          __builtin_amdgcn_s_waitcnt(0xc07f);
-          const float c = lane < nc ? s[lane] : INF;
-          int rk = 0;
-          for (int k0 = 0; k0 < nc; k0 += 4) {
-            const float4 q = *reinterpret_cast<const float4*>(s + k0);
-            rk += (q.x < c ? 1 : 0) + (q.y < c ? 1 : 0) + (q.z < c ? 1 : 0) + (q.w < c ? 1 : 0);
-          }
-          // without ties the "less" counts are a permutation of 0 .. nc - 1 (their sum tells): then the lanes holding local ranks
-          // m1 - c_lt and m2 - c_lt hold the two middle values
-          const float rsum = hypad::wave_sum(lane < nc ? (float)rk : 0.f);
-          if (rsum == 0.5f * (float)nc * (float)(nc - 1)) {
-            const unsigned long long k1 = __ballot(lane < nc && rk == m1 - c_lt), k2 = __ballot(lane < nc && rk == m2 - c_lt);
-            lo_med = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c), (int)__builtin_ctzll(k1)));
-            hi_med = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c), (int)__builtin_ctzll(k2)));
-            done = true;
-          }
-          __builtin_amdgcn_wave_barrier();
-        }
-      }
-      if (!done) {
-        // rank = #{k : v[k] < mine} + #{k < i : v[k] == mine}.  Fast pass: count "less" only (one compare + add-carry per value).
-        // Without ties those counts are a permutation of 0 .. cnt-1, with ties two values share a count and the counts' sum falls
-        // short of cnt (cnt - 1) / 2: only then is the ordered tie count needed.  (The sum is exact in fp32: < 2^15 at window 256.)
-        int rank[EPL];
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) rank[e] = 0;
-        for (int k0 = 0; k0 < cnt; k0 += 4) {
-          const float4 q = *reinterpret_cast<const float4*>(v + k0);
-          const float vk[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-          for (int u = 0; u < 4; ++u)
-#pragma unroll
-            for (int e = 0; e < EPL; ++e) rank[e] += vk[u] < mine[e] ? 1 : 0;
-        }
-        float rsum = 0.f;
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) rsum += lane + 64 * e < cnt ? (float)rank[e] : 0.f;
-        const bool ties = hypad::wave_sum(rsum) != 0.5f * (float)cnt * (float)(cnt - 1);
-        if (ties) {                                      // wave-uniform
-#pragma unroll
-          for (int e = 0; e < EPL; ++e) rank[e] = 0;
-          for (int k = 0; k < cnt; ++k) {
-            const float vk = v[k];
-#pragma unroll
-            for (int e = 0; e < EPL; ++e) {
-              const int i = lane + 64 * e;
-              rank[e] += (vk < mine[e]) || (vk == mine[e] && k < i);
-            }
-          }
-        }
-#pragma unroll
-        for (int e = 0; e < EPL; ++e)
-          if (lane + 64 * e < cnt) s[rank[e]] = mine[e];
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_s_waitcnt(0xc07f);
-        lo_med = s[m1]; hi_med = s[m2];
-      }
-      if (lane == 0) {
-        median[t] = (cnt & 1) ? lo_med : (lo_med + hi_med) * 0.5f;     // np.median of float32 stays float32
-      }
-      __builtin_amdgcn_wave_barrier();
-    }
-    __syncthreads();
-  }
+  constexpr bool FILTER = true;                              // medians only: no summary, and none of the development library's stamps
+  double* const summary = nullptr;
+  [[maybe_unused]] long long* const stamps = nullptr;
+#include "unroll_median_body.inc"
 }
 
 
@@ -1364,36 +587,7 @@ __global__ __launch_bounds__(THREADS) void dtw_error_signals_kernel(const double
   const double* __restrict__ y = y_all + to;
   const float* __restrict__ yh = yh_all + to;
   double* __restrict__ out = out_all + to;
-  for (int64_t p = (int64_t)blockIdx.x * THREADS + threadIdx.x; p < T; p += (int64_t)gridDim.x * THREADS) {
-    const int64_t i = p - HALF;                 // window start in padded coordinates
-    if (i < 0 || i >= T - LEN) { out[p] = 0.0; continue; }
-    double a[LEN], b[LEN], row[LEN];
-#pragma unroll
-    for (int k = 0; k < LEN; ++k) {
-      int64_t src = i + k - HALF;               // y_pad[i + k] = y[i + k - HALF]
-      bool ok = src >= 0 && src < T;
-      a[k] = ok ? y[src] : 0.0;
-      b[k] = ok ? (double)yh[src] : 0.0;
-    }
-    double acc = 0.0;
-#pragma unroll
-    for (int j = 0; j < LEN; ++j) { double d = a[0] - b[j]; acc += d * d; row[j] = acc; }
-#pragma unroll
-    for (int r = 1; r < LEN; ++r) {
-      double diag = row[0];
-      double d0 = a[r] - b[0];
-      row[0] = row[0] + d0 * d0;
-#pragma unroll
-      for (int j = 1; j < LEN; ++j) {
-        double up = row[j];
-        double d = a[r] - b[j];
-        double m = fmin(fmin(up, row[j - 1]), diag);
-        row[j] = d * d + m;
-        diag = up;
-      }
-    }
-    out[p] = sqrt(row[LEN - 1]);
-  }
+#include "dtw_error_body.inc"
 }
 
 // The smoothing, statistics and z-score of up to three error kinds (blockIdx.z) of every segment (blockIdx.y).  Kind k smooths src[k]
@@ -1519,7 +713,8 @@ __global__ __launch_bounds__(256) void zscore_apply_signals_kernel(RecKinds kd, 
 }
 // ---- The critic-score chain of a group (hypad_critic_chain_signals): final_critic_scores :365-404 for every segment at once.  As above,
 // every kernel takes its segment from blockIdx.y (qs_final_signals_kernel: blockIdx.x) and does on it what the single-signal kernel
-// does on that segment alone; the bodies are copies for the reason given at unroll_median_signals_kernel.
+// does on that segment alone.  The KDE and the three radix-selection kernels include the single-signal kernels' bodies (*_body.inc: shared
+// as text, for the reason given at unroll_median_signals_kernel); the statistics kernels, a dozen lines each, are written out.
 
 // kde_mode_kernel<KPL> per segment: grid (workgroups of the longest segment, segments).  n, the critic values and the modes are the
 // segment's (scalars out of the kernel arguments); a timestep's mode depends on its own segment's values only, so the partition of
@@ -1532,279 +727,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(KDE_WPE
   if ((int64_t)blockIdx.x * (THREADS / 64) >= n + W - 1) return;                     // (workgroup-uniform: beyond a short segment's end)
   const float* __restrict__ critic = critic_all + tab.off[sl];
   double* __restrict__ modes = modes_all + seg_toff(tab, sl, W);
-  constexpr int WMAX = 64 * KPL;                            // the window class: 9 KB of LDS per workgroup and slot, 18 KB at window 100
-  __shared__ double vals[THREADS / 64][WMAX];
-  __shared__ __attribute__((aligned(16))) float vals32[THREADS / 64][WMAX + 4];      // + the padding the fp32 pass reads past the end
-  __shared__ __attribute__((aligned(16))) float nsq32[THREADS / 64][WMAX + 4];       // -(value^2) for the factored form of the fp32 pass
-  __shared__ double terms[THREADS / 64][KDE_CB * WMAX];
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int64_t T = n + W - 1;
-  double* v = vals[wave];
-  float* vf = vals32[wave];
-  float* nf = nsq32[wave];
-  // per-thread constants of the timestep loop, held in SCALAR registers (they are wave-uniform; as vector values the compiler kept them
-  // in scratch memory across the loop: 20 bytes of private segment per lane and two scratch loads per timestep)
-  auto uniform = [](double x) __attribute__((always_inline)) {
-    return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(x)), __builtin_amdgcn_readfirstlane(__double2loint(x)));
-  };
-  // Scott's factor n^(-2/5) for every sample count 1 .. W, one power per thread, once (the 2 (W - 1) edge timesteps have fewer than W
-  // samples; a double-precision pow inside the loop -- ~200 instructions, its 40 polynomial constants hoisted into vector registers
-  // across the loop -- was what this kernel spilled around)
-  __shared__ double scott[WMAX];
-  for (int c = threadIdx.x; c < W && c < WMAX; c += THREADS) scott[c] = pow((double)(c + 1), -0.4);
-  __syncthreads();
-  const double rW1 = uniform(W > 1 ? 1.0 / (double)(W - 1) : 0.0);
-  for (int64_t t = (int64_t)blockIdx.x * (THREADS / 64) + wave; t < T; t += (int64_t)gridDim.x * (THREADS / 64)) {
-    const int j0 = (int)(t - n + 1 > 0 ? t - n + 1 : 0);
-    const int j1 = (int)(t + 1 < W ? t + 1 : W);
-    const int cnt = __builtin_amdgcn_readfirstlane(j1 - j0);      // (wave-uniform: the pair loops below run on scalar counters)
-    double s = 0.0;
-    for (int k = lane; k < cnt; k += 64) {
-      const float xf = critic[t - (j0 + k)];
-      v[k] = (double)xf;
-      vf[k] = xf;
-      s += (double)xf;
-    }
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-    const double mean = wave_sum(s) / (double)cnt;
-    double q = 0.0;
-    for (int k = lane; k < cnt; k += 64) { const double d = v[k] - mean; q += d * d; }
-    const double var = cnt > 1 ? wave_sum(q) * (cnt == W ? rW1 : 1.0 / (double)(cnt - 1)) : 0.0;      // np.cov: ddof = 1, `c *= 1 / fact`
-    // Scott: factor = n^(-1/5), squared.  (All but the 2 (W - 1) edge timesteps have cnt == W: that power is taken once per
-    // thread, not once per timestep -- a double-precision pow is ~200 instructions.)
-    const double cov = var * uniform(scott[cnt - 1]);
-    double out;
-    if (cnt > 1 && cov > 0.0 && cov == cov) {
-      // pass 1: fp32 densities of this lane's samples.  exp(-d^2 inv) = exp2(-(c d)^2) with c = sqrt(inv log2 e): the samples are
-      // centred and rescaled once (pass 2 reads the fp64 copies), so a pair costs a subtract, a multiply, an exp2 and an add; the
-      // slab is padded with +inf to a multiple of four (a padded pair contributes exp2(-inf) = 0) and read four values at a
-      // time, every value once for all of the lane's samples.
-      // The samples are CENTRED first, in fp64 (densities depend on differences only): rescaling the raw values would leave the
-      // fp32 copies with an absolute error of |value| 2^-24 c, which at |mean| / bandwidth beyond ~1e4 exceeds the screen's margin.
-      // The scale itself only has to be good to fp32 (an error in it is a slightly different bandwidth for every sample alike: 2e-7
-      // relative in the densities): one v_rsq_f32 instead of an fp64 division and square root per timestep; the fp64 1 / (2 cov) that
-      // pass 2 uses is taken only when pass 2 runs.  (A covariance outside the fp32 range makes the screen all-NaN or all-equal: pass 2
-      // then sees every sample, as before.)
-      const double c64 = (double)__builtin_amdgcn_rsqf((float)cov * 1.3862943611198906f);     // sqrt(log2 e / (2 cov))
-      float amax = 0.f;
-      for (int k = lane; k < cnt; k += 64) {
-        const float y = (float)((v[k] - mean) * c64);
-        vf[k] = y; nf[k] = -(y * y);
-        amax = fmaxf(amax, fabsf(y));
-      }
-      amax = wave_max(amax);
-      // (Measured and dropped in round 3, twice: using the kernel matrix's symmetry -- each unordered pair evaluated once.  With the
-      // partner's share delivered by ds_add_f32: 3.28 ms against 0.42 ms for 125 000 windows (LDS float atomics).  With the values
-      // parked in a small LDS matrix in chunks of eight steps and collected by the partners after a wave barrier (no atomics,
-      // conflict-free strides, immediate offsets): 0.69 ms -- three per-lane LDS operations per pair cost more issue time than the
-      // quarter-rate exponential they save; the broadcast form below reads each value once for all 64 lanes.)
-      const bool factored = amax <= 8.f;                   // (wave-uniform; NaN -> the direct form)
-      if (lane < 4 && cnt + lane < ((cnt + 3) & ~3)) {      // padding to a multiple of four: a pair that contributes exp2(-inf) = 0 in either form
-        vf[cnt + lane] = factored ? 0.f : __int_as_float(0x7f800000);
-        nf[cnt + lane] = __int_as_float(0xff800000);
-      }
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_s_waitcnt(0xc07f);
-      // (Measured and dropped in round 3: giving the cnt % 64 samples of the last slot 64 / b lanes each -- groups of b = 32, 16, ..
-      // samples by the binary digits of the remainder, each lane a share of the values, shares added by xor shuffles: 25 + 13 + 2 steps
-      // of four values per lane at window 100 instead of 25 + 25, 20 % fewer exponentials by counter, and no faster: 0.292 against
-      // 0.287 ms.  Per-lane LDS addresses and the shuffles cost what the idle lanes did.)
-      float d32[KPL], xs[KPL];
-      float acc[KPL][4];                                   // one accumulator per position in the group of four: <= ceil(cnt / 4) terms each
-#pragma unroll
-      for (int u = 0; u < KPL; ++u) {
-        const int k = lane + 64 * u;
-        xs[u] = vf[k < cnt ? k : 0];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) acc[u][c] = 0.f;
-      }
-      const int nu = (cnt + 63) >> 6;                                             // sample slots in use (wave-uniform)
-      if (factored) {
-        // exp2(-(x - v)^2) = exp2(-x^2) exp2(2 x v - v^2): the pair costs a fused multiply-add (2 x in a register, v and -v^2 from
-        // LDS), an exp2 and an add -- three issue slots instead of four -- and exp2(-x^2) multiplies the finished sum once.
-        // |x|, |v| <= 8 keeps 2 x v - v^2 <= x^2 <= 64 inside the fp32 exponent range and its rounding (the product's and
-        // -v^2's: 2^-24 x 64 each at the very worst) inside the budget written out at the threshold below.
-        float x2[KPL];
-#pragma unroll
-        for (int u = 0; u < KPL; ++u) x2[u] = 2.f * xs[u];
-        for (int m = 0; m < cnt; m += 4) {
-          const float4 q4 = *reinterpret_cast<const float4*>(vf + m);
-          const float4 n4 = *reinterpret_cast<const float4*>(nf + m);
-          const float vm[4] = {q4.x, q4.y, q4.z, q4.w}, nm[4] = {n4.x, n4.y, n4.z, n4.w};
-#pragma unroll
-          for (int u = 0; u < KPL; ++u) {
-            if (u >= nu) continue;
-            // (two fused multiply-adds per instruction: v_pk_fma_f32 -- the same roundings)
-            typedef float v2f __attribute__((ext_vector_type(2)));
-            const v2f xx = {x2[u], x2[u]};
-            const v2f a01 = __builtin_elementwise_fma(xx, v2f{vm[0], vm[1]}, v2f{nm[0], nm[1]});
-            const v2f a23 = __builtin_elementwise_fma(xx, v2f{vm[2], vm[3]}, v2f{nm[2], nm[3]});
-            acc[u][0] += __builtin_amdgcn_exp2f(a01.x); acc[u][1] += __builtin_amdgcn_exp2f(a01.y);
-            acc[u][2] += __builtin_amdgcn_exp2f(a23.x); acc[u][3] += __builtin_amdgcn_exp2f(a23.y);
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < KPL; ++u) d32[u] = ((acc[u][0] + acc[u][1]) + (acc[u][2] + acc[u][3])) * __builtin_amdgcn_exp2f(-(xs[u] * xs[u]));
-      } else {
-        for (int m = 0; m < cnt; m += 4) {
-          const float4 q4 = *reinterpret_cast<const float4*>(vf + m);
-          const float vm[4] = {q4.x, q4.y, q4.z, q4.w};
-#pragma unroll
-          for (int u = 0; u < KPL; ++u) {
-            if (u >= nu) continue;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) { const float d = xs[u] - vm[c]; acc[u][c] += __builtin_amdgcn_exp2f(-(d * d)); }
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < KPL; ++u) d32[u] = (acc[u][0] + acc[u][1]) + (acc[u][2] + acc[u][3]);
-      }
-      float mx = -1.f;
-#pragma unroll
-      for (int u = 0; u < KPL; ++u) {
-        if (lane + 64 * u >= cnt) d32[u] = -1.f;
-        mx = fmaxf(mx, d32[u]);
-      }
-      mx = wave_max(mx);
-      // Relative error of an fp32 density D~ against the exact D, all terms positive.  Direct form, exp2(-(x - v)^2):
-      //  * arguments: a centred, rescaled sample y carries 2^-24 |y| <= 1e-6 (|y| < 32 for every pair that contributes: two of <= 256
-      //    samples within a few units of each other lie at most 2.6 sqrt(255 / 2) = 29 units from the mean; a lone outlier beyond that
-      //    sees only its own term, exactly 1), a difference d twice that, d^2 an absolute 2 |d| 2e-6 (+ 2^-24 d^2 from the product);
-      //    a term's relative error is ln 2 times that, and weighted by the terms themselves (|d| 2^(-d^2) <= 0.52, the self term is 1)
-      //    the sum's is <= 3e-6;
-      //  * v_exp_f32: 1 ulp = 1.2e-7;
-      //  * accumulation: four partial sums of <= 64 terms, each add 2^-24 of a partial sum that never exceeds the result: 3.8e-6, + 1.2e-7
-      //    for the two combining adds
-      // -> eps <= 7.1e-6 at window 256 (4.8e-6 at 100).  Factored form (all |y| <= 8), exp2(-x^2) exp2(2 x v - v^2):
-      //  * the samples' own rounding (|y| <= 8: 2^-24 x 8): 0.7e-6 by the same weighting;
-      //  * the argument 2 x v - v^2 (|.| <= 64): -v^2 rounded once, the fused multiply-add once, 2^-24 x 64 = 3.8e-6 absolute together
-      //    at the very worst -> ln 2 x 3.8e-6 = 2.6e-6;  exp2(-x^2): x^2 rounded (1.9e-6 absolute -> 1.3e-6) + 1 ulp;
-      //  * v_exp_f32 1.2e-7, accumulation 3.9e-6 as above, the closing product 6e-8
-      // -> eps <= 8.8e-6.  If k* is the true arg-max, D~[k*] >= (1 - eps) D[k*] >= (1 - eps) D[j] >= (1 - eps) / (1 + eps) D~[j] for
-      // every j: the screen keeps k* as long as its margin exceeds 2 eps = 1.8e-5.  Margin 4e-5 (rounds 2-3 used 2e-4 with one
-      // accumulator per sample: 1.7 fp64 evaluations per timestep on random-normal values, 0.6 now).
-      const float thr = mx * (1.f - 4e-5f);
-      // pass 2: fp64 densities of the candidates, in ascending sample order (the first maximum is kept); of every sample if
-      // pass 1 produced no candidate (a bandwidth so small that its reciprocal leaves the fp32 range makes the screen NaN).
-      // A wave pays for a sequential sum as if all 64 lanes ran it, so a candidate's sum is NOT given to one lane with its
-      // exponentials: the lanes compute a candidate's cnt exponentials side by side into LDS (two per lane at window 100), four
-      // candidates per batch, then lane c adds candidate c's terms in index order -- the same additions in the same order as
-      // the one-lane loop, hence the same bits, at 1/20 of its cycles.
-      double best = -1.0;
-      int besti = 0x7fffffff;
-      double* tm = terms[wave];
-      {
-        // one candidate only: the screen has decided (its margin is far above the fp32 pass's error), no fp64 sum is needed
-        int ncand = 0, first = 0x7fffffff;
-#pragma unroll
-        for (int u = 0; u < KPL; ++u) {
-          const unsigned long long mk = __ballot(lane + 64 * u < cnt && d32[u] >= thr);
-          ncand += __builtin_popcountll(mk);
-          if (mk && first == 0x7fffffff) first = __builtin_ctzll(mk) + 64 * u;
-        }
-        if (ncand == 1) besti = first;
-      }
-      double inv = 0.0;
-      if (__builtin_amdgcn_readfirstlane(besti) == 0x7fffffff) inv = 0.5 / cov;          // (only the fp64 pass needs it)
-      for (int round = 0; round < 2 && besti == 0x7fffffff; ++round) {
-        // First the candidates' fp64 densities as TREE sums (a lane's own terms, then the wave's butterfly: no LDS, no sequential add):
-        // either order of adding <= 256 positive terms is within 3e-14 of the exact sum, so a candidate more than 1e-12 below the
-        // largest tree sum cannot be the arg-max of the ordered sums either.  One survivor (the usual case): it is the arg-max, and
-        // the ordered sums -- a lane adding 100 terms one after the other: half of this pass's time -- are not taken at all; several
-        // (equal samples, true near-ties): only those go through the ordered sums below, which decide as before.
-        bool keep[KPL];
-        {
-          double dq[KPL];
-#pragma unroll
-          for (int u = 0; u < KPL; ++u) dq[u] = -1.0;
-#pragma unroll
-          for (int u = 0; u < KPL; ++u) {
-            unsigned long long mask = __ballot(lane + 64 * u < cnt && (round == 1 || d32[u] >= thr));
-            while (mask) {                                                        // wave-uniform
-              const int k = __builtin_ctzll(mask) + 64 * u;
-              mask &= mask - 1;
-              const double xk = v[k];
-              double loc = 0.0;
-              for (int m = lane; m < cnt; m += 64) { const double d = xk - v[m]; loc += exp(-d * d * inv); }
-              const double dp = wave_sum(loc);
-              if (lane == (k & 63)) dq[u] = dp;
-            }
-          }
-          double mx2 = -1.0;
-#pragma unroll
-          for (int u = 0; u < KPL; ++u) mx2 = fmax(mx2, dq[u]);
-#pragma unroll
-          for (int off = 32; off > 0; off >>= 1) mx2 = fmax(mx2, __shfl_xor(mx2, off, WAVE));
-          const double thr2 = mx2 * (1.0 - 1e-12);
-          int nkeep = 0, first = 0x7fffffff;
-#pragma unroll
-          for (int u = 0; u < KPL; ++u) {
-            keep[u] = dq[u] >= thr2 && dq[u] > 0.0;
-            const unsigned long long mk = __ballot(keep[u]);
-            nkeep += __builtin_popcountll(mk);
-            if (mk && first == 0x7fffffff) first = __builtin_ctzll(mk) + 64 * u;
-          }
-          if (nkeep == 1) { besti = first; break; }
-        }
-#pragma unroll
-        for (int u = 0; u < KPL; ++u) {
-          unsigned long long mask = __ballot(keep[u]);
-          while (mask) {                                                          // wave-uniform
-            int kc[KDE_CB];
-            int nb = 0;
-#pragma unroll
-            for (int c = 0; c < KDE_CB; ++c) {
-              kc[c] = -1;
-              if (mask) { kc[c] = __builtin_ctzll(mask) + 64 * u; mask &= mask - 1; nb = c + 1; }
-            }
-#pragma unroll
-            for (int c = 0; c < KDE_CB; ++c) {
-              if (kc[c] < 0) continue;
-              const double xk = v[kc[c]];
-              for (int m = lane; m < cnt; m += 64) { const double d = xk - v[m]; tm[c * WMAX + m] = exp(-d * d * inv); }
-            }
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_s_waitcnt(0xc07f);
-            double dens = -1.0;
-            if (lane < nb) {
-              dens = 0.0;
-              const double* tp = tm + lane * WMAX;
-              int m = 0;
-              for (; m + 8 <= cnt; m += 8) {                 // (the terms of eight steps requested together; added in index order)
-                double t8[8];
-#pragma unroll
-                for (int x = 0; x < 8; ++x) t8[x] = tp[m + x];
-#pragma unroll
-                for (int x = 0; x < 8; ++x) dens += t8[x];
-              }
-              for (; m < cnt; ++m) dens += tp[m];
-            }
-#pragma unroll
-            for (int c = 0; c < KDE_CB; ++c) {
-              const double dc = __shfl(dens, c, WAVE);
-              if (c < nb && dc > best) { best = dc; besti = kc[c]; }
-            }
-            __builtin_amdgcn_wave_barrier();
-          }
-        }
-      }
-      out = v[besti < cnt ? besti : 0];                    // (all densities NaN -- a covariance whose reciprocal overflows: scipy's arg-max of NaNs is 0)
-    } else {
-      // median by rank counting (cnt <= 256)
-      double lo = 0.0, hi = 0.0;
-      for (int k = lane; k < cnt; k += 64) {
-        const double xk = v[k];
-        int rank = 0;
-        for (int m = 0; m < cnt; ++m) rank += (v[m] < xk) || (v[m] == xk && m < k);
-        if (rank == (cnt - 1) / 2) lo = xk;
-        if (rank == cnt / 2) hi = xk;
-      }
-      out = 0.5 * (wave_sum(lo) + wave_sum(hi));
-    }
-    if (lane == 0) modes[t] = out;
-    __builtin_amdgcn_wave_barrier();
-  }
+#include "kde_mode_body.inc"
 }
 
 // ---- np.quantile of every segment at once: the radix selection above with one workspace slice per segment of the launch.  Histogram
@@ -1864,36 +787,7 @@ __global__ __launch_bounds__(256) void qs_level_signals_kernel(const double* __r
     else st = qs_descend(ws.hist + ((size_t)(level - 1) * QS_SEL + wave) * QS_BINS, level - 1, ws.state[(level - 1) * QS_SEL + wave], h[wave]);
     if (lane == 0) { cur[wave] = st; if (blockIdx.x == 0) ws.state[level * QS_SEL + wave] = st; }
   }
-  __syncthreads();                                                                  // (h doubled as the scan's staging rows)
-  for (int i = threadIdx.x; i < QS_SEL * QS_BINS; i += 256) (&h[0][0])[i] = 0u;
-  __syncthreads();
-  const int sh = qs_shift(level), bins = qs_bins(level);
-  const int hi_sh = sh + (level == QS_LEVELS - 1 ? 64 - QS_BITS * (QS_LEVELS - 1) : QS_BITS);     // bits above the digit
-  unsigned long long pre[QS_SEL];
-  for (int s2 = 0; s2 < QS_SEL; ++s2) pre[s2] = s2 < nsel ? cur[s2].prefix : 0;
-  unsigned int nans = 0;
-  for (; base < n; base += (int64_t)gridDim.x * (256 * PER)) {
-#pragma unroll
-    for (int u = 0; u < PER; ++u) {
-      if (base + u * 256 + threadIdx.x >= n) continue;
-      if (level == 0 && x[u] != x[u]) ++nans;
-      const unsigned long long k = qs_key(x[u]);
-      const unsigned int digit = (unsigned int)(k >> sh) & (unsigned int)(bins - 1);
-#pragma unroll
-      for (int s2 = 0; s2 < QS_SEL; ++s2)
-        if (s2 < nsel && (hi_sh >= 64 || ((k ^ pre[s2]) >> hi_sh) == 0)) atomicAdd(&h[s2][digit], 1u);
-    }
-    const int64_t nb = base + (int64_t)gridDim.x * (256 * PER);
-#pragma unroll
-    for (int u = 0; u < PER; ++u) { const int64_t i = nb + u * 256 + threadIdx.x; x[u] = i < n ? in[i] : 0.0; }
-  }
-  if (level == 0 && nans) atomicAdd(ws.nan_count, nans);
-  __syncthreads();
-  unsigned int* g = ws.hist + (size_t)level * QS_SEL * QS_BINS;
-  for (int i = threadIdx.x; i < nsel * QS_BINS; i += 256) {
-    const unsigned int c = (&h[0][0])[i];
-    if (c) atomicAdd(g + i, c);
-  }
+#include "qs_level_body.inc"
 }
 // qs_compact_kernel per segment
 __global__ __launch_bounds__(256) void qs_compact_signals_kernel(const double* __restrict__ in_all, QsSegs a, SegTable tab, int window) {
@@ -1909,34 +803,7 @@ __global__ __launch_bounds__(256) void qs_compact_signals_kernel(const double* _
   const int nsel = a.nsel;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   double x[PER];
-#pragma unroll
-  for (int u = 0; u < PER; ++u) { const int64_t i = base + u * 256 + threadIdx.x; x[u] = i < n ? in[i] : 0.0; }
-  if (wave < nsel) {
-    const QsState st = qs_descend(ws.hist + ((size_t)(QS_PRE - 1) * QS_SEL + wave) * QS_BINS, QS_PRE - 1, ws.state[(QS_PRE - 1) * QS_SEL + wave], h[wave]);
-    if (lane == 0) { cur[wave] = st; if (blockIdx.x == 0) ws.state[QS_PRE * QS_SEL + wave] = st; }
-  }
-  __syncthreads();
-  const int hi_sh = qs_shift(QS_PRE - 1);                 // the 33 bits fixed so far sit above it
-  unsigned long long pre[QS_SEL];
-  for (int s2 = 0; s2 < QS_SEL; ++s2) pre[s2] = s2 < nsel ? cur[s2].prefix : 0;
-  for (; base < n; base += (int64_t)gridDim.x * (256 * PER)) {
-#pragma unroll
-    for (int u = 0; u < PER; ++u) {
-      if (base + u * 256 + threadIdx.x >= n) continue;
-      const unsigned long long k = qs_key(x[u]);
-#pragma unroll
-      for (int s2 = 0; s2 < QS_SEL; ++s2)
-        if (s2 < nsel && ((k ^ pre[s2]) >> hi_sh) == 0) {
-          const unsigned int pos = atomicAdd(ws.cand_count + s2, 1u);
-          if (pos < (unsigned int)QS_CAND) ws.cand[(size_t)s2 * QS_CAND + pos] = k;
-          atomicMax(ws.kmax + s2, k);
-          atomicMax(ws.kinv + s2, ~k);
-        }
-    }
-    const int64_t nb = base + (int64_t)gridDim.x * (256 * PER);
-#pragma unroll
-    for (int u = 0; u < PER; ++u) { const int64_t i = nb + u * 256 + threadIdx.x; x[u] = i < n ? in[i] : 0.0; }
-  }
+#include "qs_compact_body.inc"
 }
 // qs_final_kernel, one workgroup of 1 024 threads per segment (blockIdx.x): segment s's quantiles go to out[(seg0 + s) * nq ..]; a list
 // longer than QS_CAND falls back to the segment's own input range
@@ -1951,42 +818,7 @@ __global__ __launch_bounds__(1024) void qs_final_signals_kernel(const double* __
   const QsWs ws = qs_ws_seg(a, sl);
   const int nsel = a.nsel;
   double* __restrict__ out = out_all + (size_t)(tab.seg0 + sl) * (nsel / 2);
-  const int grp = threadIdx.x >> 8, tg = threadIdx.x & 255, lane = threadIdx.x & 63;
-  const bool live = grp < nsel;
-  QsState st = ws.state[QS_PRE * QS_SEL + (live ? grp : 0)];
-  const unsigned int c = live ? ws.cand_count[grp] : 0u;
-  const unsigned long long kmx = live ? ws.kmax[grp] : 0ull, kmn = live ? ~ws.kinv[grp] : 0ull;
-  const bool decided = !live || kmx == kmn;                // (group-uniform) every candidate is the same key
-  const bool listed = c <= (unsigned int)QS_CAND;
-  const unsigned long long* cand = ws.cand + (size_t)(live ? grp : 0) * QS_CAND;
-  const int64_t m = decided ? 0 : (listed ? (int64_t)c : n);
-  unsigned int* hst = stage[live ? grp : 0];
-  for (int level = QS_PRE; level < QS_LEVELS; ++level) {   // (block-uniform trip count; a decided group only keeps the barriers)
-    const int bins = qs_bins(level), sh = qs_shift(level);
-    const int hi_sh = sh + (level == QS_LEVELS - 1 ? 64 - QS_BITS * (QS_LEVELS - 1) : QS_BITS);     // bits above the digit (<= 31)
-    for (int i = tg; i < bins; i += 256) hst[i] = 0u;
-    __syncthreads();
-    for (int64_t i0 = 0; i0 < m; i0 += 4 * 256) {          // four loads in flight per thread
-      unsigned long long k[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int64_t i = i0 + u * 256 + tg;
-        k[u] = i < m ? (listed ? cand[i] : qs_key(in[i])) : ~st.prefix;      // (~prefix never matches)
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        if (((k[u] ^ st.prefix) >> hi_sh) == 0) atomicAdd(hst + ((unsigned int)(k[u] >> sh) & (unsigned int)(bins - 1)), 1u);
-    }
-    __syncthreads();
-    if (tg < 64 && !decided) {                             // the group's first wave scans its histogram
-      const QsState nx = qs_descend_staged(hst, level, st);
-      if (lane == 0) cur[grp] = nx;
-    }
-    __syncthreads();
-    if (!decided) st = cur[grp];
-  }
-  if (live && tg == 0) keys[grp] = decided ? kmx : st.prefix;
-  __syncthreads();
+#include "qs_final_body.inc"
   if (threadIdx.x < nsel / 2) {
     const int j = threadIdx.x;
     long long lo, hi; double fr;

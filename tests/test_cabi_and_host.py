@@ -212,6 +212,26 @@ def test_product_sources_carry_no_overridable_default_and_no_round_switch():
     assert not default.search(guard) and default.search("#ifndef HYPAD_KNOB\n#define HYPAD_KNOB 4\n#endif\n") and default.search("  #if !defined(HYPAD_KNOB)\n\n  # define HYPAD_KNOB (2)\n")
 
 
+def test_shared_kernel_bodies_are_included_by_two_kernels():
+    """a single-signal scoring kernel and its segmented twin share their body as text, csrc/<name>_body.inc, included
+    inside both.  Every fragment is included inside at least two different kernels (one included once, or orphaned by a later edit,
+    is just an indirection), and every `#include "... .inc"` names a fragment that exists."""
+    import glob
+    csrc = os.path.join(ROOT, "hypad_amd", "csrc")
+    fragments = {os.path.basename(p) for p in glob.glob(os.path.join(csrc, "*.inc"))}
+    assert fragments
+    users = {f: set() for f in fragments}
+    for path in glob.glob(os.path.join(csrc, "*")):
+        src = open(path).read()
+        for m in re.finditer(r'^[ \t]*#[ \t]*include[ \t]+"([^"]+\.inc)"', src, re.M):
+            assert m.group(1) in fragments, (os.path.basename(path), m.group(1))
+            # the kernel the directive sits in: the last `__global__ ... void name(` in front of it
+            kernels = re.findall(r"__global__[^;{]*?\bvoid\s+(\w+)\s*\(", src[:m.start()], re.S)
+            assert kernels, (os.path.basename(path), m.group(1))
+            users[m.group(1)].add(kernels[-1])
+    assert all(len(k) >= 2 for k in users.values()), {f: sorted(k) for f, k in users.items() if len(k) < 2}
+
+
 def test_no_scratch_in_the_kernels_the_baseline_configs_run():
     """Code-object metadata of the built gfx950 objects (hypad_amd.build.kernel_metadata: the notes hipcc wrote): the kernels the BASELINE
     configs launch -- every compile-time instantiation of configs[0..2]'s shape (window 100, latent 20, batch 64), the generator / dW / scoring
