@@ -182,6 +182,7 @@ _SIGS = {
     "hypad_critic_score_workspace_bytes": (c_size_t, []),
     "hypad_critic_score": (c_int, [P, P, c_int64, P, c_size_t, P]),
     "hypad_row_norms": (c_int, [P, P, c_int64, c_int, P]),
+    "hypad_row_diff_norms": (c_int, [P, P, P, c_int64, c_int, P]),
     "hypad_combine_scores": (c_int, [c_int, P, P, P, P, c_int64, P]),
     "hypad_score_signals_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "hypad_score_forward_signals": (c_int, [P, P, P, c_int, POINTER(c_int64), POINTER(c_int64), P, c_int64, P, P, P, P, P, c_int, c_int, c_int,
@@ -191,6 +192,8 @@ _SIGS = {
     "hypad_critic_score_signals_workspace_bytes": (c_size_t, [c_int, POINTER(c_int64), c_int]),
     "hypad_critic_score_signals": (c_int, [P, P, c_int, POINTER(c_int64), c_int, P, c_size_t, P]),
     "hypad_combine_scores_signals": (c_int, [c_int, P, P, P, P, c_int, POINTER(c_int64), c_int, P]),
+    "hypad_zscore_clip_signals_workspace_bytes": (c_size_t, [c_int]),
+    "hypad_zscore_clip_signals": (c_int, [P, P, c_int, POINTER(c_int64), c_void_p, c_size_t, P]),
     "hypad_unroll_median_signals": (c_int, [P, P, c_int, POINTER(c_int64), c_int, P]),
     "hypad_rec_scores_signals_workspace_bytes": (c_size_t, [c_int, POINTER(c_int64), c_int]),
     "hypad_rec_scores_signals": (c_int, [c_int, P, P, P, P, P, c_int, POINTER(c_int64), c_int, c_int, c_void_p, c_size_t, P]),

@@ -175,7 +175,8 @@ def score_signals(x_list, models, signal_shape, latent_dim, hyperbolic):
     models: [(encoder, decoder, critic_x)] per signal, or an Engine (its arenas as they are).  Signal s's rows of every output are
     those of score_windows on that signal alone, bit for bit.
     Returns dict(recons, eucl, hyper_real, critic, rowdist: device tensors concatenated in signal order (None where the mode has
-    none), row_off: [0, n_0, n_0 + n_1, ...])."""
+    none), row_off: [0, n_0, n_0 + n_1, ...], x: the fp32 input as uploaded -- the (sum n_s, S) window matrix, or the series back to
+    back in the series view)."""
     S, L, hyp = int(signal_shape), int(latent_dim), bool(hyperbolic)
     enc, dec, cx = _stacked_arenas(models)
     n_sig = len(x_list)
@@ -206,4 +207,5 @@ def score_signals(x_list, models, signal_shape, latent_dim, hyperbolic):
     _C.check(_C.lib.hypad_score_forward_signals(_C.ptr(enc), _C.ptr(dec), _C.ptr(cx), n_sig, _C.int64s(row_off), _C.int64s(x_off), _C.ptr(x),
                                                 stride, _C.ptr(hyper), _C.ptr(eucl), _C.ptr(hreal), _C.ptr(critic), _C.ptr(dist), S, L, int(hyp),
                                                 ws.data_ptr(), ws_bytes, _C.stream()), "score_forward_signals")
-    return {"recons": hyper if hyp else eucl, "eucl": eucl, "hyper_real": hreal, "critic": critic, "rowdist": dist, "row_off": row_off}
+    return {"recons": hyper if hyp else eucl, "eucl": eucl, "hyper_real": hreal, "critic": critic, "rowdist": dist, "row_off": row_off,
+            "x": x.reshape(n, S) if stride == S else x}

@@ -473,6 +473,20 @@ __global__ __launch_bounds__(THREADS) void row_norms_kernel(const float* __restr
   }
 }
 
+// row_norms_kernel on the difference a - b, formed in fp32 as it is read (multivariate_anomaly_detection's Euclidean reconstruction
+// score, utils/anomaly_detection_utils.py:157): the same lane partition and the same order of additions, hence the bits of
+// hypad_row_norms on the fp32 difference matrix.
+__global__ __launch_bounds__(THREADS) void row_diff_norms_kernel(const float* __restrict__ a, const float* __restrict__ b, double* __restrict__ out,
+                                                                  int64_t rows, int dim) {
+  const int lane = threadIdx.x & 63;
+  for (int64_t r = (int64_t)blockIdx.x * (THREADS / 64) + (threadIdx.x >> 6); r < rows; r += (int64_t)gridDim.x * (THREADS / 64)) {
+    float s = 0.f;
+    for (int c = lane; c < dim; c += 64) { float v = a[r * dim + c] - b[r * dim + c]; s += v * v; }
+    s = wave_sum(s);
+    if (lane == 0) out[r] = (double)sqrtf(s);
+  }
+}
+
 __global__ __launch_bounds__(THREADS) void combine_kernel(int mode, const double* __restrict__ c, const double* __restrict__ r,
                                                            const double* __restrict__ u, double* __restrict__ out, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * THREADS) {
@@ -709,6 +723,41 @@ __global__ __launch_bounds__(256) void zscore_apply_signals_kernel(RecKinds kd, 
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < T; i += (int64_t)gridDim.x * 256) {
     double z = (io[i] - mean) / sd;
     io[i] = (z != z) ? z : fmax(z, 0.0) + 1.0;  // np.clip keeps NaN
+  }
+}
+// ---- hypad_zscore_clip per segment of a plain segmented vector (hypad_zscore_clip_signals: WINDOW LAYOUT, segment s at off[s]; the
+// multivariate detector's rec_scores, utils/anomaly_detection_utils.py:160-161, 177-178).  The two kernels above without the
+// rolling-mean workspace: the partials of segment seg0 + blockIdx.y are slots (seg0 + blockIdx.y) * STAT_G .. of `parts_all`.
+__global__ __launch_bounds__(256) void zscore_partials_segments_kernel(const double* __restrict__ in_all, StatPart* __restrict__ parts_all, SegTable tab) {
+  __shared__ double sh[4];
+  const int sl = blockIdx.y;
+  const int64_t T = tab.off[sl + 1] - tab.off[sl];
+  const int nb = stat_blocks(T);
+  if ((int)blockIdx.x >= nb) return;                                                  // (workgroup-uniform)
+  const double* __restrict__ in = in_all + tab.off[sl];
+  const int64_t len = (T + nb - 1) / nb;
+  const int64_t b = (int64_t)blockIdx.x * len, e = b + len < T ? b + len : T;
+  double s = 0.0;
+  for (int64_t i = b + threadIdx.x; i < e; i += 256) s += in[i];
+  const double n = e > b ? (double)(e - b) : 0.0;
+  const double mean = n > 0.0 ? block_sum_256(s, sh) / n : 0.0;
+  double q = 0.0;
+  for (int64_t i = b + threadIdx.x; i < e; i += 256) { const double d = in[i] - mean; q += d * d; }
+  q = block_sum_256(q, sh);
+  if (threadIdx.x == 0) { StatPart p; p.n = n; p.mean = mean; p.m2 = q; p.rsum = 0.0; p.rcnt = 0.0; parts_all[(size_t)(tab.seg0 + sl) * STAT_G + blockIdx.x] = p; }
+}
+// (in and out: no __restrict__, in == out is allowed -- every element is read and written by the same thread)
+__global__ __launch_bounds__(256) void zscore_apply_segments_kernel(const double* in_all, const StatPart* __restrict__ parts_all, double* out_all, SegTable tab) {
+  __shared__ StatPart sh[STAT_G];
+  const int sl = blockIdx.y;
+  const int64_t o = tab.off[sl], T = tab.off[sl + 1] - o;
+  const StatPart st = stat_merge_all(parts_all + (size_t)(tab.seg0 + sl) * STAT_G, stat_blocks(T), sh);
+  const double mean = st.mean, sd = sqrt(st.m2 / st.n);
+  const double* in = in_all + o;
+  double* out = out_all + o;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < T; i += (int64_t)gridDim.x * 256) {
+    double z = (in[i] - mean) / sd;
+    out[i] = (z != z) ? z : fmax(z, 0.0) + 1.0;  // np.clip keeps NaN
   }
 }
 // ---- The critic-score chain of a group (hypad_critic_chain_signals): final_critic_scores :365-404 for every segment at once.  As above,
@@ -1138,6 +1187,12 @@ int hypad_row_norms(const float* x, double* out, int64_t rows, int dim, hypad_st
   HYPAD_CHECK_LAUNCH();
   return HYPAD_OK;
 }
+int hypad_row_diff_norms(const float* a, const float* b, double* out, int64_t rows, int dim, hypad_stream_t s) {
+  if (!a || !b || !out || rows <= 0 || dim <= 0) return HYPAD_EINVAL;
+  hipLaunchKernelGGL(row_diff_norms_kernel, dim3(grid_for(rows, THREADS / 64)), dim3(THREADS), 0, (hipStream_t)s, a, b, out, rows, dim);
+  HYPAD_CHECK_LAUNCH();
+  return HYPAD_OK;
+}
 int hypad_combine_scores(int mode, const double* c, const double* r, const double* u, double* out, int64_t n, hypad_stream_t s) {
   if (!out || n < 0 || mode < 0 || mode > HYPAD_COMB_EUCL_SUM) return HYPAD_EINVAL;
   if (n == 0) return HYPAD_OK;
@@ -1197,6 +1252,24 @@ int hypad_combine_scores_signals(int mode, const double* c, const double* r, con
   for (int c0 = 0; c0 < n_signals; c0 += SEG_CHUNK) {        // (SEG_CHUNK segments per launch: the table is a kernel argument)
     const SegTable t = seg_table(row_off, c0, n_signals);
     hipLaunchKernelGGL(combine_signals_kernel, dim3(grid_for(seg_longest(t), THREADS), (unsigned)t.n), dim3(THREADS), 0, (hipStream_t)s, mode, c, r, u, out, t, window);
+    HYPAD_CHECK_LAUNCH();
+  }
+  return HYPAD_OK;
+}
+
+size_t hypad_zscore_clip_signals_workspace_bytes(int n_signals) { return n_signals < 1 ? 0 : (size_t)n_signals * STAT_G * sizeof(StatPart); }
+int hypad_zscore_clip_signals(const double* in, double* out, int n_signals, const int64_t* seg_off, void* workspace, size_t workspace_bytes,
+                              hypad_stream_t s) {
+  const int rc = seg_check(n_signals, seg_off);
+  if (rc) return rc;
+  if (!in || !out) return HYPAD_EINVAL;
+  if (!workspace || workspace_bytes < hypad_zscore_clip_signals_workspace_bytes(n_signals)) return HYPAD_EWORKSPACE;
+  StatPart* parts = (StatPart*)workspace;
+  for (int c0 = 0; c0 < n_signals; c0 += SEG_CHUNK) {
+    const SegTable t = seg_table(seg_off, c0, n_signals);
+    hipLaunchKernelGGL(zscore_partials_segments_kernel, dim3(STAT_G, (unsigned)t.n), dim3(256), 0, (hipStream_t)s, in, parts, t);
+    HYPAD_CHECK_LAUNCH();
+    hipLaunchKernelGGL(zscore_apply_segments_kernel, dim3(grid_for(seg_longest(t), 1024), (unsigned)t.n), dim3(256), 0, (hipStream_t)s, in, (const StatPart*)parts, out, t);
     HYPAD_CHECK_LAUNCH();
   }
   return HYPAD_OK;

@@ -79,7 +79,8 @@ def run_signals(params, names, config_path=None, data_dir="./data", log=print, g
     to 32 models per launch sequence; under ``torchrun`` the signals are sharded over the ranks, one process per GPU) -> the test
     loop and the detector on the rank that trained each signal -> the metrics of all signals gathered on every rank.
     ``grouped_scoring`` (default): the signals this rank trained are scored together (_detect_grouped: one grouped forward, the
-    hyperbolic critic chain per segment, one copy back), with the same numbers and artefacts as the per-signal ``_detect`` loop
+    hyperbolic critic chain per segment, one copy back; multivariate datasets the same way through multivariate_scores_signals,
+    a group being either all multivariate or all univariate), with the same numbers and artefacts as the per-signal ``_detect`` loop
     (``grouped_scoring=False``, ``--per-signal-scoring``).  ``device_intervals`` (``--device-intervals``, grouped scoring only): the
     anomalous intervals of the group come from the device as well (find_anomalies_signals) instead of one host find_anomalies per signal."""
     import copy
@@ -97,7 +98,12 @@ def run_signals(params, names, config_path=None, data_dir="./data", log=print, g
     group = [(t, name) for t, name in zip(sets, names) if trained[name].get("modules") is not None and _groupable(t, trained[name]["path"])]
     if device_intervals and not grouped_scoring:
         raise ValueError("device_intervals needs grouped scoring")
-    outs = _detect_grouped(group, trained, data_dir, log, device_intervals=device_intervals) if grouped_scoring and group else {}
+    outs = {}
+    if grouped_scoring:                                # (a group is of one kind: window matrices with the multivariate detector, or series)
+        for kind in (True, False):
+            members = [g for g in group if _multivariate(g[0]) == kind]
+            if members:
+                outs.update(_detect_grouped(members, trained, data_dir, log, device_intervals=device_intervals))
     for (p, train_ds, test_ds, read_path), name in zip(sets, names):
         mods = trained[name].get("modules")
         if mods is None:
@@ -113,13 +119,21 @@ def run_signals(params, names, config_path=None, data_dir="./data", log=print, g
     return par.gather_signal_metrics(local)
 
 
+def _multivariate(t):
+    """A signal that takes the multivariate detector (anomaly_detection.py:137-140; _detect's test)."""
+    return hasattr(t[1], "device_windows") or t[0].signal == "multivariate"
+
+
 def _groupable(t, path):
-    """A signal _detect_grouped scores: univariate, in the series view, and without a score cache that the per-signal detector
-    would read back -- critic_scores.pickle under ``params.load``; for a Euclidean model any of the four pickles score_anomalies
-    keeps (``path + "dtw.pickle"`` etc., the names it reads).  Those take _detect."""
+    """A signal _detect_grouped scores: a multivariate one with test windows (its detector keeps no score cache), or a univariate
+    one in the series view without a score cache that the per-signal detector would read back -- critic_scores.pickle under
+    ``params.load``; for a Euclidean model any of the four pickles score_anomalies keeps (``path + "dtw.pickle"`` etc., the names it
+    reads).  Those take _detect."""
     import os
     p, train_ds, test_ds, _ = t
-    if hasattr(train_ds, "device_windows") or p.signal == "multivariate" or not hasattr(test_ds, "series_windows"):
+    if _multivariate(t):
+        return len(test_ds.X) > 0
+    if not hasattr(test_ds, "series_windows"):
         return False
     if getattr(p, "load", False) and path and os.path.exists(os.path.join(path, "critic_scores.pickle")):
         return False
@@ -136,7 +150,9 @@ def _detect_grouped(group, trained, data_dir, log, device_intervals=False):
     kinds when a model directory keeps score_anomalies' pickles -- and the critic chain of all signals, in timestep layout), one
     copy back, then the pickles and detect_intervals per signal; the reconstruction matrix comes back only for recons_signal.pt.
     ``device_intervals``: find_anomalies_signals extracts every signal's intervals from the final scores before the copy back, and
-    detect_intervals takes them instead of running find_anomalies."""
+    detect_intervals takes them instead of running find_anomalies.
+    Multivariate signals (window matrices): score_signals on the test sets' ``X``, multivariate_scores_signals, the intervals with the
+    multivariate settings, one copy back; then per signal the test loop's files and multivariate_intervals -- _detect's output dict."""
     import pickle
 
     import pandas as pd
@@ -149,6 +165,8 @@ def _detect_grouped(group, trained, data_dir, log, device_intervals=False):
     hyp = bool(P0.hyperbolic)
     S, L = int(P0.signal_shape), 20
     models = [tuple(trained[name]["modules"][:3]) for _, name in group]
+    if _multivariate(group[0][0]):
+        return _detect_grouped_multivariate(group, trained, models, log, device_intervals)
     res = anomaly_detection.score_signals([t[2] for t, _ in group], models, S, L, hyp)
     row_off = res["row_off"]
     keep = any(trained[name]["path"] for _, name in group)          # (some directory wants the test loop's files and the score pickles)
@@ -209,6 +227,51 @@ def _detect_grouped(group, trained, data_dir, log, device_intervals=False):
         log("predicted intervals:\n{}".format(out["intervals"]))
         log("tn, fp, fn, tp: {}".format(out["confusion"]))
         if out["metrics"]:
+            log("precision: {precision}, recall: {recall}\nf1_score: {f1}, gmean: {gmean}".format(**out["metrics"]))
+        outs[name] = out
+    return outs
+
+
+def _detect_grouped_multivariate(group, trained, models, log, device_intervals):
+    """The multivariate branch of _detect_grouped."""
+    import torch
+
+    from . import anomaly_detection
+    from .utils import anomaly_detection_utils as adu
+    from .utils.dataloader import _yahoo_timestamps
+    P0 = group[0][0][0]
+    hyp = bool(P0.hyperbolic)
+    S = int(P0.signal_shape)
+    res = anomaly_detection.score_signals([t[2] for t, _ in group], models, S, 20, hyp)       # (no series view: the X matrices)
+    row_off = res["row_off"]
+    comb = adu.multivariate_scores_signals(res, res["x"], P0.combination)
+    indices = [_yahoo_timestamps(row_off[k + 1] - row_off[k]) for k in range(len(group))]      # the reference's stand-in index (:133-137)
+    found = [None] * len(group)
+    if device_intervals:                                      # (the detector's settings: multivariate_anomaly_detection :183-187)
+        found = adu.find_anomalies_signals(comb["final_scores"], row_off, index_list=indices, window_size_portion=0.2,
+                                           window_step_size_portion=0.1, anomaly_padding=200)
+    want = {"final": comb["final_scores"]}
+    if any(trained[name]["path"] for _, name in group):       # (some directory wants the test loop's files)
+        want.update(recons=res["recons"], critic=res["critic"])
+        if hyp:
+            want.update(hyper_real=res["hyper_real"], eucl=res["eucl"])
+    host = anomaly_detection._to_host(want)
+    outs = {}
+    for k, ((p, _, test_ds, _), name) in enumerate(group):
+        a, b = row_off[k], row_off[k + 1]
+        raw = trained[name]["path"]
+        if raw:                                               # test_tadgan's cache files
+            path = raw + "/"
+            torch.save(host["recons"][a:b], path + "recons_signal.pt")
+            torch.save(np.asarray(test_ds.X), path + "gt_signal.pt")
+            torch.save(list(host["critic"][a:b]), path + "critic_score.pt")
+            if hyp:
+                torch.save(host["eucl"][a:b], path + "eucl_recons.pt")
+                torch.save(host["hyper_real"][a:b], path + "real_hyper.pt")
+        y = test_ds.y if len(getattr(test_ds, "y", [])) else None
+        out = adu.multivariate_intervals(host["final"][a:b], indices[k], y, intervals=found[k])
+        log("predicted intervals:\n{}".format(out["intervals"]))
+        if out.get("metrics"):
             log("precision: {precision}, recall: {recall}\nf1_score: {f1}, gmean: {gmean}".format(**out["metrics"]))
         outs[name] = out
     return outs

@@ -193,6 +193,17 @@ def row_norms(x):
     return out
 
 
+def row_diff_norms(a, b):
+    """np.linalg.norm(a - b, axis=1) of two fp32 matrices, the difference formed in fp32 on the device (:157, :160-161): the bits of
+    row_norms on the fp32 matrix a - b."""
+    a, b = _f32(a), _f32(b)
+    if a.shape != b.shape or a.dim() != 2:
+        raise ValueError(f"row_diff_norms: shapes {tuple(a.shape)} and {tuple(b.shape)}")
+    out = torch.empty(a.shape[0], device=a.device, dtype=torch.float64)
+    _C.check(_C.lib.hypad_row_diff_norms(_C.ptr(a), _C.ptr(b), _C.ptr(out), a.shape[0], a.shape[1], _C.stream()), "row_diff_norms")
+    return out
+
+
 def combine_scores(combination, critic_scores=[], rec_scores=[], recons_signal=[], norms=None, as_tensor=False):
     """:336-362.  ``norms``: the row norms of ``recons_signal`` when the caller already has them (sharded scoring);
     ``as_tensor``: leave the result on the device instead of returning NumPy."""
@@ -425,8 +436,16 @@ def multivariate_anomaly_detection(recons_signal, true_signal, params, combinati
         ts = np.asarray(true_signal)
         critic_scores = final_critic_scores(critic_score, ts.reshape(len(ts), -1))[: rec_scores.shape[0]]
     final_scores = np.asarray(combine_scores(combination, critic_scores, rec_scores, recons_signal), dtype=np.float64).reshape(-1)
-    intervals = find_anomalies(final_scores, x_index, window_size_portion=0.2, window_step_size_portion=0.1, fixed_threshold=True,
-                               anomaly_padding=200)
+    return multivariate_intervals(final_scores, x_index, y)
+
+
+def multivariate_intervals(final_scores, x_index, y=None, intervals=None):
+    """The host tail of multivariate_anomaly_detection (:183-222) from the final scores on: intervals with the multivariate settings
+    (window 0.2 T, step 0.1 window, padding 200), CASAS-style ground truth from ``y`` and the overlap-segment metrics.  ``intervals``:
+    the signal's (n, 3) rows when they were already extracted (find_anomalies_signals on the device); find_anomalies is skipped then."""
+    if intervals is None:
+        intervals = find_anomalies(final_scores, x_index, window_size_portion=0.2, window_step_size_portion=0.1, fixed_threshold=True,
+                                   anomaly_padding=200)
     out = dict(final_scores=final_scores, intervals=np.asarray(intervals, dtype=np.float64).reshape(-1, 3), known_anomalies=None, metrics=None)
     if y is not None:
         known = casas_anomalies(y, np.asarray(x_index))
@@ -434,6 +453,57 @@ def multivariate_anomaly_detection(recons_signal, true_signal, params, combinati
         if out["intervals"].shape[0] and len(known):
             out["metrics"] = compute_metrics(known, [(r[0], r[1]) for r in out["intervals"]], verbose=False)
     return out
+
+
+def zscore_clip_signals(x, seg_off):
+    """zscore_clip of every segment [seg_off[s], seg_off[s + 1]) of a device vector in one C call (hypad_zscore_clip_signals: two
+    launches per 64 signals): each segment's numbers are zscore_clip's on it alone, bit for bit."""
+    seg_off = [int(v) for v in seg_off]
+    entries = x.numel() if isinstance(x, torch.Tensor) else np.asarray(x).size
+    if entries != seg_off[-1]:
+        raise ValueError(f"x has {entries} entries, the offsets say {seg_off[-1]}")
+    x = _f64(x).reshape(-1)
+    k = len(seg_off) - 1
+    out = torch.empty_like(x)
+    nbytes = _C.lib.hypad_zscore_clip_signals_workspace_bytes(k)
+    ws = _scratch(x.device, nbytes, "zscore_clip_signals")
+    _C.check(_C.lib.hypad_zscore_clip_signals(_C.ptr(x), _C.ptr(out), k, _C.int64s(seg_off), ws.data_ptr(), nbytes, _C.stream()),
+             "zscore_clip_signals")
+    return out
+
+
+def multivariate_scores_signals(res, true, combination="mult"):
+    """multivariate_anomaly_detection (:129-222) up to final_scores for every signal of a score_signals result at once, nothing through
+    the host: the reconstruction score of all rows -- the L2 norm of true - recons (row_diff_norms) or, for a hyperbolic result, the
+    row-wise Poincare distance between the windows on the ball and the reconstructions --, its z-score per signal
+    (zscore_clip_signals), the critic chain per signal (final_critic_scores_signals) where the combination uses it, then the
+    combination (hypad_combine_scores_signals).  ``true``: the group's fp32 window matrix on the device, (sum n_s, S) --
+    score_signals' ``x``.  Each signal's final_scores are multivariate_anomaly_detection's on it alone, bit for bit (all NaN where
+    trunc(n_s * 0.01) is 0 and the critic is used).
+    Returns dict(final_scores (sum n_s,), rec_scores (sum n_s,), critic_scores (sum (n_s + S - 1),) or None, row_off); fp64 on the device."""
+    if combination not in ("sum", "mult", "uncertainty", "critic", "critic_uncertainty", "sum_uncertainty", "rec", "rec_uncertainty"):
+        raise ValueError(combination)
+    row_off = [int(v) for v in res["row_off"]]
+    k = len(row_off) - 1
+    recons = _f32(res["recons"])
+    w = recons.shape[1]
+    if res.get("hyper_real") is None:
+        true = _C.require_cuda(true, "true")
+        if tuple(true.shape) != tuple(recons.shape):
+            raise ValueError(f"true is {tuple(true.shape)}, the reconstructions {tuple(recons.shape)}")
+        rec = row_diff_norms(true, recons)
+    else:
+        rec = gmath.poincare_rowdist(_f32(res["hyper_real"]), recons)
+        rec = rec if rec.dtype == torch.float64 else rec.to(torch.float64)
+    rec_scores = zscore_clip_signals(rec, row_off)
+    critic_scores = None
+    if combination in ("mult", "uncertainty", "sum", "sum_uncertainty", "critic", "critic_uncertainty"):
+        critic_scores = final_critic_scores_signals(res["critic"], row_off, w)
+    u = row_norms(recons) if "uncertainty" in combination else None
+    out = torch.empty(row_off[-1], device=recons.device, dtype=torch.float64)
+    _C.check(_C.lib.hypad_combine_scores_signals(_C.COMB[combination], _C.ptr(critic_scores), _C.ptr(rec_scores), _C.ptr(u), _C.ptr(out), k,
+                                                 _C.int64s(row_off), w, _C.stream()), "combine_signals")
+    return {"final_scores": out, "rec_scores": rec_scores, "critic_scores": critic_scores, "row_off": row_off}
 
 
 def final_critic_scores_signals(critic, row_off, window, with_modes=False):

@@ -515,6 +515,11 @@ size_t hypad_critic_score_workspace_bytes(void);
 int hypad_critic_score(const double* in, double* out, int64_t t, void* workspace, size_t workspace_bytes, hypad_stream_t stream);
 /* np.linalg.norm(recons, axis=1)  :341,347,350,359 */
 int hypad_row_norms(const float* x, double* out, int64_t rows, int dim, hypad_stream_t stream);
+/* np.linalg.norm(true - recons, axis=1) with the fp32 difference formed as the two matrices are read -- the Euclidean reconstruction
+ * score of multivariate_anomaly_detection, utils/anomaly_detection_utils.py:157 (`true_signal - recons_signal`, then the norm of
+ * :160-161).  a, b (rows, dim) fp32; out (rows) fp64, the bits of hypad_row_norms on the fp32 matrix a - b.  One launch; rows of a
+ * signal group need no offsets.  NULL pointer, rows <= 0 or dim <= 0: HYPAD_EINVAL without a launch. */
+int hypad_row_diff_norms(const float* a, const float* b, double* out, int64_t rows, int dim, hypad_stream_t stream);
 /* combine_scores :336-362 */
 enum { HYPAD_COMB_SUM = 0, HYPAD_COMB_MULT = 1, HYPAD_COMB_UNCERTAINTY = 2, HYPAD_COMB_CRITIC = 3,
        HYPAD_COMB_CRITIC_UNCERTAINTY = 4, HYPAD_COMB_SUM_UNCERTAINTY = 5, HYPAD_COMB_REC = 6,
@@ -561,6 +566,15 @@ int hypad_critic_score_signals(const double* modes, double* out, int n_signals, 
  * hypad_combine_scores.  One launch per 64 signals. */
 int hypad_combine_scores_signals(int combination, const double* critic_scores, const double* rec_scores, const double* uncertainty,
                                  double* out, int n_signals, const int64_t* row_off, int window, hypad_stream_t stream);
+/* stats.zscore -> clip(min=0) + 1 of every segment [seg_off[s], seg_off[s + 1]) of a plain segmented fp64 vector -- WINDOW LAYOUT, one
+ * entry per window: the multivariate detector's reconstruction scores, utils/anomaly_detection_utils.py:160-161 (Euclidean) and
+ * :177-178 (hyperbolic), for a group.  Segment s of `out` equals hypad_zscore_clip on that segment alone, bit for bit (the same slices,
+ * the same merge tree; no floating-point atomics, so it does not depend on the group either); in == out is allowed.  seg_off
+ * (n_signals + 1, HOST): checked like row_off.  Two launches per 64 signals, whatever the segment lengths.  No launch when an
+ * argument check fails.  workspace: hypad_zscore_clip_signals_workspace_bytes(n_signals) (0 for n_signals < 1). */
+size_t hypad_zscore_clip_signals_workspace_bytes(int n_signals);
+int hypad_zscore_clip_signals(const double* in, double* out, int n_signals, const int64_t* seg_off, void* workspace,
+                              size_t workspace_bytes, hypad_stream_t stream);
 /* The Euclidean (TadGAN) branch of a group, score_anomalies :407-576 per signal.  Un-roll (reconstruction_errors :918-935): segment s
  * of `median` (timestep layout, fp32) is hypad_unroll_median(y_hat + row_off[s] * window, ., NULL, n_s, window) -- the median of every
  * anti-diagonal of the signal's own rows, no summary.  One launch per 64 signals; a tile never straddles two signals. */

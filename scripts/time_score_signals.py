@@ -8,7 +8,12 @@ Prints one JSON line per case: median wall ms of each path over --reps (after on
 whether the final scores are equal bit for bit.  ``--chain``: the critic-score chain alone on the same cases -- per_segment =
 hypad_kde_mode_signals + hypad_critic_score_signals (one set of launches per signal), segmented = hypad_critic_chain_signals; seeded
 critic values on the device, device tensors in and out, one synchronise at the end of each repetition.  Launch counts: run one case under `rocprofv3 --kernel-trace --stats -- python scripts/time_score_signals.py --cases ragged
---reps 1 --only grouped` (and --only per_signal)."""
+--reps 1 --only grouped` (and --only per_signal).
+``--multivariate [--signals 8,32]``: multivariate signals (window matrices, S = 150, 600-2 000 windows each), hyperbolic and Euclidean
+models -- per_signal = score_windows, one copy back and multivariate_anomaly_detection per signal (main._detect's loop), grouped =
+score_signals + multivariate_scores_signals, one copy back and the host interval search per signal (main._detect_grouped),
+grouped_device = the same with find_anomalies_signals on the device.  ``--reps 0`` runs each selected path once and times nothing
+(for a kernel trace that holds one pass)."""
 import argparse
 import json
 import os
@@ -77,6 +82,82 @@ def chain_alone(args):
         print(json.dumps(row), flush=True)
 
 
+def multivariate(args):
+    """Grouped multivariate scoring against the per-signal loop, from trained models to final scores and intervals on the host."""
+    from types import SimpleNamespace
+
+    from hypad_amd import anomaly_detection as ad
+    from hypad_amd.models import tadgan
+    from hypad_amd.utils import anomaly_detection_utils as adu
+    from hypad_amd.utils.dataloader import _yahoo_timestamps
+    W = 150
+    rng = np.random.default_rng(0)
+    for n_sig in [int(v) for v in args.signals.split(",")]:
+        counts = [int(v) for v in rng.integers(600, 2_001, size=n_sig)]
+        xs = []
+        for k, n in enumerate(counts):
+            t = np.arange(n)[:, None] * 0.07 + np.arange(W)[None, :] * (0.11 + 0.002 * k)
+            x = np.clip(np.sin(t) + 0.1 * rng.standard_normal((n, W)), -1, 1)
+            x[n // 2: n // 2 + 20] *= -0.5                      # a stretch that reconstructs badly
+            xs.append(x)                                        # fp64 windows, as MultivariateDataset.X holds them
+        index = [_yahoo_timestamps(n) for n in counts]
+        for hyp in (True, False):
+            models = []
+            for k in range(n_sig):
+                torch.manual_seed(k)
+                models.append(tuple(m.cuda().eval() for m in (tadgan.Encoder(W, L), tadgan.Decoder(W, L, hyp), tadgan.CriticX(W, L))))
+            P = SimpleNamespace(hyperbolic=hyp, signal_shape=W)
+
+            def per_signal():
+                out = []
+                for k in range(n_sig):
+                    r = ad.score_windows(torch.from_numpy(xs[k]), *models[k], W, L, hyp)
+                    want = {"recons": r["recons"], "critic": r["critic"]}
+                    if hyp:
+                        want["hyper_real"] = r["hyper_real"]
+                    host = ad._to_host(want)
+                    out.append(adu.multivariate_anomaly_detection(host["recons"], host["hyper_real"] if hyp else xs[k], P, "mult",
+                                                                  list(host["critic"])))
+                return out
+
+            def grouped(device_intervals=False):
+                r = ad.score_signals(xs, models, W, L, hyp)
+                f = adu.multivariate_scores_signals(r, r["x"], "mult")
+                ro = r["row_off"]
+                found = [None] * n_sig
+                if device_intervals:
+                    found = adu.find_anomalies_signals(f["final_scores"], ro, index_list=index, window_size_portion=0.2,
+                                                       window_step_size_portion=0.1, anomaly_padding=200)
+                final = ad._to_host({"final": f["final_scores"]})["final"]
+                return [adu.multivariate_intervals(final[ro[k]: ro[k + 1]].copy(), index[k], intervals=found[k]) for k in range(n_sig)]
+
+            row = {"multivariate": True, "hyperbolic": hyp, "signals": n_sig, "windows": int(sum(counts)), "S": W}
+            results = {}
+            for name, fn in (("per_signal", per_signal), ("grouped", grouped), ("grouped_device", lambda: grouped(True))):
+                if args.only and name != args.only:
+                    continue
+                results[name] = fn()
+                ts = []
+                for _ in range(args.reps):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    fn()
+                    ts.append((time.perf_counter() - t0) * 1e3)
+                if ts:
+                    row[name + "_ms"] = round(float(np.median(ts)), 3)
+                    row[name + "_min_max_ms"] = [round(float(min(ts)), 3), round(float(max(ts)), 3)]
+            if "per_signal" in results:
+                ref = results["per_signal"]
+                for name in ("grouped", "grouped_device"):
+                    if name in results:
+                        got = results[name]
+                        row[name + "_bit_equal"] = all(a["final_scores"].tobytes() == b["final_scores"].tobytes() for a, b in zip(got, ref))
+                        row[name + "_same_bounds"] = all(np.array_equal(a["intervals"][:, :2], b["intervals"][:, :2]) for a, b in zip(got, ref))
+                        if name + "_ms" in row and "per_signal_ms" in row:
+                            row[name + "_speedup"] = round(row["per_signal_ms"] / row[name + "_ms"], 2)
+            print(json.dumps(row), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", default="1000,5000,20000,ragged")
@@ -86,9 +167,13 @@ def main():
     ap.add_argument("--rec-error", default="dtw")
     ap.add_argument("--all-kinds", action="store_true")
     ap.add_argument("--chain", action="store_true")
+    ap.add_argument("--multivariate", action="store_true")
+    ap.add_argument("--signals", default="8,32", help="--multivariate: group sizes")
     args = ap.parse_args()
     if args.chain:
         return chain_alone(args)
+    if args.multivariate:
+        return multivariate(args)
     from hypad_amd import anomaly_detection as ad
     from hypad_amd.models import tadgan
     from hypad_amd.utils import anomaly_detection_utils as adu

@@ -1,0 +1,113 @@
+"""CPU-only checks of grouped multivariate scoring (hypad_row_diff_norms, hypad_zscore_clip_signals, main._groupable): the new entry
+points are declared in include/hypad.h, exported and bound at ABI version 7; their argument errors come back with the documented
+codes before anything is launched (no GPU needed); main._groupable takes a multivariate test set that has windows."""
+import ctypes
+import os
+import re
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+import torch
+
+from hypad_amd import _C
+from hypad_amd.utils import anomaly_detection_utils as adu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = ("hypad_row_diff_norms", "hypad_zscore_clip_signals_workspace_bytes", "hypad_zscore_clip_signals")
+EINVAL, EWORKSPACE = -1, -2
+BIG = 1 << 40
+
+
+def _ptr(v):
+    return None if v is None else ctypes.c_void_p(v)
+
+
+def _diff(a=256, b=256, out=256, rows=4, dim=150):
+    return _C.lib.hypad_row_diff_norms(_ptr(a), _ptr(b), _ptr(out), rows, dim, None)
+
+
+def _zs(src=256, out=256, off=(0, 4, 9), n=None, ws=256, ws_bytes=BIG):
+    n = len(off) - 1 if n is None else n
+    return _C.lib.hypad_zscore_clip_signals(_ptr(src), _ptr(out), n, _C.int64s(off) if off is not None else None, _ptr(ws), ws_bytes, None)
+
+
+def test_new_entry_points_are_declared_exported_and_bound():
+    text = open(os.path.join(ROOT, "include", "hypad.h")).read()
+    header = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    declared = set(re.findall(r"\b(hypad_[a-z0-9_]+)\s*\(", header))
+    for name in NEW:
+        assert name in declared, name
+        assert name in _C.EXPORTS and hasattr(_C.lib, name), name
+    assert _C.lib.hypad_abi_version() == 7 == _C.ABI_VERSION and re.search(r"#define HYPAD_ABI_VERSION 7\b", text)
+    for fn in ("row_diff_norms", "zscore_clip_signals", "multivariate_scores_signals", "multivariate_intervals"):
+        assert callable(getattr(adu, fn)), fn
+
+
+def test_declarations_cite_the_reference_lines_they_replace():
+    header = open(os.path.join(ROOT, "include", "hypad.h")).read()
+    for decl, lines in (("int hypad_row_diff_norms", (":157", ":160-161")), ("size_t hypad_zscore_clip_signals_workspace_bytes", (":160-161", ":177-178"))):
+        comment = header[:header.index(decl)].rsplit("/*", 1)[1]
+        for ref in lines:
+            assert ref in comment, (decl, ref)
+
+
+def test_row_diff_norms_argument_errors():
+    assert _diff(a=None) == EINVAL and _diff(b=None) == EINVAL and _diff(out=None) == EINVAL
+    assert _diff(rows=0) == EINVAL and _diff(rows=-1) == EINVAL
+    assert _diff(dim=0) == EINVAL and _diff(dim=-5) == EINVAL
+
+
+@pytest.mark.parametrize("off", [[1, 5, 9], [0, 5, 5, 9], [0, 5, 3], [0]])
+def test_bad_offsets_are_rejected_without_a_launch(off):
+    # (seg_off[0] != 0, an empty segment, descending offsets, no segment at all)
+    assert _zs(off=off) == EINVAL
+
+
+def test_zscore_clip_signals_argument_errors():
+    assert _zs(src=None) == EINVAL and _zs(out=None) == EINVAL
+    assert _zs(off=None, n=2) == EINVAL and _zs(n=0) == EINVAL and _zs(n=-2) == EINVAL
+    wsb = _C.lib.hypad_zscore_clip_signals_workspace_bytes
+    assert wsb(0) == 0 and wsb(-1) == 0
+    for n in (1, 2, 64, 70):
+        need = wsb(n)
+        assert need == n * 256 * 5 * 8                       # n_signals x STAT_G partials of five doubles
+        off = list(range(0, 3 * n + 1, 3))
+        assert _zs(off=off, ws_bytes=need - 1) == EWORKSPACE and _zs(off=off, ws=None) == EWORKSPACE and _zs(off=off, ws_bytes=0) == EWORKSPACE
+    assert wsb(1) == _C.STATS_WORKSPACE_BYTES
+
+
+def test_mirrors_refuse_mismatched_arguments():
+    with pytest.raises(ValueError, match="offsets say 9"):
+        adu.zscore_clip_signals(torch.zeros(8, dtype=torch.float64), [0, 4, 9])
+    with pytest.raises(ValueError):
+        adu.multivariate_scores_signals({"row_off": [0, 3], "recons": None, "hyper_real": None, "critic": None}, None, "product")
+
+
+def _casas_sets(tmp_path, windows):
+    """(params, train set, test set, read_path) as main.run_signals holds them, from CASAS-style tensors; ``windows`` test windows."""
+    from hypad_amd.utils.dataloader_multivariate import MultivariateDataset
+    g = np.random.default_rng(0)
+    seq, gt = tmp_path / "seq.pt", tmp_path / "gt.pt"
+    test_seq = tmp_path / f"test_{windows}.pt"
+    torch.save(torch.from_numpy(g.standard_normal((6, 5, 30)).astype(np.float32)), seq)
+    torch.save(torch.from_numpy(g.standard_normal((windows, 5, 30)).astype(np.float32)), test_seq)
+    torch.save(torch.zeros(1, 100, 1), gt)
+    p = SimpleNamespace(dataset="CASAS", signal="fall", hyperbolic=True, load=False)
+    return (p, MultivariateDataset(seq_path=str(seq), gt_path=str(gt), dataset="CASAS"),
+            MultivariateDataset(seq_path=str(test_seq), gt_path=str(gt), test=True, dataset="CASAS"), "")
+
+
+def test_groupable_takes_a_multivariate_test_set_with_rows(tmp_path):
+    from hypad_amd import main as hmain
+    full = _casas_sets(tmp_path, 7)
+    empty = full[:2] + (SimpleNamespace(X=np.zeros((0, 150)), y=[], device_windows=full[2].device_windows), "")
+    assert full[2].X.shape == (7, 150) and hasattr(full[1], "device_windows")
+    assert hmain._groupable(full, "") is True and hmain._groupable(full, str(tmp_path)) is True
+    assert hmain._groupable(empty, "") is False
+    assert hmain._multivariate(full)
+    # `signal: multivariate` (configs/multivariate.yaml) marks a multivariate run as well, whatever the dataset class
+    plain = (SimpleNamespace(dataset="CASAS", signal="multivariate", hyperbolic=False, load=False), SimpleNamespace(),
+             SimpleNamespace(X=np.zeros((3, 150))), "")
+    assert hmain._groupable(plain, "") is True
+    assert hmain._groupable(plain[:2] + (SimpleNamespace(X=np.zeros((0, 150))), ""), "") is False
