@@ -36,7 +36,7 @@ __global__ __launch_bounds__(THREADS) void linear_fwd_kernel(const float* __rest
   const int valid = (int)min((int64_t)16, rows - r0);
   tile_load(xs, ldx, x + r0 * K, K, 16, K, valid);
   __syncthreads();
-  gemm_nt<1>(xs, ldx, w, K, K, N, identity_map(), b, nullptr, ys, ldy, 0, wst);
+  gemm_nt<1, true>(xs, ldx, w, K, K, N, identity_map(), b, nullptr, ys, ldy, 0, wst);
   __syncthreads();
   for (int i = threadIdx.x; i < valid * N; i += THREADS) {
     int r = i / N, c = i - r * N;
@@ -125,8 +125,8 @@ __global__ __launch_bounds__(THREADS) void lstm_fwd_kernel(const float* __restri
   const int valid = (int)min((int64_t)16, rows - r0);
   tile_load(xs, ldx, x + r0 * K, K, 16, K, valid);
   __syncthreads();
-  gemm_nt<1>(xs, ldx, wf, K, K, 3 * H, lstm_gate_map(H), bif, bhf, gs, ldg, 0, wst);
-  gemm_nt<1>(xs, ldx, wr, K, K, 3 * H, lstm_gate_map(H), bir, bhr, gs, ldg, 3 * H, wst);
+  gemm_nt<1, true>(xs, ldx, wf, K, K, 3 * H, lstm_gate_map(H), bif, bhf, gs, ldg, 0, wst);
+  gemm_nt<1, true>(xs, ldx, wr, K, K, 3 * H, lstm_gate_map(H), bir, bhr, gs, ldg, 3 * H, wst);
   __syncthreads();
   lstm_cell_tile(gs, ldg, H, 16, hs, ldh, gates_save ? gates_save + r0 * 8 * H : nullptr, valid);
   __syncthreads();
@@ -770,7 +770,7 @@ __global__ __launch_bounds__(THREADS) void mobius_linear_fwd_kernel(const float*
   const int valid = (int)min((int64_t)16, rows - r0);
   tile_load(xs, ldx, x + r0 * K, K, 16, K, valid);
   __syncthreads();
-  gemm_nt<1>(xs, ldx, w, K, K, N, identity_map(), nullptr, nullptr, ys, ldy, 0, wst);
+  gemm_nt<1, true>(xs, ldx, w, K, K, N, identity_map(), nullptr, nullptr, ys, ldy, 0, wst);
   __syncthreads();
   if (u_save) tile_store(u_save + r0 * N, N, ys, ldy, 16, N, valid);
   __syncthreads();
@@ -828,6 +828,13 @@ __global__ __launch_bounds__(THREADS) void score_forward_kernel(const float* __r
 
 inline int tiles16(int64_t rows) { return (int)((rows + 15) / 16); }
 
+// zeros on the caller's stream (a parameter gradient summed over no rows); p may be null
+inline int zero_floats(float* p, size_t n, hypad_stream_t s) {
+  if (!p) return HYPAD_OK;
+  hipError_t e = hipMemsetAsync(p, 0, n * sizeof(float), (hipStream_t)s);
+  return e == hipSuccess ? HYPAD_OK : (int)e;
+}
+
 // ---- stand-alone optimizers (the update rules of the training kernels: train_common.h)
 using train::AdamCoef; using train::adam_coef; using train::adam_update; using train::radam_ball_wave;
 __global__ __launch_bounds__(THREADS) void adam_flat_kernel(float* p, const float* g, float* m, float* v, int64_t n, int step,
@@ -855,8 +862,9 @@ extern "C" {
 
 int hypad_linear_act_fwd(const float* x, const float* w, const float* b, float* y, int64_t rows, int K, int N, int act,
                          hypad_stream_t s) {
-  if (!x || !w || !y || rows < 0 || K <= 0 || N <= 0) return HYPAD_EINVAL;
-  if (rows == 0) return HYPAD_OK;
+  if (!w || rows < 0 || K <= 0 || N <= 0) return HYPAD_EINVAL;
+  if (rows == 0) return HYPAD_OK;                          // (an empty batch has no rows to point at: x / y may be NULL)
+  if (!x || !y) return HYPAD_EINVAL;
   size_t lds = (size_t)(16 * (ld_of(K) + ld_of(N)) + WST) * sizeof(float);
   if (lds > 150 * 1024) return HYPAD_EUNSUPPORTED;
   hipError_t e = allow_lds((const void*)linear_fwd_kernel, lds);
@@ -868,10 +876,16 @@ int hypad_linear_act_fwd(const float* x, const float* w, const float* b, float* 
 
 int hypad_linear_act_bwd(const float* x, const float* w, const float* y, const float* gy, float* gx, float* gw, float* gb,
                          float* gpre, int64_t rows, int K, int N, int act, hypad_stream_t s) {
-  if (!w || !gy || rows < 0 || K <= 0 || N <= 0) return HYPAD_EINVAL;
+  if (!w || rows < 0 || K <= 0 || N <= 0) return HYPAD_EINVAL;
+  if (gb && !gw) return HYPAD_EINVAL;                      // (the bias sums ride in the weight-gradient launch)
+  if (rows == 0) {
+    // an empty batch (its row buffers may be NULL): the sums over no rows are zeros, written like any other result
+    int rc = zero_floats(gw, (size_t)N * K, s);
+    return rc ? rc : zero_floats(gb, (size_t)N, s);
+  }
+  if (!gy) return HYPAD_EINVAL;
   if (act != HYPAD_ACT_NONE && !y) return HYPAD_EINVAL;
-  if ((gw || gb) && (!gpre || !x)) return HYPAD_EINVAL;
-  if (rows == 0) return HYPAD_OK;
+  if (gw && (!gpre || !x)) return HYPAD_EINVAL;
   size_t lds = (size_t)16 * (ld_of(K) + ld_of(N)) * sizeof(float);
   if (lds > 150 * 1024) return HYPAD_EUNSUPPORTED;
   hipError_t e = allow_lds((const void*)linear_bwd_data_kernel, lds);
@@ -879,12 +893,11 @@ int hypad_linear_act_bwd(const float* x, const float* w, const float* y, const f
   hipLaunchKernelGGL(linear_bwd_data_kernel, dim3(tiles16(rows)), dim3(THREADS), lds, (hipStream_t)s, w, y, gy, gpre, gx,
                      rows, K, N, act);
   HYPAD_CHECK_LAUNCH();
-  if (gw || gb) {
+  if (gw) {
     int tiles = ((N + 15) / 16) * ((K + 15) / 16);
     int blocks = (tiles + 3) / 4;
     int bb = (N + THREADS - 1) / THREADS;
     if (bb > blocks) blocks = bb;
-    if (!gw) return HYPAD_EINVAL;
     hipLaunchKernelGGL(outer_sum_kernel, dim3(blocks), dim3(THREADS), 0, (hipStream_t)s, gpre, N, x, K, gw, gb, rows, N, K);
     HYPAD_CHECK_LAUNCH();
   }
@@ -894,8 +907,9 @@ int hypad_linear_act_bwd(const float* x, const float* w, const float* y, const f
 int hypad_lstm_bidir_fwd(const float* x, const float* wf, const float* bif, const float* bhf, const float* wr,
                          const float* bir, const float* bhr, float* out, float* gates_save, int64_t rows, int K, int H,
                          hypad_stream_t s) {
-  if (!x || !wf || !bif || !bhf || !wr || !bir || !bhr || !out || rows < 0 || K <= 0 || H <= 0) return HYPAD_EINVAL;
+  if (!wf || !bif || !bhf || !wr || !bir || !bhr || rows < 0 || K <= 0 || H <= 0) return HYPAD_EINVAL;
   if (rows == 0) return HYPAD_OK;
+  if (!x || !out) return HYPAD_EINVAL;
   // many rows: the weights-stationary form (one direction's W_ih in LDS per workgroup); HYPAD_LSTM_LDS=0 keeps the streamed form
   static const int lds_form = HYPAD_TUNE_INT("HYPAD_LSTM_LDS", 1);
   if (lds_form && rows >= 2048 && ((H == 50 && K == 100) || (H == 64 && (K == 128 || K == 50)))) {
@@ -977,8 +991,9 @@ int hypad_lstm_bidir_fwd(const float* x, const float* wf, const float* bif, cons
 
 int hypad_lstm_bidir_bwd(const float* wf, const float* wr, const float* gates_saved, const float* gout, float* ggates,
                          float* gx, int64_t rows, int K, int H, hypad_stream_t s) {
-  if (!wf || !wr || !gates_saved || !gout || rows < 0 || K <= 0 || H <= 0) return HYPAD_EINVAL;
+  if (!wf || !wr || rows < 0 || K <= 0 || H <= 0) return HYPAD_EINVAL;
   if (rows == 0) return HYPAD_OK;
+  if (!gates_saved || !gout) return HYPAD_EINVAL;
   size_t lds = (size_t)16 * (ld_of(K) + ld_of(6 * H) + ld_of(2 * H)) * sizeof(float);
   if (lds > 150 * 1024) return HYPAD_EUNSUPPORTED;
   hipError_t e = allow_lds((const void*)lstm_bwd_kernel, lds);
@@ -1061,9 +1076,10 @@ size_t hypad_mobius_linear_workspace_bytes(int64_t rows, int out_dim) {
 }
 int hypad_mobius_linear_fwd(const float* x, const float* w, const float* bias, float* out, float* u_save, int64_t rows,
                             int K, int N, hypad_stream_t s) {
-  if (!x || !w || !bias || !out || rows < 0 || K <= 0 || N <= 0) return HYPAD_EINVAL;
+  if (!w || !bias || rows < 0 || K <= 0 || N <= 0) return HYPAD_EINVAL;
   if (N > 64 * MAX_EPL) return HYPAD_EUNSUPPORTED;
   if (rows == 0) return HYPAD_OK;
+  if (!x || !out) return HYPAD_EINVAL;
   size_t lds = (size_t)(16 * (ld_of(K) + ld_of(N)) + WST) * sizeof(float);
   if (lds > 150 * 1024) return HYPAD_EUNSUPPORTED;
   hipError_t e = allow_lds((const void*)mobius_linear_fwd_kernel, lds);
@@ -1076,9 +1092,14 @@ int hypad_mobius_linear_fwd(const float* x, const float* w, const float* bias, f
 int hypad_mobius_linear_bwd(const float* x, const float* w, const float* bias, const float* u_saved, const float* go,
                             float* gx, float* gw, float* gbias, void* workspace, size_t workspace_bytes, int64_t rows,
                             int K, int N, hypad_stream_t s) {
-  if (!x || !w || !bias || !u_saved || !go || rows < 0 || K <= 0 || N <= 0) return HYPAD_EINVAL;
+  if (!w || !bias || rows < 0 || K <= 0 || N <= 0) return HYPAD_EINVAL;
+  if (N > 64 * MAX_EPL) return HYPAD_EUNSUPPORTED;
+  if (rows == 0) {                                         // an empty batch: zeros for the parameter gradients (hypad_linear_act_bwd)
+    int rc = zero_floats(gbias, (size_t)N, s);
+    return rc ? rc : hypad_linear_act_bwd(nullptr, w, nullptr, nullptr, nullptr, gw, nullptr, nullptr, 0, K, N, HYPAD_ACT_NONE, s);
+  }
+  if (!x || !u_saved || !go) return HYPAD_EINVAL;
   if (!workspace || workspace_bytes < hypad_mobius_linear_workspace_bytes(rows, N)) return HYPAD_EWORKSPACE;
-  if (rows == 0) return HYPAD_OK;
   float* gu = (float*)workspace;
   float* gb_rows = gu + (size_t)rows * N;
   int rc = hypad_mobius_head_bwd(u_saved, bias, go, gu, gb_rows, rows, N, s);

@@ -132,7 +132,7 @@ __device__ __forceinline__ void nt_tile_staged(const float* __restrict__ Xs, int
 }
 
 // direct (un-staged) tile for odd K / unaligned weights: scalar loads, branch-free
-template <int MT>
+template <int MT, bool SETTLE>
 __device__ __forceinline__ void nt_tile_scalar(const float* __restrict__ Xs, int ldx, const float* __restrict__ wp, int K, int j, int q,
                                                f32x4 (&acc)[MT]) {
   constexpr int CH = MT == 1 ? 16 : 8;
@@ -155,12 +155,22 @@ __device__ __forceinline__ void nt_tile_scalar(const float* __restrict__ Xs, int
       for (int m = 0; m < MT; ++m) acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(live ? a[m][u] : 0.f, b[u], acc[m], 0, 0, 0);
     }
   }
+  // The last MFMA's result needs 11 wait states before a VALU instruction may read it (an 8-pass XDL write), and hipcc (ROCm 7.2)
+  // does not count them across this loop's exit: where the epilogue follows the loop directly (no bias to fetch, K a multiple of 4:
+  // mobius_linear with a weight pointer that is not 8-byte aligned) it emitted `v_mfma ... ; s_cbranch ; s_cbranch ; s_branch ;
+  // v_accvgpr_read a3`, and rows 4 q + 3 of the tile -- the register read first -- came out stale now and then
+  // (tests/test_gpu_dense_layers.py, docs/history/dense_layer_sweep.md).  SETTLE spells the wait out on the loop's exit path; the
+  // stand-alone layer kernels of ops_dense.hip, which take any pointer a caller hands them, ask for it.
+  if constexpr (SETTLE) {
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_nop 7\n\ts_nop 3");
+  }
 }
 
 // Y (LDS) [MT*16][ldy], columns ycol0 .. ycol0+N-1.  X (LDS) [MT*16][ldx], K columns, ldx % 4 == 0, X 16-byte aligned.
 // W rows of length ldw (global, or LDS through a flat pointer); bias pointers (indexed like W rows) may be null.
 // wstage: LDS, WSTAGE_FLOATS per wave of the workgroup (wave-private weight slabs).
-template <int MT>
+template <int MT, bool SETTLE = false>
 __device__ __forceinline__ void gemm_nt(const float* __restrict__ Xs, int ldx, const float* __restrict__ W, int ldw, int K, int N,
                         RowMap map, const float* __restrict__ bias0, const float* __restrict__ bias1,
                         float* __restrict__ Ys, int ldy, int ycol0, float* __restrict__ wstage, int wave_rot = 0) {
@@ -184,7 +194,7 @@ __device__ __forceinline__ void gemm_nt(const float* __restrict__ Xs, int ldx, c
     for (int m = 0; m < MT; ++m) acc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
     if (vw == 4) nt_tile_staged<MT, 4>(Xs, ldx, W, ldw, K, N, t * 16, map, stage, lane, acc);
     else if (vw == 2) nt_tile_staged<MT, 2>(Xs, ldx, W, ldw, K, N, t * 16, map, stage, lane, acc);
-    else nt_tile_scalar<MT>(Xs, ldx, W + (size_t)wr * ldw, K, j, q, acc);
+    else nt_tile_scalar<MT, SETTLE>(Xs, ldx, W + (size_t)wr * ldw, K, j, q, acc);
     if (nv) {
 #pragma unroll
       for (int m = 0; m < MT; ++m)

@@ -82,7 +82,8 @@ int hypad_mobius_head_bwd(const float* u, const float* bias, const float* grad_o
                           float* grad_bias_rows, int64_t rows, int dim, hypad_stream_t stream);
 /* MobiusLinear.forward / mobius_linear  hyperspace/hyrnn_nets.py:186-200, :13-35
  * (hyperbolic_input=False, hyperbolic_bias=True, nonlin=None).  weight (out_dim, in_dim), bias (out_dim).
- * workspace: hypad_mobius_linear_workspace_bytes(rows, out_dim) -- holds u = x W^T for the backward. */
+ * workspace: hypad_mobius_linear_workspace_bytes(rows, out_dim) -- holds u = x W^T for the backward.
+ * rows == 0 (the row buffers and the workspace may then be NULL): the backward writes zeros to grad_weight and grad_bias. */
 size_t hypad_mobius_linear_workspace_bytes(int64_t rows, int out_dim);
 int hypad_mobius_linear_fwd(const float* x, const float* weight, const float* bias, float* out, float* u_save,
                             int64_t rows, int in_dim, int out_dim, hypad_stream_t stream);
@@ -108,22 +109,28 @@ int hypad_column_sum(const float* in, float* out, int64_t rows, int dim, hypad_s
  * Dense building blocks (torch ATen calls of the reference: F.linear, nn.LSTM at T=1).
  * ---------------------------------------------------------------------------------------------- */
 enum { HYPAD_ACT_NONE = 0, HYPAD_ACT_TANH = 1, HYPAD_ACT_LEAKY02 = 2 };
-/* y = act(x W^T + b): nn.Linear + nn.Tanh / nn.LeakyReLU(0.2)  models/tadgan.py:21,34,39,40,77-89 */
+/* y = act(x W^T + b): nn.Linear + nn.Tanh / nn.LeakyReLU(0.2)  models/tadgan.py:21,34,39,40,77-89.  rows == 0 launches nothing (x and y
+ * may then be NULL). */
 int hypad_linear_act_fwd(const float* x, const float* weight, const float* bias, float* y,
                          int64_t rows, int in_dim, int out_dim, int act, hypad_stream_t stream);
-/* grad_x = (grad_y * act'(y)) W ; grad_w = (grad_y * act')^T x ; grad_b = colsum(grad_y * act').  y = forward output. */
+/* grad_x = (grad_y * act'(y)) W ; grad_w = (grad_y * act')^T x ; grad_b = colsum(grad_y * act').  y = forward output.
+ * grad_x, grad_weight, grad_bias and grad_pre_scratch may each be NULL (not computed); grad_weight needs x and grad_pre_scratch, and
+ * grad_bias needs grad_weight: every argument is validated before anything is launched or written.  rows == 0 (the row buffers may
+ * then be NULL) writes zeros to grad_weight and grad_bias on `stream`. */
 int hypad_linear_act_bwd(const float* x, const float* weight, const float* y, const float* grad_y,
                          float* grad_x, float* grad_weight, float* grad_bias, float* grad_pre_scratch,
                          int64_t rows, int in_dim, int out_dim, int act, hypad_stream_t stream);
 /* One bidirectional LSTM layer at seq_len 1 with h0 = c0 = 0 (models/tadgan.py:15-20,35-37 as driven by
  * :24-25,59-60): out (rows, 2*hidden) = [h_fwd | h_rev].  w_ih_* (4*hidden, in_dim) with
  * PyTorch gate order [i,f,g,o]; W_hh cannot influence the result and is not read.
- * gates_save (rows, 2, 4, hidden) receives (i, g, o, tanh(c)) for the backward (may be NULL). */
+ * gates_save (rows, 2, 4, hidden) receives (i, g, o, tanh(c)) for the backward (may be NULL).  rows == 0 launches nothing (x and out
+ * may then be NULL). */
 int hypad_lstm_bidir_fwd(const float* x, const float* w_ih_f, const float* b_ih_f, const float* b_hh_f,
                          const float* w_ih_r, const float* b_ih_r, const float* b_hh_r,
                          float* out, float* gates_save, int64_t rows, int in_dim, int hidden, hypad_stream_t stream);
 /* grad_gates (rows, 2, 4*hidden) pre-activation gradients in PyTorch gate order (f block zero);
- * grad_x (rows, in_dim); parameter gradients follow as grad_gates^T x (hypad_linear weight rule). */
+ * grad_x (rows, in_dim); parameter gradients follow as grad_gates^T x (hypad_linear weight rule).  rows == 0 launches nothing (the
+ * row buffers may then be NULL). */
 int hypad_lstm_bidir_bwd(const float* w_ih_f, const float* w_ih_r, const float* gates_saved, const float* grad_out,
                          float* grad_gates, float* grad_x, int64_t rows, int in_dim, int hidden, hypad_stream_t stream);
 

@@ -1,5 +1,6 @@
 """Shared pieces of the shape sweep (tests/test_shape_sweep_rules.py on CPU, tests/test_gpu_shape_sweep.py on the GPU): the
 comparison rule against fp64 ``oracle/manual.py``, the grid of runtime shapes, and the weights and data every shape starts from.
+``Checker``, ``_ball_rows`` and ``_unaligned`` also serve tests/test_gpu_dense_layers.py.
 
 Comparison rule.  For a compared tensor T with fp64 result ``ref64``:
     err(t) = max|t - ref64| / max(1, max|ref64|)
@@ -213,3 +214,32 @@ def optimizer_step(sd, grads, net, t, hyperbolic, moments=None):
             np_, nm, nv = manual.adam_step(p, g, m, v, t, LR, BETA1, BETA2, ADAM_EPS)
             out[k] = (np_, nm, nv, g)
     return out
+
+
+# ------------------------------------------------------------------------------------------------ data of the row-kernel sweeps
+def _ball_rows(g, rows, dim, tangent=False, zero_row=True, edge=True, radius=0.95):
+    """Rows inside the ball at radii up to ``radius``, one on the 1 - 1e-3 norm (beyond project's limit; edge=False: none), one zero
+    row; tangent=True: rows for expmap0, one with norm above 15 (the tanh clamp)."""
+    a = torch.randn(rows, dim, generator=g, dtype=torch.float64)
+    a = a / a.norm(dim=1, keepdim=True).clamp_min(1e-300)
+    if tangent:
+        r = torch.rand(rows, 1, generator=g, dtype=torch.float64) * 3
+        if rows >= 3:
+            r[1] = 16.0 + rows % 7
+    else:
+        r = torch.rand(rows, 1, generator=g, dtype=torch.float64) * radius
+        if rows >= 3 and edge:
+            r[1] = 1 - 1e-3
+    a = a * r
+    if rows >= 2 and zero_row:
+        a[-1] = 0
+    return a.float()
+
+
+def _unaligned(t):
+    """A contiguous view at storage offset 1 of a larger buffer (the kernels' al == false path)."""
+    buf = torch.empty(t.numel() + 1, device="cuda")
+    v = buf[1:].view(t.shape)
+    v.copy_(t)
+    assert v.is_contiguous() and v.data_ptr() % 16 != 0
+    return v

@@ -286,3 +286,24 @@ def test_design_document_stays_readable():
     for section in ("## 0. Scope", "## 1. The path and its boundary", "## 2. Oracle and parity", "## 3. Data layout in HBM", "## 4. Kernels", "## 5. Measurement",
                     "## 6. Multi-GPU", "## 7. Next components", "## 8. Status"):
         assert section in text, section
+
+
+def test_dense_entry_points_validate_their_arguments_before_any_hip_call(lib):
+    """No GPU needed: each of these is refused by the argument checks, which come before the first HIP call of the entry point (on a
+    machine without a device anything later returns a HIP error code instead).  hypad_linear_act_bwd used to find "grad_bias without
+    grad_weight" only after it had launched the data kernel."""
+    buf = (ctypes.c_float * 4096)()
+    p, n64 = ctypes.cast(buf, ctypes.c_void_p), ctypes.c_int64
+    EINVAL, EWORKSPACE, EUNSUPPORTED = -1, -2, -3
+    # (x, w, y, gy, gx, gw, gb, gpre, rows, K, N, act, stream): a bias gradient without a weight gradient
+    assert lib.hypad_linear_act_bwd(p, p, p, p, p, None, p, p, n64(4), 3, 2, 0, None) == EINVAL
+    assert lib.hypad_linear_act_bwd(p, p, None, p, p, p, p, p, n64(4), 3, 2, 1, None) == EINVAL           # tanh needs y
+    assert lib.hypad_linear_act_bwd(p, p, p, p, p, p, p, None, n64(4), 3, 2, 0, None) == EINVAL           # grad_weight needs the scratch
+    # out_dim 257 > 64 * MAX_EPL; a workspace one float short of hypad_mobius_linear_workspace_bytes(4, 2)
+    assert lib.hypad_mobius_linear_fwd(p, p, p, p, None, n64(4), 3, 257, None) == EUNSUPPORTED
+    lib.hypad_mobius_linear_workspace_bytes.restype = ctypes.c_size_t
+    need = lib.hypad_mobius_linear_workspace_bytes(n64(4), 2)
+    assert need == 4 * 2 * 2 * 4
+    assert lib.hypad_mobius_linear_bwd(p, p, p, p, p, p, p, p, p, ctypes.c_size_t(need - 4), n64(4), 3, 2, None) == EWORKSPACE
+    assert lib.hypad_mobius_linear_bwd(p, p, p, p, p, p, p, p, p, ctypes.c_size_t(1 << 20), n64(4), 3, 257, None) == EUNSUPPORTED
+    assert lib.hypad_mobius_head_bwd(p, p, p, p, None, n64(4), 257, None) == EUNSUPPORTED

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import sweep_common as sc
+from sweep_common import _ball_rows, _unaligned
 from epoch_oracle import NB, NC, cu
 from epoch_oracle import check_step as _check_step, engine as _engine, epoch_against_oracle as _epoch_against_oracle, state as _state
 from oracle import gmath as og
@@ -242,34 +243,6 @@ def test_score_forward_signals_ragged_group_at_a_runtime_window(series_view):
 # ------------------------------------------------------------------------------------------------ 5. stand-alone Poincare-ball kernels
 DIMS = (1, 3, 63, 64, 65, 127, 128, 129, 255, 256)
 ROWS = (1, 2, 3, 5, 4 * 9 + 3)
-
-
-def _ball_rows(g, rows, dim, tangent=False, zero_row=True, edge=True, radius=0.95):
-    """Rows inside the ball at radii up to ``radius``, one on the 1 - 1e-3 norm (beyond project's limit; edge=False: none), one zero
-    row; tangent=True: rows for expmap0, one with norm above 15 (the tanh clamp)."""
-    a = torch.randn(rows, dim, generator=g, dtype=F64)
-    a = a / a.norm(dim=1, keepdim=True).clamp_min(1e-300)
-    if tangent:
-        r = torch.rand(rows, 1, generator=g, dtype=F64) * 3
-        if rows >= 3:
-            r[1] = 16.0 + rows % 7
-    else:
-        r = torch.rand(rows, 1, generator=g, dtype=F64) * radius
-        if rows >= 3 and edge:
-            r[1] = 1 - 1e-3
-    a = a * r
-    if rows >= 2 and zero_row:
-        a[-1] = 0
-    return a.float()
-
-
-def _unaligned(t):
-    """A contiguous view at storage offset 1 of a larger buffer (the kernels' al == false path)."""
-    buf = torch.empty(t.numel() + 1, device="cuda")
-    v = buf[1:].view(t.shape)
-    v.copy_(t)
-    assert v.is_contiguous() and v.data_ptr() % 16 != 0
-    return v
 
 
 def _op_check(ck, name, gpu_fn, ref_fn, ins, gout, unaligned=False):
