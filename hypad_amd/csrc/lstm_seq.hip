@@ -294,10 +294,11 @@ int hypad_lstm_bidir_seq_fwd_train(const float* x, const float* w_ih_f, const fl
                                    const float* w_ih_r, const float* w_hh_r, const float* b_ih_r, const float* b_hh_r, const float* h0,
                                    const float* c0, float* out, float* hn, float* cn, float* saved, int seq_len, int64_t rows, int in_dim,
                                    int hidden, void* workspace, size_t workspace_bytes, hypad_stream_t s) {
-  if (!x || !w_ih_f || !w_hh_f || !b_ih_f || !b_hh_f || !w_ih_r || !w_hh_r || !b_ih_r || !b_hh_r || !out || seq_len <= 0 || rows <= 0 ||
-      in_dim <= 0 || hidden <= 0)
+  if (!w_ih_f || !w_hh_f || !b_ih_f || !b_hh_f || !w_ih_r || !w_hh_r || !b_ih_r || !b_hh_r || seq_len <= 0 || rows < 0 || in_dim <= 0 || hidden <= 0)
     return HYPAD_EINVAL;
   if (hidden > 64) return HYPAD_EUNSUPPORTED;               // four waves x 16 units; W_hh in LDS
+  if (rows == 0) return HYPAD_OK;                           // the empty batch: every row buffer is empty (and may be null), nothing to write
+  if (!x || !out) return HYPAD_EINVAL;
   if (!workspace || workspace_bytes < hypad_lstm_seq_workspace_bytes(seq_len, rows, hidden)) return HYPAD_EWORKSPACE;
   if ((int64_t)seq_len * rows > 0x7fffffff) return HYPAD_EINVAL;
   float* pre_f = (float*)workspace;
@@ -338,10 +339,21 @@ int hypad_lstm_bidir_seq_bwd(const float* x, const float* w_ih_f, const float* w
                              const float* grad_hn, const float* grad_cn, float* grad_x, float* grad_w_ih_f, float* grad_w_hh_f,
                              float* grad_b_f, float* grad_w_ih_r, float* grad_w_hh_r, float* grad_b_r, float* grad_h0, float* grad_c0,
                              int seq_len, int64_t rows, int in_dim, int hidden, void* workspace, size_t workspace_bytes, hypad_stream_t s) {
-  if (!x || !w_ih_f || !w_hh_f || !w_ih_r || !w_hh_r || !out || !saved || seq_len <= 0 || rows <= 0 || in_dim <= 0 || hidden <= 0) return HYPAD_EINVAL;
-  if (!grad_out && !grad_hn && !grad_cn) return HYPAD_EINVAL;
-  if (!grad_x || !grad_w_ih_f || !grad_w_hh_f || !grad_b_f || !grad_w_ih_r || !grad_w_hh_r || !grad_b_r) return HYPAD_EINVAL;
+  if (!w_ih_f || !w_hh_f || !w_ih_r || !w_hh_r || seq_len <= 0 || rows < 0 || in_dim <= 0 || hidden <= 0) return HYPAD_EINVAL;
+  if (!grad_w_ih_f || !grad_w_hh_f || !grad_b_f || !grad_w_ih_r || !grad_w_hh_r || !grad_b_r) return HYPAD_EINVAL;
   if (hidden > 64) return HYPAD_EUNSUPPORTED;
+  if (rows == 0) {                                          // the empty batch: sums over no rows; every row buffer may be null
+    const size_t nih = (size_t)4 * hidden * in_dim, nhh = (size_t)4 * hidden * hidden, nb = (size_t)4 * hidden;
+    float* const gp[6] = {grad_w_ih_f, grad_w_hh_f, grad_b_f, grad_w_ih_r, grad_w_hh_r, grad_b_r};
+    const size_t np[6] = {nih, nhh, nb, nih, nhh, nb};
+    for (int i = 0; i < 6; ++i) {
+      hipError_t e = hipMemsetAsync(gp[i], 0, np[i] * sizeof(float), (hipStream_t)s);
+      if (e != hipSuccess) return (int)e;
+    }
+    return HYPAD_OK;
+  }
+  if (!x || !out || !saved || !grad_x) return HYPAD_EINVAL;
+  if (!grad_out && !grad_hn && !grad_cn) return HYPAD_EINVAL;
   if (!workspace || workspace_bytes < hypad_lstm_seq_bwd_workspace_bytes(seq_len, rows, in_dim, hidden)) return HYPAD_EWORKSPACE;
   if ((int64_t)seq_len * rows > 0x7fffffff) return HYPAD_EINVAL;
   const size_t tr = (size_t)seq_len * rows;

@@ -208,11 +208,15 @@ __device__ __forceinline__ void radam_ball_wave(float* p, float* m, float* v, Ro
 #pragma unroll
   for (int e = 0; e < MAX_EPL; ++e) rg.v[e] = g.v[e] * ilam2;
   float inner = lam * lam * row_dot(rg, rg);
+  // the ball's second moment is ONE number, kept once per element: every element takes the same two roundings (left to the compiler's
+  // contraction, three of a lane's four elements became fma(b2, v, (1 - b2) inner) and the fourth a rounded product plus an add --
+  // the stored vector was no longer one value repeated beyond 192 elements)
+  const float vin = (1.f - c.b2) * inner;
   RowVec np;
 #pragma unroll
   for (int e = 0; e < MAX_EPL; ++e) {
     Mv.v[e] = c.b1 * Mv.v[e] + (1.f - c.b1) * rg.v[e];
-    V.v[e] = c.b2 * V.v[e] + (1.f - c.b2) * inner;
+    V.v[e] = __builtin_fmaf(c.b2, V.v[e], vin);
     float den = __builtin_amdgcn_sqrtf(V.v[e] * ibc2) + c.eps;
     np.v[e] = P.v[e] - c.lr * (Mv.v[e] * ibc1) * __builtin_amdgcn_rcpf(den);
   }

@@ -141,7 +141,8 @@ int hypad_lstm_bidir_bwd(const float* w_ih_f, const float* w_ih_r, const float* 
  * out (seq_len, rows, 2*hidden) = [h_fwd(t) | h_rev(t)]; hn / cn (2, rows, hidden) final states, may be NULL.  The input
  * projections of all steps run as one MFMA GEMM; the recurrence is a persistent kernel per (16-row tile, direction): W_hh in
  * LDS, h_t in LDS, c_t in registers, the four gates of a unit on one lane, one barrier per step.  hidden <= 64.
- * workspace: hypad_lstm_seq_workspace_bytes(seq_len, rows, hidden). */
+ * workspace: hypad_lstm_seq_workspace_bytes(seq_len, rows, hidden).  rows == 0 launches nothing: the row buffers and the
+ * (zero-byte) workspace may then be NULL. */
 size_t hypad_lstm_seq_workspace_bytes(int seq_len, int64_t rows, int hidden);
 int hypad_lstm_bidir_seq_fwd(const float* x, const float* w_ih_f, const float* w_hh_f, const float* b_ih_f, const float* b_hh_f,
                              const float* w_ih_r, const float* w_hh_r, const float* b_ih_r, const float* b_hh_r,
@@ -156,7 +157,8 @@ int hypad_lstm_bidir_seq_fwd(const float* x, const float* w_ih_f, const float* w
  *   the forward took / returned them.  A persistent kernel per (16-row tile, direction) walks the steps in reverse (W_hh^T in
  *   LDS, carried dh / dc in registers, one barrier per step) and writes the pre-activation gradients of every step; the
  *   parameter / input gradients are dense contractions over seq_len * rows rows (hypad_linear_act_bwd).  hidden <= 64.
- * workspace: hypad_lstm_seq_bwd_workspace_bytes(seq_len, rows, in_dim, hidden). */
+ * workspace: hypad_lstm_seq_bwd_workspace_bytes(seq_len, rows, in_dim, hidden).  rows == 0: fwd_train writes nothing, bwd writes
+ *   zeros to the six parameter gradients on the caller's stream; row buffers and workspace may be NULL. */
 int hypad_lstm_bidir_seq_fwd_train(const float* x, const float* w_ih_f, const float* w_hh_f, const float* b_ih_f, const float* b_hh_f,
                                    const float* w_ih_r, const float* w_hh_r, const float* b_ih_r, const float* b_hh_r,
                                    const float* h0, const float* c0, float* out, float* hn, float* cn, float* saved, int seq_len,

@@ -1,6 +1,8 @@
 """Shared pieces of the shape sweep (tests/test_shape_sweep_rules.py on CPU, tests/test_gpu_shape_sweep.py on the GPU): the
 comparison rule against fp64 ``oracle/manual.py``, the grid of runtime shapes, and the weights and data every shape starts from.
-``Checker``, ``_ball_rows`` and ``_unaligned`` also serve tests/test_gpu_dense_layers.py.
+``Checker``, ``_ball_rows`` and ``_unaligned`` also serve tests/test_gpu_dense_layers.py; ``Ck`` (the Checker plus the reduction rule of
+that file's docstring) and the guard / offset helpers at the end serve it, tests/test_gpu_lstm_seq.py and
+tests/test_gpu_optimizer_steps.py.
 
 Comparison rule.  For a compared tensor T with fp64 result ``ref64``:
     err(t) = max|t - ref64| / max(1, max|ref64|)
@@ -15,10 +17,16 @@ errgpu / (C * err32 + F) over every compared tensor of one critic_x, critic_z an
 Euclidean.  The runtime shapes of the grid come out between 0.17 and 0.82 (the largest at (200, 31, 256)).  The rule is the same at
 every shape; no shape gets its own constants.
 
+A recurrence over T steps (tests/test_gpu_lstm_seq.py) passes ``steps=T``: the absolute floor becomes T * F.  F is what ONE application
+of the device activations (hardware exp and reciprocal) was given; a recurrence applies them T times, and err32 already carries the
+growth of rounding.  steps = 1, the default, is the rule above unchanged.
+
 Adam's first step moves a weight by about lr * sign(g) wherever |g| sits at rounding level, so updated parameters are compared under
 the rule only where the fp64 gradient is resolvable (|g64| well above the gradient's own allowance); every other element is bounded
 by the distance Adam can travel in that step.
 """
+import re
+
 import numpy as np
 import torch
 
@@ -90,7 +98,7 @@ class Checker:
     def __init__(self, case=""):
         self.case, self.failures, self.worst = case, [], 0.0
 
-    def cmp(self, name, got, ref64, ref32, mask=None):
+    def cmp(self, name, got, ref64, ref32, mask=None, steps=1):
         g, r64, r32 = _f64(got), _f64(ref64), _f64(ref32)
         assert g.shape == r64.shape == r32.shape, (name, g.shape, r64.shape, r32.shape)
         scale = max(1.0, float(np.abs(r64).max())) if r64.size else 1.0
@@ -104,11 +112,12 @@ class Checker:
         dg = np.where(np.isnan(dg), np.inf, dg)
         e32, i = float(d32.max()) / scale, int(np.argmax(dg))
         eg = float(dg.reshape(-1)[i]) / scale
-        allow = C * e32 + F
+        allow = C * e32 + steps * F
         self.worst = max(self.worst, eg / allow)
         if not eg <= allow:
             j = int(shape_idx[i]) if mask is not None else i
-            self.failures.append(f"{self.case} {name}: errgpu {eg:.3e} > {C:g} * err32 {e32:.3e} + {F:g} at {_where(_f64(ref64).shape, j)}")
+            floor = f"{F:g}" if steps == 1 else f"{steps} * {F:g}"
+            self.failures.append(f"{self.case} {name}: errgpu {eg:.3e} > {C:g} * err32 {e32:.3e} + {floor} at {_where(_f64(ref64).shape, j)}")
 
     def bound(self, name, moved, limit):
         """|moved| <= limit elementwise (Adam's reach where the gradient is not resolvable)."""
@@ -243,3 +252,86 @@ def _unaligned(t):
     v.copy_(t)
     assert v.is_contiguous() and v.data_ptr() % 16 != 0
     return v
+
+
+# ------------------------------------------------------------------------------------------------ the layer sweeps' checker and buffers
+SENTINEL = 12345.0
+NAN = float("nan")
+
+
+class Ck(Checker):
+    """The Checker plus the reduction rule (tests/test_gpu_dense_layers.py's docstring); for the weights-stationary LSTM layer
+    (``tiles=(rows, waves)``) a failure also names the 16-row tile of its worst row and which iteration of its wave's walk that tile
+    is."""
+
+    def __init__(self, case="", tiles=None):
+        super().__init__(case)
+        self.rworst = 0.0
+        self.tstep = None
+        if tiles:
+            rows, nw = tiles
+            ntiles = (rows + 15) // 16
+            self.nw, self.tstep = nw, min(128, -(-ntiles // nw)) * nw      # hypad_lstm_bidir_fwd: at most 128 slices of `nw` waves per direction
+
+    def _tile_note(self, first):
+        for i in range(first, len(self.failures)):
+            m = re.search(r"\(row (\d+),", self.failures[i])
+            if m and self.tstep:
+                tile = int(m.group(1)) // 16
+                self.failures[i] += (f" [tile {tile}: iteration {tile // self.tstep} (from 0) of wave {tile % self.tstep % self.nw} in slice "
+                                     f"{tile % self.tstep // self.nw}, tiles {self.tstep} apart]")
+
+    def cmp(self, name, got, ref64, ref32, mask=None, steps=1):
+        n = len(self.failures)
+        super().cmp(name, got, ref64, ref32, mask, steps)
+        self._tile_note(n)
+
+    def red(self, name, got, ref64, abs_terms, rows, summand_allow=0.0):
+        g, r, t = _f64(got), _f64(ref64), _f64(abs_terms)
+        assert g.shape == r.shape == t.shape, (name, g.shape, r.shape, t.shape)
+        if r.size == 0:
+            return
+        scale = max(1.0, float(np.abs(r).max()))
+        allow = (summand_allow + (rows + 4) * 2.0 ** -24 * t) / scale
+        d = np.abs(g - r) / scale
+        d = np.where(np.isnan(d), np.inf, d)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            ratio = np.where(d == 0, 0.0, d / allow)                       # (no allowance at all -- a sum over no rows -- takes exact zeros)
+        i = int(np.argmax(ratio))
+        worst = float(ratio.reshape(-1)[i])
+        self.rworst = max(self.rworst, worst)
+        if not worst <= 1.0:
+            self.failures.append(f"{self.case} {name}: error {d.reshape(-1)[i]:.3e} > reduction allowance {allow.reshape(-1)[i]:.3e} "
+                                 f"over {rows} rows at {_where(r.shape, i)}")
+
+    def report(self, sweep="dense sweep"):
+        print(f"\n{sweep} {self.case}: worst errgpu / allowance {self.worst:.3f}, worst reduction error / allowance {self.rworst:.3f}")
+
+
+def _leaf(t, dt):
+    """A fresh leaf of dtype ``dt`` (never the tensor itself: .to() returns its argument when the dtype already matches)."""
+    return t.detach().to(dt).clone().requires_grad_(True)
+
+
+def _at_offset(t, off):
+    """A contiguous copy of ``t`` at storage offset ``off`` floats of a larger buffer."""
+    buf = torch.empty(t.numel() + off, device="cuda")
+    v = buf[off:].view(t.shape)
+    v.copy_(t)
+    assert v.is_contiguous() and v.data_ptr() % 16 == (4 * off) % 16
+    return v
+
+
+def _guarded(shape, offset):
+    """A NaN-filled (shape) view at storage offset ``offset`` floats with one sentinel float in front of it and one behind."""
+    n = int(np.prod(shape))
+    buf = torch.full((offset + n + 1,), NAN, device="cuda")
+    buf[offset - 1] = SENTINEL
+    buf[offset + n] = SENTINEL
+    v = buf[offset:offset + n].view(shape)
+    assert v.data_ptr() % 64 == (4 * offset) % 64
+    return buf, v
+
+
+def _guards_intact(buf, offset):
+    return float(buf[offset - 1]) == SENTINEL and float(buf[-1]) == SENTINEL

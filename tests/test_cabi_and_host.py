@@ -307,3 +307,40 @@ def test_dense_entry_points_validate_their_arguments_before_any_hip_call(lib):
     assert lib.hypad_mobius_linear_bwd(p, p, p, p, p, p, p, p, p, ctypes.c_size_t(need - 4), n64(4), 3, 2, None) == EWORKSPACE
     assert lib.hypad_mobius_linear_bwd(p, p, p, p, p, p, p, p, p, ctypes.c_size_t(1 << 20), n64(4), 3, 257, None) == EUNSUPPORTED
     assert lib.hypad_mobius_head_bwd(p, p, p, p, None, n64(4), 257, None) == EUNSUPPORTED
+
+
+def test_lstm_seq_and_optimizer_entry_points_validate_their_arguments_before_any_hip_call(lib):
+    """No GPU needed.  The general-T LSTM layer accepts the empty batch like every other layer entry point: rows == 0 returns HYPAD_OK
+    from the two forwards with NULL row buffers and a NULL zero-byte workspace (nothing to write, no HIP call); the backward's zeroing
+    of the parameter gradients is a HIP call and is checked on the GPU (tests/test_gpu_lstm_seq.py).  seq_len <= 0, rows < 0, a NULL
+    parameter and hidden > 64 are refused before that.  The stand-alone optimizer steps refuse a ball wider than 256, a ball that does
+    not fit, step < 1 and NULL buffers, and accept n == 0."""
+    buf = (ctypes.c_float * 4096)()
+    p, n64, sz, f = ctypes.cast(buf, ctypes.c_void_p), ctypes.c_int64, ctypes.c_size_t, ctypes.c_float
+    OK, EINVAL, EWORKSPACE, EUNSUPPORTED = 0, -1, -2, -3
+    lib.hypad_lstm_seq_workspace_bytes.restype = lib.hypad_lstm_seq_bwd_workspace_bytes.restype = ctypes.c_size_t
+    assert lib.hypad_lstm_seq_workspace_bytes(3, n64(0), 20) == 0 and lib.hypad_lstm_seq_bwd_workspace_bytes(3, n64(0), 12, 20) == 0
+    w8 = [p] * 8
+    fwd = lambda rows, T=3, ws=None, params=w8, H=20: lib.hypad_lstm_bidir_seq_fwd(None, *params, None, None, None, None, None, T, n64(rows), 12, H,
+                                                                                 ws, sz(0), None)
+    trn = lambda rows, T=3, ws=None, params=w8, H=20: lib.hypad_lstm_bidir_seq_fwd_train(None, *params, None, None, None, None, None, None, T,
+                                                                                       n64(rows), 12, H, ws, sz(0), None)
+    for call in (fwd, trn):
+        assert call(0) == OK
+        assert call(0, T=0) == EINVAL and call(0, T=-1) == EINVAL and call(-1) == EINVAL
+        assert call(0, params=[p] * 3 + [None] + [p] * 4) == EINVAL
+        assert call(0, H=65) == EUNSUPPORTED
+        assert call(4) == EINVAL                                           # rows without x / out
+    # (x, w_ih_f, w_hh_f, w_ih_r, w_hh_r, h0, c0, out, saved, grad_out, grad_hn, grad_cn, grad_x, six parameter gradients, grad_h0, grad_c0, ...)
+    bwd = lambda rows, T=3, H=20, gw=p, ws=None, nws=0, rowbuf=None: lib.hypad_lstm_bidir_seq_bwd(
+        rowbuf, p, p, p, p, None, None, rowbuf, rowbuf, rowbuf, None, None, rowbuf, p, gw, p, p, p, p, None, None, T, n64(rows), 12, H, ws, sz(nws), None)
+    assert bwd(0, T=0) == EINVAL and bwd(-1) == EINVAL and bwd(0, gw=None) == EINVAL and bwd(0, H=65) == EUNSUPPORTED
+    assert bwd(4) == EINVAL                                                # rows without the row buffers
+    assert bwd(4, rowbuf=p) == EWORKSPACE and bwd(4, rowbuf=p, ws=p, nws=64) == EWORKSPACE
+    # (p, g, m, v, n, step, lr, b1, b2, eps, wd, stream) / (p, g, m, v, n, ball_off, ball_dim, step, lr, b1, b2, eps, wd, stabilize, stream)
+    hp = (f(0.05), f(0.9), f(0.999), f(1e-8), f(0.0))
+    adam = lambda a=p, n=8, step=1: lib.hypad_adam_step(a, p, p, p, n64(n), step, *hp, None)
+    radam = lambda a=p, n=300, off=0, dim=0, step=1: lib.hypad_radam_step(p, a, p, p, n64(n), n64(off), dim, step, *hp, 10, None)
+    assert adam(n=0) == OK and adam(step=0) == EINVAL and adam(a=None) == EINVAL and adam(n=-1) == EINVAL
+    assert radam(n=0) == OK and radam(step=0) == EINVAL and radam(a=None) == EINVAL
+    assert radam(dim=257, n=300) == EINVAL and radam(off=45, dim=256) == EINVAL and radam(off=-1, dim=4) == EINVAL

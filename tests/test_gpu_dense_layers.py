@@ -24,75 +24,22 @@ Checker rule allows the summed operand itself (``sweep_common.grad_allowance`` o
 and fp32 references) times the largest |b| it is multiplied with; it is zero where the summands are the call's own inputs.  At 39
 rows a dropped or doubled row is three orders of magnitude beyond this.
 """
-import re
-
-import numpy as np
 import pytest
 import torch
 
 import sweep_common as sc
-from sweep_common import _ball_rows, _unaligned
+from sweep_common import NAN, SENTINEL, Ck, _at_offset, _ball_rows, _guarded, _guards_intact, _leaf, _unaligned
 from oracle import gmath as og
 
 pytestmark = pytest.mark.gpu
 
 F64, F32 = torch.float64, torch.float32
 HYPAD_EINVAL, HYPAD_EWORKSPACE, HYPAD_EUNSUPPORTED = -1, -2, -3          # include/hypad.h
-SENTINEL = 12345.0
-NAN = float("nan")
 
 
 def _C():
     from hypad_amd import _C as c
     return c
-
-
-class Ck(sc.Checker):
-    """The Checker plus the reduction rule; for the weights-stationary LSTM layer (``tiles=(rows, waves)``) a failure also names the
-    16-row tile of its worst row and which iteration of its wave's walk that tile is."""
-
-    def __init__(self, case="", tiles=None):
-        super().__init__(case)
-        self.rworst = 0.0
-        self.tstep = None
-        if tiles:
-            rows, nw = tiles
-            ntiles = (rows + 15) // 16
-            self.nw, self.tstep = nw, min(128, -(-ntiles // nw)) * nw      # hypad_lstm_bidir_fwd: at most 128 slices of `nw` waves per direction
-
-    def _tile_note(self, first):
-        for i in range(first, len(self.failures)):
-            m = re.search(r"\(row (\d+),", self.failures[i])
-            if m and self.tstep:
-                tile = int(m.group(1)) // 16
-                self.failures[i] += (f" [tile {tile}: iteration {tile // self.tstep} (from 0) of wave {tile % self.tstep % self.nw} in slice "
-                                     f"{tile % self.tstep // self.nw}, tiles {self.tstep} apart]")
-
-    def cmp(self, name, got, ref64, ref32, mask=None):
-        n = len(self.failures)
-        super().cmp(name, got, ref64, ref32, mask)
-        self._tile_note(n)
-
-    def red(self, name, got, ref64, abs_terms, rows, summand_allow=0.0):
-        g, r, t = sc._f64(got), sc._f64(ref64), sc._f64(abs_terms)
-        assert g.shape == r.shape == t.shape, (name, g.shape, r.shape, t.shape)
-        if r.size == 0:
-            return
-        scale = max(1.0, float(np.abs(r).max()))
-        allow = (summand_allow + (rows + 4) * 2.0 ** -24 * t) / scale
-        d = np.abs(g - r) / scale
-        d = np.where(np.isnan(d), np.inf, d)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            ratio = np.where(d == 0, 0.0, d / allow)                       # (no allowance at all -- a sum over no rows -- takes exact zeros)
-        i = int(np.argmax(ratio))
-        worst = float(ratio.reshape(-1)[i])
-        self.rworst = max(self.rworst, worst)
-        if not worst <= 1.0:
-            self.failures.append(f"{self.case} {name}: error {d.reshape(-1)[i]:.3e} > reduction allowance {allow.reshape(-1)[i]:.3e} "
-                                 f"over {rows} rows at {sc._where(r.shape, i)}")
-
-    def report(self):
-        print(f"\ndense sweep {self.case}: worst errgpu / allowance {self.worst:.3f}, worst reduction error / allowance {self.rworst:.3f}")
 
 
 def _finish(cks):
@@ -102,37 +49,8 @@ def _finish(cks):
     assert not failures, "\n".join(failures)
 
 
-def _leaf(t, dt):
-    """A fresh leaf of dtype ``dt`` (never the tensor itself: .to() returns its argument when the dtype already matches)."""
-    return t.detach().to(dt).clone().requires_grad_(True)
-
-
 def _nan(*shape):
     return torch.full(shape, NAN, device="cuda")
-
-
-def _at_offset(t, off):
-    """A contiguous copy of ``t`` at storage offset ``off`` floats of a larger buffer."""
-    buf = torch.empty(t.numel() + off, device="cuda")
-    v = buf[off:].view(t.shape)
-    v.copy_(t)
-    assert v.is_contiguous() and v.data_ptr() % 16 == (4 * off) % 16
-    return v
-
-
-def _guarded(shape, offset):
-    """A NaN-filled (shape) view at storage offset ``offset`` floats with one sentinel float in front of it and one behind."""
-    n = int(np.prod(shape))
-    buf = torch.full((offset + n + 1,), NAN, device="cuda")
-    buf[offset - 1] = SENTINEL
-    buf[offset + n] = SENTINEL
-    v = buf[offset:offset + n].view(shape)
-    assert v.data_ptr() % 64 == (4 * offset) % 64
-    return buf, v
-
-
-def _guards_intact(buf, offset):
-    return float(buf[offset - 1]) == SENTINEL and float(buf[-1]) == SENTINEL
 
 
 # ================================================================================================ A. weights-stationary LSTM layer
