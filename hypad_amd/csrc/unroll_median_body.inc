@@ -97,6 +97,21 @@
       float mine[EPL];
 #pragma unroll
       for (int e = 0; e < EPL; ++e) { const int i = lane + 64 * e; mine[e] = i < cnt ? v[i] : INF; }
+      // A NaN on the anti-diagonal: np.median, np.percentile, np.min and np.max of it are NaN.  It compares false with everything, so
+      // the counts below would give it rank 0 beside the minimum and leave the top slot of `s` unwritten -- a finite median of the
+      // other values and a stale maximum.  One ballot per timestep; the wave writes the NaNs and skips the ranking.
+      bool isnan_mine = false;                               // (an unordered compare takes two slots at once: one instruction at EPL 1 and 2)
+#pragma unroll
+      for (int e = 0; e < EPL; e += 2) isnan_mine |= __builtin_isunordered(mine[e], mine[e + 1 < EPL ? e + 1 : e]);
+      if (__ballot(isnan_mine)) {                            // wave-uniform
+        if (lane == 0) {
+          const float QNAN = __int_as_float(0x7fc00000);
+          median[t] = QNAN;
+          if (summary)
+            for (int q = 0; q < 5; ++q) summary[t * 5 + q] = (double)QNAN;
+        }
+        continue;
+      }
       const int m1 = (cnt - 1) >> 1, m2 = cnt >> 1;
       float lo_med = 0.f, hi_med = 0.f;
       bool done = false;
@@ -192,7 +207,9 @@
         lo_med = s[m1]; hi_med = s[m2];
       }
       if (lane == 0) {
-        median[t] = (cnt & 1) ? lo_med : (lo_med + hi_med) * 0.5f;     // np.median of float32 stays float32
+        // np.median of float32 stays float32.  It is numpy's MEAN of the middle value(s), a sum that starts from +0.0: a median that
+        // is a zero is +0.0 there even when the middle values are -0.0 -- hence the + 0.f, which changes nothing else
+        median[t] = ((cnt & 1) ? lo_med : (lo_med + hi_med) * 0.5f) + 0.f;
         if (summary) {
           double* o = summary + t * 5;
           o[0] = (double)s[0];

@@ -344,3 +344,19 @@ def test_lstm_seq_and_optimizer_entry_points_validate_their_arguments_before_any
     assert adam(n=0) == OK and adam(step=0) == EINVAL and adam(a=None) == EINVAL and adam(n=-1) == EINVAL
     assert radam(n=0) == OK and radam(step=0) == EINVAL and radam(a=None) == EINVAL
     assert radam(dim=257, n=300) == EINVAL and radam(off=45, dim=256) == EINVAL and radam(off=-1, dim=4) == EINVAL
+
+
+def test_error_kernels_refuse_score_windows_without_an_instantiation_before_any_launch(lib):
+    """No GPU needed (fake pointers): hypad_dtw_error has the window lengths 3, 5, 7, 9, 11 and 21 -- score windows 12 and 22 (lengths
+    13 and 23) are HYPAD_EUNSUPPORTED, score window 1 is HYPAD_EINVAL for it and for hypad_area_error; an empty series is HYPAD_OK.  All of
+    them return before the first HIP call (on a machine without a device anything later returns a HIP error code instead)."""
+    buf = (ctypes.c_double * 64)()
+    p, n64 = ctypes.cast(buf, ctypes.c_void_p), ctypes.c_int64
+    OK, EINVAL, EUNSUPPORTED = 0, -1, -3
+    for sw in (12, 13, 22, 23, 14, 40):
+        assert lib.hypad_dtw_error(p, p, p, n64(40), sw, None) == EUNSUPPORTED, sw
+    for sw in (1, 0, -3):
+        assert lib.hypad_dtw_error(p, p, p, n64(40), sw, None) == EINVAL, sw
+        assert lib.hypad_area_error(p, p, p, n64(40), sw, None) == EINVAL, sw
+    assert lib.hypad_dtw_error(p, p, p, n64(-1), 10, None) == EINVAL and lib.hypad_area_error(p, p, None, n64(4), 10, None) == EINVAL
+    assert lib.hypad_dtw_error(p, p, p, n64(0), 10, None) == OK and lib.hypad_area_error(p, p, p, n64(0), 10, None) == OK
