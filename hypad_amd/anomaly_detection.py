@@ -1,5 +1,7 @@
 """Test-time driver (reference: anomaly_detection.py:20-155): eval-mode batch loop fused into one kernel per
 batch -- encoder -> decoder -> hyperbolic_linear(sample) -> critic_x(sample) [-> row-wise Poincare distance]."""
+import os
+
 import numpy as np
 import torch
 
@@ -105,7 +107,6 @@ def test_tadgan(test_loader, encoder, decoder, critic_x, read_path="", signal=""
     """anomaly_detection.py:20-155 up to the hand-off to the scoring utilities.  Writes the same cache files
     (recons_signal.pt, gt_signal.pt, critic_score.pt [, eucl_recons.pt, real_hyper.pt]) and returns
     (recons_signal, true_signal, critic_score) as the reference passes them on."""
-    path = path + "/" if path else ""
     res = score_batches(test_loader, encoder, decoder, critic_x, signal_shape)
     # results back through page-locked buffers, all copies queued before the one wait (a pageable .cpu() of an (N, S) array is
     # staged by the driver in pieces: 4-5 ms per array at 125 000 windows); the arrays returned are views of those buffers
@@ -120,17 +121,21 @@ def test_tadgan(test_loader, encoder, decoder, critic_x, read_path="", signal=""
     recons_signal = host["recons"]
     gt_signal = host["true"] if "true" in host else (res["true"].numpy() if isinstance(res["true"], torch.Tensor) else np.concatenate(res["true"]))
     critic_score = list(host["critic"])
-    true_signal = gt_signal
+    true_signal = host["hyper_real"] if decoder.hyperbolic else gt_signal
     if path:
-        torch.save(recons_signal, path + "recons_signal.pt")
-        torch.save(gt_signal, path + "gt_signal.pt")
-        torch.save(critic_score, path + "critic_score.pt")
-    if decoder.hyperbolic:
-        true_signal = host["hyper_real"]
-        if path:
-            torch.save(host["eucl"], path + "eucl_recons.pt")
-            torch.save(true_signal, path + "real_hyper.pt")
+        save_test_outputs(path, recons_signal, gt_signal, critic_score, host.get("eucl"), host.get("hyper_real"))
     return recons_signal, true_signal, critic_score
+
+
+def save_test_outputs(path, recons, gt, critic, eucl=None, hyper_real=None):
+    """The test loop's cache files under the model directory ``path`` (anomaly_detection.py:114-126): the reconstructions and the ground
+    truth as arrays, the window-critic values as a Python list, and for a hyperbolic model (``hyper_real`` given) the Euclidean
+    reconstructions and the real windows on the ball."""
+    files = {"recons_signal.pt": recons, "gt_signal.pt": gt, "critic_score.pt": list(critic)}
+    if hyper_real is not None:
+        files.update({"eucl_recons.pt": eucl, "real_hyper.pt": hyper_real})
+    for name, obj in files.items():
+        torch.save(obj, os.path.join(path, name))
 
 
 def _to_host(tensors):

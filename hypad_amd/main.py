@@ -10,68 +10,79 @@ call instead (three iteration functions per minibatch); ``--resident`` draws all
 test-loop forward, device scoring kernels, host interval extraction and overlap-segment metrics.  Prints the metrics and
 returns them from ``run``."""
 import argparse
+from collections import namedtuple
 from types import SimpleNamespace
 
 import numpy as np
+
+LATENT_DIM = 20                       # the latent dimension of every model (the reference's train.py:413 sets it, whatever the config says)
+Signal = namedtuple("Signal", "params train test read_path name")       # one signal of a run: its params, datasets, CSV path and name
 
 
 def run(params, config_path=None, data_dir="./data", drop_in=True, log=print, resident=False, per_iteration=False):
     """``drop_in`` (default True) = the reference's call chain over a DataLoader; ``drop_in=False`` or ``resident=True`` = the resident path."""
     resident = resident or not drop_in
-    import pandas as pd
     from torch.utils.data import DataLoader
 
-    from . import anomaly_detection
     from . import train as ht
-    from .utils import anomaly_detection_utils as adu
     from .utils import data as od
 
     log("dataset: {}, signal: {}".format(params.dataset, params.signal))
     train_dataset, test_dataset, read_path = od.dataset_selection(params, data_dir)
-    multivariate = hasattr(train_dataset, "device_windows")            # utils/dataloader_multivariate.py datasets
     if not resident:
         if per_iteration:
             params.per_iteration = True
         train_loader = DataLoader(train_dataset, batch_size=params.batch_size, drop_last=True, shuffle=True, num_workers=0)
         encoder, decoder, critic_x, _, path = ht.train(train_loader, params, config_path)
-    else:
-        resident = train_dataset.device_windows("cpu") if multivariate else train_dataset
+    else:                                                              # (utils/dataloader_multivariate.py datasets train on their window matrix)
+        resident = train_dataset.device_windows("cpu") if hasattr(train_dataset, "device_windows") else train_dataset
         encoder, decoder, critic_x, _, path, _ = ht.train_resident(resident, params, config_path, log=log)
+    multivariate = _multivariate(Signal(params, train_dataset, test_dataset, read_path, params.signal))
     return _detect(params, test_dataset, read_path, encoder, decoder, critic_x, path, data_dir, multivariate, log)
 
 
 def _detect(params, test_dataset, read_path, encoder, decoder, critic_x, path, data_dir, multivariate, log):
     """main.py:57-70 / anomaly_detection.py:20-155: the test loop and the detector for one trained model."""
-    import pandas as pd
     from torch.utils.data import DataLoader
 
     from . import anomaly_detection
     from .utils import anomaly_detection_utils as adu
-    from .utils import data as od
     test_loader = DataLoader(test_dataset, batch_size=params.batch_size, drop_last=False, shuffle=False, num_workers=0)
     recons_signal, true_signal, critic_score = anomaly_detection.test_tadgan(
         test_loader, encoder, decoder, critic_x, read_path=read_path, signal=params.signal, path=path, signal_shape=params.signal_shape,
         params=params)
-    if params.signal == "multivariate" or multivariate:                 # anomaly_detection.py:137-140
-        # the reference torch.load()s the labels from its data tree (utils/anomaly_detection_utils.py:143-151); the test
-        # dataset already holds that tensor
-        y = test_dataset.y if len(getattr(test_dataset, "y", [])) else None
-        out = adu.multivariate_anomaly_detection(recons_signal, true_signal, params, params.combination, critic_score, path, y=y)
-        log("predicted intervals:\n{}".format(out["intervals"]))
-        if out.get("metrics"):
-            log("precision: {precision}, recall: {recall}\nf1_score: {f1}, gmean: {gmean}".format(**out["metrics"]))
-        return out
-    if params.dataset in ("A1", "A2", "A3", "A4"):                       # anomaly_detection.py:32-37
-        known = pd.read_csv(read_path[:-4] + "_known_anomalies.csv")
+    if multivariate:                                                   # anomaly_detection.py:137-140
+        out = adu.multivariate_anomaly_detection(recons_signal, true_signal, params, params.combination, critic_score, path, y=_labels(test_dataset))
     else:
-        known = od.load_anomalies(params.signal, data_dir=data_dir)
-    out = adu.univariate_anomaly_detection(recons_signal, true_signal, params, params.combination, critic_score, path, read_path,
-                                           params.rec_error, _true_index(test_dataset, params), known, params.signal, params.signal_shape)
-    log("predicted intervals:\n{}".format(out["intervals"]))
-    log("tn, fp, fn, tp: {}".format(out["confusion"]))
-    if out["metrics"]:
-        log("precision: {precision}, recall: {recall}\nf1_score: {f1}, gmean: {gmean}".format(**out["metrics"]))
+        out = adu.univariate_anomaly_detection(recons_signal, true_signal, params, params.combination, critic_score, path, read_path,
+                                               params.rec_error, _true_index(test_dataset, params), _known_anomalies(params, read_path, data_dir),
+                                               params.signal, params.signal_shape)
+    _log_result(out, log)
     return out
+
+
+def _labels(test_dataset):
+    """The reference torch.load()s the multivariate labels from its data tree (utils/anomaly_detection_utils.py:143-151); the test
+    dataset already holds that tensor."""
+    return test_dataset.y if len(getattr(test_dataset, "y", [])) else None
+
+
+def _known_anomalies(params, read_path, data_dir):
+    """The labelled intervals of a univariate signal (anomaly_detection.py:32-37)."""
+    if params.dataset in ("A1", "A2", "A3", "A4"):
+        import pandas as pd
+        return pd.read_csv(read_path[:-4] + "_known_anomalies.csv")
+    from .utils import data as od
+    return od.load_anomalies(params.signal, data_dir=data_dir)
+
+
+def _log_result(out, log):
+    """A detector's result dict as the log lines of a run (the multivariate detector counts no confusion matrix)."""
+    log("predicted intervals:\n{}".format(out["intervals"]))
+    if "confusion" in out:
+        log("tn, fp, fn, tp: {}".format(out["confusion"]))
+    if out.get("metrics"):
+        log("precision: {precision}, recall: {recall}\nf1_score: {f1}, gmean: {gmean}".format(**out["metrics"]))
 
 
 def run_signals(params, names, config_path=None, data_dir="./data", log=print, grouped_scoring=True, device_intervals=False):
@@ -92,26 +103,27 @@ def run_signals(params, names, config_path=None, data_dir="./data", log=print, g
     for name in names:
         p = copy.copy(params)
         p.signal = name
-        sets.append((p,) + tuple(od.dataset_selection(p, data_dir)))
-    trained = ht.train_signals_resident([t[1] for t in sets], params, names=names, log=log)
+        sets.append(Signal(p, *od.dataset_selection(p, data_dir), name))
+    trained = ht.train_signals_resident([s.train for s in sets], params, names=names, log=log)
     local = {}
-    group = [(t, name) for t, name in zip(sets, names) if trained[name].get("modules") is not None and _groupable(t, trained[name]["path"])]
+    group = [s for s in sets if trained[s.name].get("modules") is not None and _groupable(s, trained[s.name]["path"])]
     if device_intervals and not grouped_scoring:
         raise ValueError("device_intervals needs grouped scoring")
     outs = {}
     if grouped_scoring:                                # (a group is of one kind: window matrices with the multivariate detector, or series)
         for kind in (True, False):
-            members = [g for g in group if _multivariate(g[0]) == kind]
+            members = [s for s in group if _multivariate(s) == kind]
             if members:
                 outs.update(_detect_grouped(members, trained, data_dir, log, device_intervals=device_intervals))
-    for (p, train_ds, test_ds, read_path), name in zip(sets, names):
+    for s in sets:
+        name = s.name
         mods = trained[name].get("modules")
         if mods is None:
             continue                                   # another rank's signal
-        p.latent_space_dim = 20
+        s.params.latent_space_dim = LATENT_DIM
         out = outs.get(name)
         if out is None:
-            out = _detect(p, test_ds, read_path, mods[0], mods[1], mods[2], trained[name]["path"], data_dir, hasattr(train_ds, "device_windows"), log)
+            out = _detect(s.params, s.test, s.read_path, mods[0], mods[1], mods[2], trained[name]["path"], data_dir, _multivariate(s), log)
         # (tn is None in the overlap-segment count)
         local[name] = {"confusion": [None if v is None else int(v) for v in out.get("confusion", [])] or None, "metrics": out.get("metrics"),
                        "n_intervals": int(len(out["intervals"])), "final": trained[name]["final"], "path": trained[name]["path"],
@@ -119,19 +131,19 @@ def run_signals(params, names, config_path=None, data_dir="./data", log=print, g
     return par.gather_signal_metrics(local)
 
 
-def _multivariate(t):
-    """A signal that takes the multivariate detector (anomaly_detection.py:137-140; _detect's test)."""
-    return hasattr(t[1], "device_windows") or t[0].signal == "multivariate"
+def _multivariate(s):
+    """A signal that takes the multivariate detector (anomaly_detection.py:137-140): the one place that decides it."""
+    return hasattr(s.train, "device_windows") or s.params.signal == "multivariate"
 
 
-def _groupable(t, path):
+def _groupable(s, path):
     """A signal _detect_grouped scores: a multivariate one with test windows (its detector keeps no score cache), or a univariate
     one in the series view without a score cache that the per-signal detector would read back -- critic_scores.pickle under
     ``params.load``; for a Euclidean model any of the four pickles score_anomalies keeps (``path + "dtw.pickle"`` etc., the names it
     reads).  Those take _detect."""
     import os
-    p, train_ds, test_ds, _ = t
-    if _multivariate(t):
+    p, test_ds = s.params, s.test
+    if _multivariate(s):
         return len(test_ds.X) > 0
     if not hasattr(test_ds, "series_windows"):
         return False
@@ -143,137 +155,70 @@ def _groupable(t, path):
 
 
 def _detect_grouped(group, trained, data_dir, log, device_intervals=False):
-    """_detect for several trained signals at once: one score_signals call (pack, critic and forward launches for all of them), for
-    hyperbolic models hyperbolic_scores_signals, everything back in one page-locked copy and one wait; then per signal on the host
-    the cache files test_tadgan writes, critic_scores.pickle, and detect_intervals (anomalies.csv, counts, metrics, results row) --
-    the same contents as _detect's.  Euclidean models: euclidean_scores_signals (the un-roll, the reconstruction scores -- all three
-    kinds when a model directory keeps score_anomalies' pickles -- and the critic chain of all signals, in timestep layout), one
-    copy back, then the pickles and detect_intervals per signal; the reconstruction matrix comes back only for recons_signal.pt.
-    ``device_intervals``: find_anomalies_signals extracts every signal's intervals from the final scores before the copy back, and
-    detect_intervals takes them instead of running find_anomalies.
-    Multivariate signals (window matrices): score_signals on the test sets' ``X``, multivariate_scores_signals, the intervals with the
-    multivariate settings, one copy back; then per signal the test loop's files and multivariate_intervals -- _detect's output dict."""
-    import pickle
-
-    import pandas as pd
-    import torch
-
+    """_detect for several trained signals of one kind at once, with _detect's numbers, files and output dicts: one score_signals call
+    (pack, critic and forward launches for all of them), the final scores of the kind, optionally every signal's intervals from the
+    device (``device_intervals``: find_anomalies_signals; the host tails then skip find_anomalies), everything back in one page-locked
+    copy and one wait; then per signal on the host the cache files test_tadgan writes, the kind's score pickles and the detector's tail.
+    The kinds: multivariate signals (window matrices) -- multivariate_scores_signals on the test sets' ``X``, no pickles,
+    multivariate_intervals; univariate hyperbolic models -- hyperbolic_scores_signals, critic_scores.pickle, detect_intervals (anomalies.csv,
+    counts, metrics, results row); univariate Euclidean models -- euclidean_scores_signals in timestep layout (the un-roll, the
+    reconstruction scores and the critic chain; all three kinds of score when a model directory keeps score_anomalies' pickles),
+    detect_intervals.  The (N, S) matrices and the pickles' vectors come back only when some signal has a model directory."""
     from . import anomaly_detection
     from .utils import anomaly_detection_utils as adu
-    from .utils import data as od
-    P0 = group[0][0][0]
-    hyp = bool(P0.hyperbolic)
-    S, L = int(P0.signal_shape), 20
-    models = [tuple(trained[name]["modules"][:3]) for _, name in group]
-    if _multivariate(group[0][0]):
-        return _detect_grouped_multivariate(group, trained, models, log, device_intervals)
-    res = anomaly_detection.score_signals([t[2] for t, _ in group], models, S, L, hyp)
+    P0 = group[0].params
+    hyp, S = bool(P0.hyperbolic), int(P0.signal_shape)
+    multivariate = _multivariate(group[0])
+    paths = [trained[s.name]["path"] for s in group]       # (the detector's files are named path + file, as _detect names them)
+    keep = any(paths)
+    tests = [s.test for s in group]
+    res = anomaly_detection.score_signals(tests, [tuple(trained[s.name]["modules"][:3]) for s in group], S, LATENT_DIM, hyp)
     row_off = res["row_off"]
-    keep = any(trained[name]["path"] for _, name in group)          # (some directory wants the test loop's files and the score pickles)
-    want = {"recons": res["recons"], "critic": res["critic"]} if hyp or keep else {}
-    if hyp:
-        want.update(hyper_real=res["hyper_real"], eucl=res["eucl"])
-        comb = adu.hyperbolic_scores_signals(res, P0.combination)
-        want["final"] = comb["final_scores"]
-        if comb["critic_scores"] is not None:
-            want["critic_scores"] = comb["critic_scores"]
+    t_off = adu.timestep_offsets(row_off, S)
+    # the kind's scores step: the final scores, the offsets of their segments, the index and the settings of the interval search, and
+    # the vectors (timestep layout) a model directory keeps as <name>.pickle
+    if multivariate:
+        from .utils.dataloader import _yahoo_timestamps
+        comb = adu.multivariate_scores_signals(res, res["x"], P0.combination)
+        seg_off, settings, pickles = row_off, adu.MULTIVARIATE_INTERVALS, {}
+        indices = [_yahoo_timestamps(b - a) for a, b in zip(row_off, row_off[1:])]        # the reference's stand-in index (:133-137)
     else:
-        tests = [t[2] for t, _ in group]
-        comb = adu.euclidean_scores_signals(res, adu.unroll_true_signals(tests, row_off, S), P0.rec_error, P0.combination,
-                                            kinds=("point", "area", "dtw") if keep else None, with_critic=keep or None)
-        t_off = comb["t_off"]
-        want["final"] = comb["final_scores"]
-        if keep:
-            want["critic_scores"] = comb["critic_scores"]
-            want.update({kind: v for kind, v in comb["rec_scores"].items()})
-    found = [None] * len(group)
-    if device_intervals:                                      # (the detector's settings: univariate_anomaly_detection :89-95)
-        found = adu.find_anomalies_signals(comb["final_scores"], row_off if hyp else t_off,
-                                           index_list=[_true_index(t[2], t[0]) for t, _ in group], window_size_portion=0.33,
-                                           window_step_size_portion=0.1)
-    host = anomaly_detection._to_host(want)
-    outs = {}
-    for k, ((p, _, test_ds, read_path), name) in enumerate(group):
-        a, b = row_off[k], row_off[k + 1]
-        raw = trained[name]["path"]                           # (the detector's files are named raw + file, as _detect names them)
-        path = raw + "/" if raw else ""
-        gt_signal = np.asarray(test_ds.X)
-        if path or hyp:
-            recons_signal = host["recons"][a:b]
-            critic_score = list(host["critic"][a:b])
-        true_signal = host["hyper_real"][a:b] if hyp else gt_signal
-        if path:
-            torch.save(recons_signal, path + "recons_signal.pt")
-            torch.save(gt_signal, path + "gt_signal.pt")
-            torch.save(critic_score, path + "critic_score.pt")
-            if hyp:
-                torch.save(host["eucl"][a:b], path + "eucl_recons.pt")
-                torch.save(true_signal, path + "real_hyper.pt")
-        if p.dataset in ("A1", "A2", "A3", "A4"):
-            known = pd.read_csv(read_path[:-4] + "_known_anomalies.csv")
-        else:
-            known = od.load_anomalies(p.signal, data_dir=data_dir)
+        settings = adu.UNIVARIATE_INTERVALS
+        indices = [_true_index(s.test, s.params) for s in group]
         if hyp:
-            if raw and "critic_scores" in host:                # (compute_critic_scores' cache, the signal's whole segment)
-                with open(raw + "critic_scores.pickle", "wb") as f:
-                    pickle.dump(host["critic_scores"][a + k * (S - 1): b + (k + 1) * (S - 1)], f, protocol=pickle.HIGHEST_PROTOCOL)
-            out = adu.detect_intervals(host["final"][a:b], p, raw, _true_index(test_ds, p), known, p.signal, intervals=found[k])
+            comb = adu.hyperbolic_scores_signals(res, P0.combination)
+            seg_off = row_off                                 # (compute_critic_scores' cache holds the signal's whole timestep segment)
+            pickles = {} if comb["critic_scores"] is None else {"critic_scores": comb["critic_scores"]}
         else:
-            ta, tb = t_off[k], t_off[k + 1]
-            if raw:                                            # (score_anomalies' caches: the arrays and the protocol it writes)
-                for f in ("critic_scores", "point", "area", "dtw"):
-                    adu._dump_pickle(host[f][ta:tb].copy(), raw + f + ".pickle")
-            out = adu.detect_intervals(host["final"][ta:tb], p, raw, _true_index(test_ds, p), known, p.signal, intervals=found[k])
-        log("predicted intervals:\n{}".format(out["intervals"]))
-        log("tn, fp, fn, tp: {}".format(out["confusion"]))
-        if out["metrics"]:
-            log("precision: {precision}, recall: {recall}\nf1_score: {f1}, gmean: {gmean}".format(**out["metrics"]))
-        outs[name] = out
-    return outs
-
-
-def _detect_grouped_multivariate(group, trained, models, log, device_intervals):
-    """The multivariate branch of _detect_grouped."""
-    import torch
-
-    from . import anomaly_detection
-    from .utils import anomaly_detection_utils as adu
-    from .utils.dataloader import _yahoo_timestamps
-    P0 = group[0][0][0]
-    hyp = bool(P0.hyperbolic)
-    S = int(P0.signal_shape)
-    res = anomaly_detection.score_signals([t[2] for t, _ in group], models, S, 20, hyp)       # (no series view: the X matrices)
-    row_off = res["row_off"]
-    comb = adu.multivariate_scores_signals(res, res["x"], P0.combination)
-    indices = [_yahoo_timestamps(row_off[k + 1] - row_off[k]) for k in range(len(group))]      # the reference's stand-in index (:133-137)
+            comb = adu.euclidean_scores_signals(res, adu.unroll_true_signals(tests, row_off, S), P0.rec_error, P0.combination,
+                                                kinds=("point", "area", "dtw") if keep else None, with_critic=keep or None)
+            seg_off = t_off
+            pickles = dict(comb["rec_scores"], critic_scores=comb["critic_scores"]) if keep else {}      # (score_anomalies' four caches)
     found = [None] * len(group)
-    if device_intervals:                                      # (the detector's settings: multivariate_anomaly_detection :183-187)
-        found = adu.find_anomalies_signals(comb["final_scores"], row_off, index_list=indices, window_size_portion=0.2,
-                                           window_step_size_portion=0.1, anomaly_padding=200)
+    if device_intervals:
+        found = adu.find_anomalies_signals(comb["final_scores"], seg_off, index_list=indices, **settings)
     want = {"final": comb["final_scores"]}
-    if any(trained[name]["path"] for _, name in group):       # (some directory wants the test loop's files)
-        want.update(recons=res["recons"], critic=res["critic"])
+    if keep:                                                  # (some directory wants the test loop's files and the score pickles)
+        want.update(pickles, recons=res["recons"], critic=res["critic"])
         if hyp:
-            want.update(hyper_real=res["hyper_real"], eucl=res["eucl"])
+            want.update(eucl=res["eucl"], hyper_real=res["hyper_real"])
     host = anomaly_detection._to_host(want)
     outs = {}
-    for k, ((p, _, test_ds, _), name) in enumerate(group):
+    for k, (s, raw) in enumerate(zip(group, paths)):
         a, b = row_off[k], row_off[k + 1]
-        raw = trained[name]["path"]
-        if raw:                                               # test_tadgan's cache files
-            path = raw + "/"
-            torch.save(host["recons"][a:b], path + "recons_signal.pt")
-            torch.save(np.asarray(test_ds.X), path + "gt_signal.pt")
-            torch.save(list(host["critic"][a:b]), path + "critic_score.pt")
-            if hyp:
-                torch.save(host["eucl"][a:b], path + "eucl_recons.pt")
-                torch.save(host["hyper_real"][a:b], path + "real_hyper.pt")
-        y = test_ds.y if len(getattr(test_ds, "y", [])) else None
-        out = adu.multivariate_intervals(host["final"][a:b], indices[k], y, intervals=found[k])
-        log("predicted intervals:\n{}".format(out["intervals"]))
-        if out.get("metrics"):
-            log("precision: {precision}, recall: {recall}\nf1_score: {f1}, gmean: {gmean}".format(**out["metrics"]))
-        outs[name] = out
+        if raw:
+            anomaly_detection.save_test_outputs(raw, host["recons"][a:b], np.asarray(s.test.X), host["critic"][a:b],
+                                                *((host["eucl"][a:b], host["hyper_real"][a:b]) if hyp else ()))
+            for f in pickles:
+                adu._dump_pickle(host[f][t_off[k]: t_off[k + 1]], raw + f + ".pickle")
+        final = host["final"][seg_off[k]: seg_off[k + 1]]
+        if multivariate:
+            out = adu.multivariate_intervals(final, indices[k], _labels(s.test), intervals=found[k])
+        else:
+            out = adu.detect_intervals(final, s.params, raw, indices[k], _known_anomalies(s.params, s.read_path, data_dir), s.params.signal,
+                                       intervals=found[k])
+        _log_result(out, log)
+        outs[s.name] = out
     return outs
 
 

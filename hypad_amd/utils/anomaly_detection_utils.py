@@ -22,6 +22,25 @@ from .intervals import (_find_sequences, _find_threshold, _fixed_threshold, _mer
                         casas_anomalies, compute_metrics, contextual_confusion_matrix, find_anomalies)
 
 
+COMBINATIONS = ("sum", "mult", "uncertainty", "critic", "critic_uncertainty", "sum_uncertainty", "rec", "rec_uncertainty")    # combine_scores (:336-362)
+EUCLIDEAN_MODES = {"mult": "eucl_mult", "sum": "eucl_sum", "rec": "rec", "critic": "critic"}         # score_anomalies' ``comb`` (:553-570) -> _C.COMB
+# find_anomalies' settings of the two detectors (:89-95 and :183-187; fixed_threshold=True in both)
+UNIVARIATE_INTERVALS = dict(window_size_portion=0.33, window_step_size_portion=0.1)
+MULTIVARIATE_INTERVALS = dict(window_size_portion=0.2, window_step_size_portion=0.1, anomaly_padding=200)
+
+
+def uses_critic(combination):
+    """Whether a combination of COMBINATIONS reads the critic scores (:70-73, :166-169)."""
+    return combination not in ("rec", "rec_uncertainty")
+
+
+def _euclidean_mode(comb):
+    mode = EUCLIDEAN_MODES.get(comb)
+    if mode is None:
+        raise ValueError('Unknown combination specified {}, use "mult", "sum", or "rec" instead.'.format(comb))
+    return mode
+
+
 def _dev():
     return torch.device("cuda")
 
@@ -100,12 +119,6 @@ def _scratch(device, nbytes, tag):
 _SIDE_STREAMS = {}
 
 
-def _side_stream_for(main, dev):
-    """A stream whose work really runs beside ``main``'s (hypad_amd/streams.py: streams can share a hardware queue)."""
-    from .. import streams
-    return streams.beside([main], dev)
-
-
 def concurrently(fn_main, fn_side):
     """``fn_main()`` on the current stream and ``fn_side()`` on a side stream BESIDE it: both start behind everything queued so far,
     whatever is queued afterwards starts behind both.  Returns (fn_main(), fn_side()).  What it is for: the critic smoothing of a
@@ -115,8 +128,9 @@ def concurrently(fn_main, fn_side):
     dev = torch.cuda.current_device()
     main = torch.cuda.current_stream()
     side = _SIDE_STREAMS.get((dev, main.cuda_stream))
-    if side is None:
-        side = _SIDE_STREAMS[(dev, main.cuda_stream)] = _side_stream_for(main, dev)
+    if side is None:                                   # (one whose work really runs beside main's: streams can share a hardware queue)
+        from .. import streams
+        side = _SIDE_STREAMS[(dev, main.cuda_stream)] = streams.beside([main], dev)
     side.wait_stream(main)
     with torch.cuda.stream(side):
         b = fn_side()
@@ -207,7 +221,7 @@ def row_diff_norms(a, b):
 def combine_scores(combination, critic_scores=[], rec_scores=[], recons_signal=[], norms=None, as_tensor=False):
     """:336-362.  ``norms``: the row norms of ``recons_signal`` when the caller already has them (sharded scoring);
     ``as_tensor``: leave the result on the device instead of returning NumPy."""
-    if combination not in ("sum", "mult", "uncertainty", "critic", "critic_uncertainty", "sum_uncertainty", "rec", "rec_uncertainty"):
+    if combination not in COMBINATIONS:
         raise ValueError(combination)
     c = _f64(critic_scores) if len(critic_scores) else None
     r = _f64(rec_scores) if len(rec_scores) else None
@@ -224,9 +238,7 @@ def combine_scores(combination, critic_scores=[], rec_scores=[], recons_signal=[
 
 def combine_euclidean(comb, critic_scores, rec_scores, as_tensor=False):
     """Tail of score_anomalies (:553-570), lambda_rec = 0.5."""
-    mode = {"mult": "eucl_mult", "sum": "eucl_sum", "rec": "rec", "critic": "critic"}.get(comb)
-    if mode is None:
-        raise ValueError('Unknown combination specified {}, use "mult", "sum", or "rec" instead.'.format(comb))
+    mode = _euclidean_mode(comb)
     c, r = _f64(critic_scores), _f64(rec_scores)
     out = torch.empty_like(r)
     _C.check(_C.lib.hypad_combine_scores(_C.COMB[mode], _C.ptr(c), _C.ptr(r), None, _C.ptr(out), r.numel(), _C.stream()), "combine")
@@ -353,7 +365,7 @@ def hyperbolic_scores(recons_signal, true_signal, critic_score, signal_shape, co
     ``critic_scores.pickle`` cache of compute_critic_scores)."""
     rec = hyperbolic_rec_scores(recons_signal, true_signal, signal_shape)
     critic_scores = []
-    if combination in ("mult", "uncertainty", "sum", "sum_uncertainty", "critic", "critic_uncertainty"):
+    if uses_critic(combination):
         critic_scores = compute_critic_scores(rec, critic_score, true_signal, params, path)
     return combine_scores(combination, critic_scores, rec, recons_signal)
 
@@ -399,8 +411,7 @@ def detect_intervals(final_scores, params, path=None, true_index=None, known_ano
     if true_index is None:
         true_index = np.arange(final_scores.size)
     if intervals is None:
-        intervals = find_anomalies(final_scores, true_index, window_size_portion=0.33, window_step_size_portion=0.1,
-                                   fixed_threshold=True)
+        intervals = find_anomalies(final_scores, true_index, fixed_threshold=True, **UNIVARIATE_INTERVALS)
     out = dict(final_scores=final_scores, intervals=np.asarray(intervals, dtype=np.float64).reshape(-1, 3), confusion=[0, 0, 0, 0],
                metrics=None)
     if path:
@@ -432,7 +443,7 @@ def multivariate_anomaly_detection(recons_signal, true_signal, params, combinati
     rec = rec if isinstance(rec, torch.Tensor) else torch.as_tensor(np.asarray(rec, dtype=np.float64))
     rec_scores = zscore_clip(rec.to(torch.float64)).cpu().numpy()
     critic_scores = []
-    if combination in ("mult", "uncertainty", "sum", "sum_uncertainty", "critic", "critic_uncertainty"):
+    if uses_critic(combination):
         ts = np.asarray(true_signal)
         critic_scores = final_critic_scores(critic_score, ts.reshape(len(ts), -1))[: rec_scores.shape[0]]
     final_scores = np.asarray(combine_scores(combination, critic_scores, rec_scores, recons_signal), dtype=np.float64).reshape(-1)
@@ -444,8 +455,7 @@ def multivariate_intervals(final_scores, x_index, y=None, intervals=None):
     (window 0.2 T, step 0.1 window, padding 200), CASAS-style ground truth from ``y`` and the overlap-segment metrics.  ``intervals``:
     the signal's (n, 3) rows when they were already extracted (find_anomalies_signals on the device); find_anomalies is skipped then."""
     if intervals is None:
-        intervals = find_anomalies(final_scores, x_index, window_size_portion=0.2, window_step_size_portion=0.1, fixed_threshold=True,
-                                   anomaly_padding=200)
+        intervals = find_anomalies(final_scores, x_index, fixed_threshold=True, **MULTIVARIATE_INTERVALS)
     out = dict(final_scores=final_scores, intervals=np.asarray(intervals, dtype=np.float64).reshape(-1, 3), known_anomalies=None, metrics=None)
     if y is not None:
         known = casas_anomalies(y, np.asarray(x_index))
@@ -481,29 +491,17 @@ def multivariate_scores_signals(res, true, combination="mult"):
     score_signals' ``x``.  Each signal's final_scores are multivariate_anomaly_detection's on it alone, bit for bit (all NaN where
     trunc(n_s * 0.01) is 0 and the critic is used).
     Returns dict(final_scores (sum n_s,), rec_scores (sum n_s,), critic_scores (sum (n_s + S - 1),) or None, row_off); fp64 on the device."""
-    if combination not in ("sum", "mult", "uncertainty", "critic", "critic_uncertainty", "sum_uncertainty", "rec", "rec_uncertainty"):
+    if combination not in COMBINATIONS:
         raise ValueError(combination)
-    row_off = [int(v) for v in res["row_off"]]
-    k = len(row_off) - 1
-    recons = _f32(res["recons"])
-    w = recons.shape[1]
     if res.get("hyper_real") is None:
-        true = _C.require_cuda(true, "true")
+        true, recons = _C.require_cuda(true, "true"), _f32(res["recons"])
         if tuple(true.shape) != tuple(recons.shape):
             raise ValueError(f"true is {tuple(true.shape)}, the reconstructions {tuple(recons.shape)}")
         rec = row_diff_norms(true, recons)
     else:
-        rec = gmath.poincare_rowdist(_f32(res["hyper_real"]), recons)
-        rec = rec if rec.dtype == torch.float64 else rec.to(torch.float64)
-    rec_scores = zscore_clip_signals(rec, row_off)
-    critic_scores = None
-    if combination in ("mult", "uncertainty", "sum", "sum_uncertainty", "critic", "critic_uncertainty"):
-        critic_scores = final_critic_scores_signals(res["critic"], row_off, w)
-    u = row_norms(recons) if "uncertainty" in combination else None
-    out = torch.empty(row_off[-1], device=recons.device, dtype=torch.float64)
-    _C.check(_C.lib.hypad_combine_scores_signals(_C.COMB[combination], _C.ptr(critic_scores), _C.ptr(rec_scores), _C.ptr(u), _C.ptr(out), k,
-                                                 _C.int64s(row_off), w, _C.stream()), "combine_signals")
-    return {"final_scores": out, "rec_scores": rec_scores, "critic_scores": critic_scores, "row_off": row_off}
+        rec = _poincare_rowdist_f64(res)
+    rec_scores = zscore_clip_signals(rec, res["row_off"])
+    return dict(_combine_signals(res, rec_scores, combination), rec_scores=rec_scores)
 
 
 def final_critic_scores_signals(critic, row_off, window, with_modes=False):
@@ -535,24 +533,31 @@ def hyperbolic_scores_signals(res, combination="mult"):
     hyperbolic_scores on it alone, bit for bit, nothing through the host.
     Returns dict(final_scores (sum n_s,) fp64, critic_scores (sum (n_s + S - 1),) fp64 or None -- signal s's final_critic_scores at
     row_off[s] + s (S - 1) --, row_off) on the device."""
-    if combination not in ("sum", "mult", "uncertainty", "critic", "critic_uncertainty", "sum_uncertainty", "rec", "rec_uncertainty"):
+    if combination not in COMBINATIONS:
         raise ValueError(combination)
-    row_off = [int(v) for v in res["row_off"]]
-    k = len(row_off) - 1
-    recons, real = res["recons"], res["hyper_real"]
-    if real is None:
+    if res["hyper_real"] is None:
         raise ValueError("hyperbolic_scores_signals needs a hyperbolic score_signals result")
+    return _combine_signals(res, _poincare_rowdist_f64(res), combination)
+
+
+def _poincare_rowdist_f64(res):
+    """Row-wise Poincare distance between the windows on the ball and the reconstructions of a hyperbolic score_signals result, fp64."""
+    rec = gmath.poincare_rowdist(_f32(res["hyper_real"]), _f32(res["recons"]))
+    return rec if rec.dtype == torch.float64 else rec.to(torch.float64)
+
+
+def _combine_signals(res, rec, combination):
+    """The shared second half of hyperbolic_scores_signals and multivariate_scores_signals: ``rec`` the (sum n_s,) fp64 reconstruction
+    score of every row of the score_signals result ``res``; the critic chain per signal where the combination uses it, the row norms of
+    the reconstructions where it has "uncertainty", then hypad_combine_scores_signals.  Returns dict(final_scores, critic_scores, row_off)."""
+    row_off = [int(v) for v in res["row_off"]]
+    recons = _f32(res["recons"])
     w = recons.shape[1]
-    offs = _C.int64s(row_off)
-    rec = gmath.poincare_rowdist(_f32(real), _f32(recons))
-    rec = rec if rec.dtype == torch.float64 else rec.to(torch.float64)
-    critic_scores = None
-    if combination in ("mult", "uncertainty", "sum", "sum_uncertainty", "critic", "critic_uncertainty"):
-        critic_scores = final_critic_scores_signals(res["critic"], row_off, w)
+    critic_scores = final_critic_scores_signals(res["critic"], row_off, w) if uses_critic(combination) else None
     u = row_norms(recons) if "uncertainty" in combination else None
     out = torch.empty(row_off[-1], device=recons.device, dtype=torch.float64)
-    _C.check(_C.lib.hypad_combine_scores_signals(_C.COMB[combination], _C.ptr(critic_scores), _C.ptr(rec), _C.ptr(u), _C.ptr(out), k, offs, w,
-                                                 _C.stream()), "combine_signals")
+    _C.check(_C.lib.hypad_combine_scores_signals(_C.COMB[combination], _C.ptr(critic_scores), _C.ptr(rec), _C.ptr(u), _C.ptr(out),
+                                                 len(row_off) - 1, _C.int64s(row_off), w, _C.stream()), "combine_signals")
     return {"final_scores": out, "critic_scores": critic_scores, "row_off": row_off}
 
 
@@ -593,9 +598,7 @@ def euclidean_scores_signals(res, true_unrolled, rec_error_type="dtw", comb="mul
     "rec"), then the combination over the whole vector.  Each signal's numbers are score_anomalies' on it alone, bit for bit.
     ``true_unrolled``: unroll_true_signals of the group.
     Returns dict(final_scores, critic_scores (or None), rec_scores {kind: tensor}, row_off, t_off); tensors fp64 on the device."""
-    mode = {"mult": "eucl_mult", "sum": "eucl_sum", "rec": "rec", "critic": "critic"}.get(comb)
-    if mode is None:
-        raise ValueError('Unknown combination specified {}, use "mult", "sum", or "rec" instead.'.format(comb))
+    mode = _euclidean_mode(comb)
     kind = rec_error_type.lower()
     kinds = [kind] if kinds is None else [k.lower() for k in kinds]
     if kind not in kinds:

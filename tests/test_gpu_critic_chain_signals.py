@@ -3,29 +3,16 @@ utils.anomaly_detection_utils.final_critic_scores_signals) against the per-segme
 per segment, hypad_kde_mode_signals + hypad_critic_score_signals, final_critic_scores per signal -- equal fp64 bit patterns, NaNs
 included -- and the reference's own final_critic_scores numbers (fixture score.npz)."""
 import ctypes
+import functools
 
 import numpy as np
 import pytest
 import torch
 
-from helpers import load
+from helpers import load, same_bits
 
 pytestmark = pytest.mark.gpu
-
-
-def _bits(t):
-    t = torch.as_tensor(t).detach().cpu().contiguous()
-    assert t.dtype == torch.float64
-    return t.view(torch.int64)
-
-
-def _same_bits(a, b, what=""):
-    a, b = torch.as_tensor(a).cpu(), torch.as_tensor(b).cpu()
-    assert a.shape == b.shape, (what, a.shape, b.shape)
-    ba, bb = _bits(a), _bits(b)
-    if not torch.equal(ba, bb):
-        bad = torch.nonzero(ba != bb).reshape(-1)
-        raise AssertionError((what, int(bad.numel()), "first at", int(bad[0]), float(a[bad[0]]), float(b[bad[0]])))
+_same_bits = functools.partial(same_bits, dtype=torch.float64)       # (every score compared here is fp64)
 
 
 def _toff(row_off, w):

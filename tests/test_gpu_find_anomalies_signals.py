@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import load
+from helpers import csv_signals, load
 
 pytestmark = pytest.mark.gpu
 
@@ -287,21 +287,6 @@ def test_capacity_overflow_is_reported_and_nothing_is_written_out_of_bounds():
     assert_same(got[1], want[1], "retried")
 
 
-def _csv_signals(d, lengths):
-    t0 = 1_400_000_000
-    rows = []
-    for k, (name, n) in enumerate(lengths):
-        rng = np.random.default_rng(70 + k)
-        tt = np.arange(n)
-        v = np.sin(2 * np.pi * tt / (55.0 + 9 * k)) + 0.05 * rng.standard_normal(n)
-        v[n // 2: n // 2 + 25] += 1.5
-        with open(d / f"{name}.csv", "w") as f:
-            f.write("timestamp,value\n" + "\n".join(f"{t0 + 600 * i},{x:.6f}" for i, x in zip(tt, v)) + "\n")
-        rows.append('%s,"[[%d, %d]]"' % (name, t0 + 600 * (n // 2 - 5), t0 + 600 * (n // 2 + 30)))
-    with open(d / "anomalies.csv", "w") as f:
-        f.write("signal,events\n" + "\n".join(rows) + "\n")
-
-
 def _anomaly_files(root):
     import pandas as pd
     out = {}
@@ -319,7 +304,7 @@ def test_run_signals_device_intervals(tmp_path, monkeypatch, hyperbolic):
     d = tmp_path / "data"
     d.mkdir()
     names = [("sa", 400), ("sb", 300)]
-    _csv_signals(d, names)
+    csv_signals(d, names)
     cfg = dict(dataset="NAB", signal="sa", epochs=1, hyperbolic=hyperbolic, signal_shape=100, lr=5e-4, batch_size=64, save_result=False,
                filename="", rec_error="dtw", combination="mult", interval=600, unique_dataset=True, resume=False, resume_epoch=0, load=False)
     seen = []
@@ -354,7 +339,7 @@ def test_cli_device_intervals_flag(tmp_path, monkeypatch):
     from hypad_amd.utils import anomaly_detection_utils as adu
     d = tmp_path / "data"
     d.mkdir()
-    _csv_signals(d, [("sa", 400), ("sb", 300)])
+    csv_signals(d, [("sa", 400), ("sb", 300)])
     cfg = dict(dataset="NAB", signal="sa", epochs=1, hyperbolic=True, signal_shape=100, lr=5e-4, batch_size=64, save_result=False, filename="",
                rec_error="dtw", combination="mult", interval=600, unique_dataset=True, resume=False, resume_epoch=0, load=False)
     with open(tmp_path / "cfg.yaml", "w") as f:

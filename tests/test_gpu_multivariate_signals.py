@@ -1,27 +1,21 @@
 """Grouped scoring of multivariate signals (hypad_row_diff_norms, hypad_zscore_clip_signals, utils.anomaly_detection_utils.
 multivariate_scores_signals, main.run_signals on window-matrix datasets) against the per-signal path it replaces -- equal bit patterns,
 NaNs equal where both sides have them -- and against the oracle's composition on the fixture score.npz."""
+import functools
 import os
-import pickle
 from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
 
-from helpers import load
+from helpers import artefacts, equal, load, metrics_repr, same_bits, signal_models
 
 pytestmark = pytest.mark.gpu
 
 COMBINATIONS = ["sum", "mult", "uncertainty", "critic", "critic_uncertainty", "sum_uncertainty", "rec", "rec_uncertainty"]
+_same_bits = functools.partial(same_bits, dtype=torch.float64)       # (every score compared here is fp64)
 MV = dict(window_size_portion=0.2, window_step_size_portion=0.1, anomaly_padding=200)      # multivariate_anomaly_detection's settings
-
-
-def _same_bits(a, b, what=""):
-    a, b = (torch.as_tensor(np.asarray(v.cpu() if isinstance(v, torch.Tensor) else v)).contiguous() for v in (a, b))
-    assert a.dtype == b.dtype == torch.float64 and a.shape == b.shape, (what, a.dtype, b.dtype, a.shape, b.shape)
-    same = a.view(torch.int64) == b.view(torch.int64)
-    assert bool(same.all()), (what, int((~same).sum()), a[~same][:4], b[~same][:4])
 
 
 # ---------------------------------------------------------------------------------------------- hypad_row_diff_norms
@@ -112,18 +106,12 @@ COUNTS = [1, 99, 100, 257, 1_300]          # 1 and 99 windows: smoothing window 
 _FORWARD = {}
 
 
-def _models(k, S, L, hyp):
-    from hypad_amd.models import tadgan
-    torch.manual_seed(1000 + k)
-    return tuple(m.cuda().eval() for m in (tadgan.Encoder(S, L), tadgan.Decoder(S, L, hyp), tadgan.CriticX(S, L)))
-
-
 def _forward(S, hyp):
     """One grouped forward of small random models per (S, hyp), shared by the eight combinations and left unchanged."""
     if (S, hyp) not in _FORWARD:
         from hypad_amd.anomaly_detection import score_signals
         g = np.random.default_rng(S + int(hyp))
-        models = [_models(k, S, 20, hyp) for k in range(len(COUNTS))]
+        models = [signal_models(k, S, 20, hyp) for k in range(len(COUNTS))]
         xs = []
         for k, n in enumerate(COUNTS):
             t = np.arange(n)[:, None] * 0.07 + np.arange(S)[None, :] * (0.11 + 0.02 * k)
@@ -236,38 +224,6 @@ def _cfg(hyperbolic):
                 filename="", rec_error="dtw", combination="mult", resume=False, resume_epoch=0, load=False, new_features=False, id=1, split=1)
 
 
-def _artefacts(root):
-    """Every file the runs wrote below ./trained_models except the model weights, loaded."""
-    out = {}
-    for dirpath, _, files in os.walk(root):
-        for f in files:
-            p = os.path.join(dirpath, f)
-            key = os.path.relpath(p, root)
-            if f.endswith(".pt") and f not in ("recons_signal.pt", "gt_signal.pt", "critic_score.pt", "eucl_recons.pt", "real_hyper.pt"):
-                continue
-            if f.endswith(".pt"):
-                out[key] = torch.load(p, weights_only=False)
-            elif f.endswith(".pickle"):
-                with open(p, "rb") as fh:
-                    out[key] = pickle.load(fh)
-            else:
-                with open(p) as fh:
-                    out[key] = fh.read()
-    return out
-
-
-def _equal(a, b):
-    if isinstance(a, np.ndarray):
-        return isinstance(b, np.ndarray) and a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
-    if isinstance(a, list):
-        return isinstance(b, list) and len(a) == len(b) and all(_equal(np.asarray(x), np.asarray(y)) for x, y in zip(a, b))
-    return a == b
-
-
-def _metrics(m):
-    return None if m is None else repr(sorted(m.items()))
-
-
 @pytest.mark.parametrize("hyperbolic", [True, False])
 def test_run_signals_grouped_multivariate_equals_per_signal(tmp_path, monkeypatch, hyperbolic):
     from hypad_amd import main as hmain
@@ -300,21 +256,21 @@ def test_run_signals_grouped_multivariate_equals_per_signal(tmp_path, monkeypatc
         assert g["final_scores"].shape == (n,) and np.isfinite(g["final_scores"]).all(), name
         _same_bits(np.asarray(g["final_scores"]), np.asarray(p["final_scores"]), name)
         _same_bits(np.asarray(v["final_scores"]), np.asarray(p["final_scores"]), name)
-        assert _equal(g["intervals"], p["intervals"]), name
+        assert equal(g["intervals"], p["intervals"]), name
         assert len(p["known_anomalies"]) == 1 and g["known_anomalies"].equals(p["known_anomalies"]) and v["known_anomalies"].equals(p["known_anomalies"])
-        assert _metrics(g["metrics"]) == _metrics(p["metrics"]), name
+        assert metrics_repr(g["metrics"]) == metrics_repr(p["metrics"]), name
         # the device's intervals: equal bounds, scores within the device-interval contract
         assert v["intervals"].shape == p["intervals"].shape and np.array_equal(v["intervals"][:, :2], p["intervals"][:, :2]), name
         np.testing.assert_allclose(v["intervals"][:, 2], p["intervals"][:, 2], rtol=1e-9, atol=0, err_msg=name)
         for key in ("grouped", "device"):
             r, q = runs[key][name], runs["per_signal"][name]
-            assert r["n_intervals"] == q["n_intervals"] and r["confusion"] == q["confusion"] and _metrics(r["metrics"]) == _metrics(q["metrics"])
-    fa, fb = _artefacts(tmp_path / "grouped" / "trained_models"), _artefacts(tmp_path / "per_signal" / "trained_models")
+            assert r["n_intervals"] == q["n_intervals"] and r["confusion"] == q["confusion"] and metrics_repr(r["metrics"]) == metrics_repr(q["metrics"])
+    fa, fb = artefacts(tmp_path / "grouped" / "trained_models"), artefacts(tmp_path / "per_signal" / "trained_models")
     assert sorted(fa) == sorted(fb), (sorted(fa), sorted(fb))
     for f in ("recons_signal.pt", "gt_signal.pt", "critic_score.pt") + (("eucl_recons.pt", "real_hyper.pt") if hyperbolic else ()):
         assert sum(k.endswith(f) for k in fa) == len(NAMES), (f, sorted(fa))
     for k in fa:
-        assert _equal(fa[k], fb[k]), k
+        assert equal(fa[k], fb[k]), k
 
 
 def test_cli_signals_device_intervals_on_a_multivariate_dataset(tmp_path, monkeypatch):

@@ -1,33 +1,15 @@
 """Grouped scoring of many trained signals (anomaly_detection.score_signals, utils.anomaly_detection_utils.hyperbolic_scores_signals,
 main.run_signals(grouped_scoring=True)) against the per-signal path it replaces: equal bit patterns (NaNs equal where both sides have
 them), and the reference's numbers for the grouped forward (fixture fwd_S100_B64.npz, oracle.tadgan)."""
-import os
-import pickle
 from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
 
-from helpers import load, maxdiff, oracle_models, sub_state
+from helpers import artefacts, csv_signals, equal, load, maxdiff, metrics_repr, oracle_models, same_bits, signal_models, sub_state
 
 pytestmark = pytest.mark.gpu
-
-
-def _bits(t):
-    t = torch.as_tensor(t).detach().cpu().contiguous()
-    return t.view(torch.int64) if t.dtype == torch.float64 else t.view(torch.int32)
-
-
-def _same_bits(a, b, what=""):
-    assert a.shape == b.shape, (what, a.shape, b.shape)
-    assert torch.equal(_bits(a), _bits(b)), (what, maxdiff(torch.as_tensor(a).cpu().double().numpy(), torch.as_tensor(b).cpu().double().numpy()))
-
-
-def _models(k, S, L, hyp):
-    from hypad_amd.models import tadgan
-    torch.manual_seed(1000 + k)
-    return tuple(m.cuda().eval() for m in (tadgan.Encoder(S, L), tadgan.Decoder(S, L, hyp), tadgan.CriticX(S, L)))
 
 
 class _Series:
@@ -42,7 +24,7 @@ class _Series:
 def _check_group(counts, S, L, hyp, series_view, seed=0):
     from hypad_amd.anomaly_detection import score_signals, score_windows
     rng = np.random.default_rng(seed)
-    models = [_models(k, S, L, hyp) for k in range(len(counts))]
+    models = [signal_models(k, S, L, hyp) for k in range(len(counts))]
     xs, singles = [], []
     for k, n in enumerate(counts):
         series = np.clip(np.sin(np.arange(n + S - 1) * (0.05 + 0.01 * k)) + 0.1 * rng.standard_normal(n + S - 1), -1, 1).astype(np.float32)
@@ -63,7 +45,7 @@ def _check_group(counts, S, L, hyp, series_view, seed=0):
             if singles[k][key] is None:
                 assert res[key] is None
                 continue
-            _same_bits(res[key][a:b], singles[k][key], (counts, k, key))
+            same_bits(res[key][a:b], singles[k][key], (counts, k, key))
 
 
 @pytest.mark.parametrize("S,L", [(100, 20), (150, 20), (48, 12)])
@@ -89,7 +71,7 @@ def test_engine_arenas_score_as_the_modules():
     from hypad_amd.anomaly_detection import score_signals
     from hypad_amd.engine import Engine
     S, L = 100, 20
-    models = [_models(k, S, L, True) for k in range(3)]
+    models = [signal_models(k, S, L, True) for k in range(3)]
     eng = Engine(S, L, 64, True, n_signals=3)
     for k, (enc, dec, cx) in enumerate(models):
         for net, m in (("enc", enc), ("dec", dec), ("cx", cx)):
@@ -98,7 +80,7 @@ def test_engine_arenas_score_as_the_modules():
     a = score_signals(x, models, S, L, True)
     b = score_signals(x, eng, S, L, True)
     for key in ("recons", "eucl", "hyper_real", "critic", "rowdist"):
-        _same_bits(a[key], b[key], key)
+        same_bits(a[key], b[key], key)
 
 
 def test_grouped_forward_meets_the_reference_numbers():
@@ -155,60 +137,16 @@ def test_grouped_hyperbolic_chain_equals_per_signal(combination):
         a, b = ro[k], ro[k + 1]
         rec, real, crit = res["recons"][a:b].cpu().numpy(), res["hyper_real"][a:b].cpu().numpy(), res["critic"][a:b].cpu().numpy()
         want = adu.hyperbolic_scores(rec, real, list(crit), S, combination)
-        _same_bits(out["final_scores"][a:b], torch.from_numpy(np.asarray(want)), (combination, k))
+        same_bits(out["final_scores"][a:b], torch.from_numpy(np.asarray(want)), (combination, k))
         if out["critic_scores"] is not None:
             fc = adu.final_critic_scores(list(crit), real)
-            _same_bits(out["critic_scores"][a + k * (S - 1): b + (k + 1) * (S - 1)], torch.from_numpy(fc), (combination, k, "critic"))
+            same_bits(out["critic_scores"][a + k * (S - 1): b + (k + 1) * (S - 1)], torch.from_numpy(fc), (combination, k, "critic"))
             if counts[k] < 100:
                 assert bool(torch.isnan(out["critic_scores"][a + k * (S - 1): b + (k + 1) * (S - 1)]).all())
 
 
-def _csv_signals(d, lengths):
-    t0 = 1_400_000_000
-    rows = []
-    for k, (name, n) in enumerate(lengths):
-        rng = np.random.default_rng(70 + k)
-        tt = np.arange(n)
-        v = np.sin(2 * np.pi * tt / (55.0 + 9 * k)) + 0.05 * rng.standard_normal(n)
-        v[n // 2: n // 2 + 25] += 1.5
-        with open(d / f"{name}.csv", "w") as f:
-            f.write("timestamp,value\n" + "\n".join(f"{t0 + 600 * i},{x:.6f}" for i, x in zip(tt, v)) + "\n")
-        rows.append('%s,"[[%d, %d]]"' % (name, t0 + 600 * (n // 2 - 5), t0 + 600 * (n // 2 + 30)))
-    with open(d / "anomalies.csv", "w") as f:
-        f.write("signal,events\n" + "\n".join(rows) + "\n")
-
-
-def _artefacts(root):
-    """Every file the runs wrote below ./trained_models except the model weights, loaded."""
-    out = {}
-    for dirpath, _, files in os.walk(root):
-        for f in files:
-            p = os.path.join(dirpath, f)
-            key = os.path.relpath(p, root)
-            if f.endswith(".pt") and f not in ("recons_signal.pt", "gt_signal.pt", "critic_score.pt", "eucl_recons.pt", "real_hyper.pt"):
-                continue
-            if f.endswith(".pt"):
-                out[key] = torch.load(p, weights_only=False)
-            elif f.endswith(".pickle"):
-                with open(p, "rb") as fh:
-                    out[key] = pickle.load(fh)
-            else:
-                with open(p) as fh:
-                    out[key] = fh.read()
-    return out
-
-
 def _metrics(r):
-    """The metrics dict in a form where NaN equals NaN (f1 of a run without any true positive)."""
-    return None if r["metrics"] is None else repr(sorted(r["metrics"].items()))
-
-
-def _equal(a, b):
-    if isinstance(a, np.ndarray):
-        return isinstance(b, np.ndarray) and a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
-    if isinstance(a, list):
-        return isinstance(b, list) and len(a) == len(b) and all(_equal(np.asarray(x), np.asarray(y)) for x, y in zip(a, b))
-    return a == b
+    return metrics_repr(r["metrics"])
 
 
 @pytest.mark.parametrize("hyperbolic", [True, False])
@@ -218,7 +156,7 @@ def test_run_signals_grouped_equals_per_signal(tmp_path, monkeypatch, hyperbolic
     d = tmp_path / "data"
     d.mkdir()
     names = [("sa", 700), ("sb", 520), ("sc", 180)]          # 180 - 100 windows: a smoothing window of 0 (NaN critic scores)
-    _csv_signals(d, names)
+    csv_signals(d, names)
     cfg = dict(dataset="NAB", signal="sa", epochs=1, hyperbolic=hyperbolic, signal_shape=100, lr=5e-4, batch_size=64, save_result=False,
                filename="", rec_error="dtw", combination="mult", interval=600, unique_dataset=True, resume=False, resume_epoch=0, load=False)
     seen = {}
@@ -241,12 +179,12 @@ def test_run_signals_grouped_equals_per_signal(tmp_path, monkeypatch, hyperbolic
     for name, _ in names:
         ga, pa = runs["grouped"][name], runs["per_signal"][name]
         assert ga["confusion"] == pa["confusion"] and _metrics(ga) == _metrics(pa) and ga["n_intervals"] == pa["n_intervals"]
-    fa, fb = _artefacts(tmp_path / "grouped" / "trained_models"), _artefacts(tmp_path / "per_signal" / "trained_models")
+    fa, fb = artefacts(tmp_path / "grouped" / "trained_models"), artefacts(tmp_path / "per_signal" / "trained_models")
     assert sorted(fa) == sorted(fb) and any(k.endswith("anomalies.csv") for k in fa) and any(k.endswith("recons_signal.pt") for k in fa)
     if hyperbolic:
         assert any(k.endswith("critic_scores.pickle") for k in fa)
     for k in fa:
-        assert _equal(fa[k], fb[k]), k
+        assert equal(fa[k], fb[k]), k
 
 
 def test_cli_per_signal_scoring_flag(tmp_path, monkeypatch):
@@ -254,7 +192,7 @@ def test_cli_per_signal_scoring_flag(tmp_path, monkeypatch):
     from hypad_amd import main as hmain
     d = tmp_path / "data"
     d.mkdir()
-    _csv_signals(d, [("sa", 400), ("sb", 300)])
+    csv_signals(d, [("sa", 400), ("sb", 300)])
     cfg = dict(dataset="NAB", signal="sa", epochs=1, hyperbolic=True, signal_shape=100, lr=5e-4, batch_size=64, save_result=False, filename="",
                rec_error="dtw", combination="mult", interval=600, unique_dataset=True, resume=False, resume_epoch=0, load=False)
     with open(tmp_path / "cfg.yaml", "w") as f:

@@ -11,24 +11,12 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import load, maxdiff
+from helpers import artefacts, csv_signals, equal, load, maxdiff, same_bits
 
 pytestmark = pytest.mark.gpu
 
 KINDS = ("point", "area", "dtw")
 SENT32, SENT64 = -12345.5, -98765.25
-
-
-def _bits(t):
-    t = torch.as_tensor(t).detach().cpu().contiguous()
-    return t.view(torch.int64) if t.dtype == torch.float64 else t.view(torch.int32)
-
-
-def _same_bits(a, b, what=""):
-    a, b = torch.as_tensor(a).detach().cpu(), torch.as_tensor(b).detach().cpu()
-    assert a.shape == b.shape and a.dtype == b.dtype, (what, a.shape, b.shape, a.dtype, b.dtype)
-    assert torch.equal(torch.isnan(a), torch.isnan(b)), (what, "NaN positions differ", int(torch.isnan(a).sum()), int(torch.isnan(b).sum()))
-    assert torch.equal(_bits(a), _bits(b)), (what, maxdiff(a.double().numpy(), b.double().numpy()))
 
 
 def _offsets(counts):
@@ -59,8 +47,8 @@ def _check_unroll(counts, S, seed, decimals=False):
     for k in range(len(counts)):
         part = y_hat[row_off[k]: row_off[k + 1]]
         got = med[t_off[k]: t_off[k + 1]]
-        _same_bits(got, adu.unroll_predictions(part, with_summary=True)[0], (S, k, counts[k], "with summary"))
-        _same_bits(got, adu.unroll_predictions(part, with_summary=False)[0], (S, k, counts[k], "median only"))
+        same_bits(got, adu.unroll_predictions(part, with_summary=True)[0], (S, k, counts[k], "with summary"))
+        same_bits(got, adu.unroll_predictions(part, with_summary=False)[0], (S, k, counts[k], "median only"))
 
 
 @pytest.mark.parametrize("S", [48, 100, 150, 256])
@@ -124,17 +112,17 @@ def test_segmented_reconstruction_scores_equal_single_signal():
     median, t_off = _unroll_signals(y_hat, row_off, S)
     assert true.numel() == t_off[-1]
     for k in range(len(counts)):
-        _same_bits(true[t_off[k]: t_off[k + 1]], adu.unroll_true(ys[k]), (k, "true"))
+        same_bits(true[t_off[k]: t_off[k + 1]], adu.unroll_true(ys[k]), (k, "true"))
     outs = _rec_scores_signals(true, median.contiguous(), row_off, S)
     only_dtw = _rec_scores_signals(true, median.contiguous(), row_off, S, kinds=("dtw",))
-    _same_bits(only_dtw["dtw"], outs["dtw"], "dtw alone")
+    same_bits(only_dtw["dtw"], outs["dtw"], "dtw alone")
     for k, n in enumerate(counts):
         w = math.trunc(n * 0.01)
         for kind in KINDS:
             err = adu.reconstruction_errors(ys[k], yhs[k], 1, 10, w, True, kind, with_summary=False)[0]
             want = adu.zscore_clip(err)
             got = outs[kind][t_off[k]: t_off[k + 1]]
-            _same_bits(got, want, (k, n, kind))
+            same_bits(got, want, (k, n, kind))
             if n < 100 or k == 7:
                 assert bool(torch.isnan(got).all()), (k, kind)
             else:
@@ -156,7 +144,7 @@ def test_other_dtw_lengths_and_windows():
         for k, n in enumerate(counts):
             for kind in KINDS:
                 err = adu.reconstruction_errors(ys[k], yhs[k], 1, sw, math.trunc(n * 0.01), True, kind, with_summary=False)[0]
-                _same_bits(outs[kind][t_off[k]: t_off[k + 1]], adu.zscore_clip(err), (S, sw, k, kind))
+                same_bits(outs[kind][t_off[k]: t_off[k + 1]], adu.zscore_clip(err), (S, sw, k, kind))
 
 
 def _group(counts, S, seed, dtype=np.float64):
@@ -191,13 +179,13 @@ def test_grouped_euclidean_scores_equal_score_anomalies(kind, comb):
     for k in range(len(counts)):
         a, b, ta, tb = ro[k], ro[k + 1], out["t_off"][k], out["t_off"][k + 1]
         want = adu.score_anomalies(xs[k], res["recons"][a:b], res["critic"][a:b], None, rec_error_type=kind, comb=comb, path=None, with_true=False)[0]
-        _same_bits(out["final_scores"][ta:tb], torch.from_numpy(np.asarray(want)), (kind, comb, k))
-        _same_bits(true[ta:tb], adu.unroll_true(xs[k]), (k, "true"))
+        same_bits(out["final_scores"][ta:tb], torch.from_numpy(np.asarray(want)), (kind, comb, k))
+        same_bits(true[ta:tb], adu.unroll_true(xs[k]), (k, "true"))
     if kind == "dtw" and comb == "mult":               # all three kinds at once: the same numbers as one at a time
         allk = adu.euclidean_scores_signals(res, true, kind, comb, kinds=KINDS)
-        _same_bits(allk["final_scores"], out["final_scores"], "all kinds")
+        same_bits(allk["final_scores"], out["final_scores"], "all kinds")
         for kk in KINDS:
-            _same_bits(allk["rec_scores"][kk], adu.euclidean_scores_signals(res, true, kk, "rec")["final_scores"], kk)
+            same_bits(allk["rec_scores"][kk], adu.euclidean_scores_signals(res, true, kk, "rec")["final_scores"], kk)
 
 
 def test_grouped_euclidean_scores_meet_the_reference_numbers():
@@ -226,7 +214,6 @@ def _run_pair(tmp_path, monkeypatch, cfg, names, data, prepare=None):
     """run_signals grouped and per signal in two working directories; returns (runs, final scores seen by find_anomalies, artefacts)."""
     from hypad_amd import main as hmain
     from hypad_amd.utils import anomaly_detection_utils as adu
-    from test_gpu_score_signals import _artefacts
     seen = {}
     real_find = adu.find_anomalies
 
@@ -243,13 +230,13 @@ def _run_pair(tmp_path, monkeypatch, cfg, names, data, prepare=None):
             prepare(wd)
         torch.manual_seed(9)
         runs[key] = hmain.run_signals(SimpleNamespace(**cfg), [n for n, _ in names], None, str(data), log=lambda s_: None, grouped_scoring=grouped)
-        files[key] = _artefacts(wd / "trained_models")
+        files[key] = artefacts(wd / "trained_models")
     monkeypatch.setattr(adu, "find_anomalies", real_find)
     return runs, seen, files
 
 
 def _assert_runs_equal(runs, seen, files, names):
-    from test_gpu_score_signals import _equal, _metrics
+    from test_gpu_score_signals import _metrics
     assert len(seen["grouped"]) == len(seen["per_signal"]) == len(names)
     by_len = lambda arrs: {a.size: a for a in arrs}      # (the grouped run scores its group first: the signals differ in length)
     ga, pa = by_len(seen["grouped"]), by_len(seen["per_signal"])
@@ -264,7 +251,7 @@ def _assert_runs_equal(runs, seen, files, names):
     for f in ("anomalies.csv", "recons_signal.pt", "critic_scores.pickle", "point.pickle", "area.pickle", "dtw.pickle"):
         assert sum(k.endswith(f) for k in fa) == len(names), f
     for k in fa:
-        assert _equal(fa[k], fb[k]), k
+        assert equal(fa[k], fb[k]), k
 
 
 CFG = dict(dataset="NAB", signal="sa", epochs=1, hyperbolic=False, signal_shape=100, lr=5e-4, batch_size=64, save_result=False, filename="",
@@ -275,13 +262,12 @@ NAMES = [("sa", 700), ("sb", 520), ("sc", 180)]          # 180 - 100 windows: a 
 @pytest.mark.parametrize("rec_error", ["point", "area"])
 def test_run_signals_grouped_equals_per_signal_sum(tmp_path, monkeypatch, rec_error):
     from hypad_amd import main as hmain
-    from test_gpu_score_signals import _csv_signals
     d = tmp_path / "data"
     d.mkdir()
-    _csv_signals(d, NAMES)
+    csv_signals(d, NAMES)
     groups = []
     real = hmain._detect_grouped
-    monkeypatch.setattr(hmain, "_detect_grouped", lambda group, *a, **k: groups.append([n for _, n in group]) or real(group, *a, **k))
+    monkeypatch.setattr(hmain, "_detect_grouped", lambda group, *a, **k: groups.append([s.name for s in group]) or real(group, *a, **k))
     runs, seen, files = _run_pair(tmp_path, monkeypatch, dict(CFG, rec_error=rec_error, combination="sum"), NAMES, d)
     assert groups == [[n for n, _ in NAMES]]           # the grouped run scored all three together, the other run none
     _assert_runs_equal(runs, seen, files, NAMES)
@@ -290,10 +276,9 @@ def test_run_signals_grouped_equals_per_signal_sum(tmp_path, monkeypatch, rec_er
 def test_run_signals_leaves_a_cached_signal_to_the_per_signal_detector(tmp_path, monkeypatch):
     from hypad_amd import main as hmain
     from hypad_amd import train as ht
-    from test_gpu_score_signals import _csv_signals
     d = tmp_path / "data"
     d.mkdir()
-    _csv_signals(d, NAMES)
+    csv_signals(d, NAMES)
     # a first run tells the length of sb's scores; its dtw scores, doubled, are the cache both later runs find
     first = tmp_path / "first"
     first.mkdir()
@@ -311,7 +296,7 @@ def test_run_signals_leaves_a_cached_signal_to_the_per_signal_detector(tmp_path,
             pickle.dump(cached, f, protocol=pickle.HIGHEST_PROTOCOL)
     groups = []
     real = hmain._detect_grouped
-    monkeypatch.setattr(hmain, "_detect_grouped", lambda group, *a, **k: groups.append([n for _, n in group]) or real(group, *a, **k))
+    monkeypatch.setattr(hmain, "_detect_grouped", lambda group, *a, **k: groups.append([s.name for s in group]) or real(group, *a, **k))
     runs, seen, files = _run_pair(tmp_path, monkeypatch, CFG, NAMES, d, prepare)
     assert groups == [["sa", "sc"]]
     _assert_runs_equal(runs, seen, files, NAMES)

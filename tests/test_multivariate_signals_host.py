@@ -100,14 +100,14 @@ def _casas_sets(tmp_path, windows):
 
 def test_groupable_takes_a_multivariate_test_set_with_rows(tmp_path):
     from hypad_amd import main as hmain
-    full = _casas_sets(tmp_path, 7)
-    empty = full[:2] + (SimpleNamespace(X=np.zeros((0, 150)), y=[], device_windows=full[2].device_windows), "")
-    assert full[2].X.shape == (7, 150) and hasattr(full[1], "device_windows")
+    full = hmain.Signal(*_casas_sets(tmp_path, 7), "fall")
+    empty = full._replace(test=SimpleNamespace(X=np.zeros((0, 150)), y=[], device_windows=full.test.device_windows))
+    assert full.test.X.shape == (7, 150) and hasattr(full.train, "device_windows")
     assert hmain._groupable(full, "") is True and hmain._groupable(full, str(tmp_path)) is True
     assert hmain._groupable(empty, "") is False
     assert hmain._multivariate(full)
     # `signal: multivariate` (configs/multivariate.yaml) marks a multivariate run as well, whatever the dataset class
-    plain = (SimpleNamespace(dataset="CASAS", signal="multivariate", hyperbolic=False, load=False), SimpleNamespace(),
-             SimpleNamespace(X=np.zeros((3, 150))), "")
+    plain = hmain.Signal(SimpleNamespace(dataset="CASAS", signal="multivariate", hyperbolic=False, load=False), SimpleNamespace(),
+                         SimpleNamespace(X=np.zeros((3, 150))), "", "multivariate")
     assert hmain._groupable(plain, "") is True
-    assert hmain._groupable(plain[:2] + (SimpleNamespace(X=np.zeros((0, 150))), ""), "") is False
+    assert hmain._groupable(plain._replace(test=SimpleNamespace(X=np.zeros((0, 150)))), "") is False

@@ -97,15 +97,16 @@ def test_groupable_keeps_cached_euclidean_signals_per_signal(tmp_path):
     d = tmp_path / "NAB" / "sa"
     d.mkdir(parents=True)
     raw = str(d)                                    # the detector's files are named raw + file (train.model_path has no trailing slash)
-    assert hmain._groupable((eucl, ds, ds, None), raw)
-    assert hmain._groupable((eucl, ds, ds, None), "")
+    eucl, hyper = (hmain.Signal(p, ds, ds, None, "sa") for p in (eucl, hyper))
+    assert hmain._groupable(eucl, raw)
+    assert hmain._groupable(eucl, "")
     for cache in ("dtw", "point", "area", "critic_scores"):
         f = raw + cache + ".pickle"
         open(f, "wb").close()
-        assert not hmain._groupable((eucl, ds, ds, None), raw), cache
-        assert hmain._groupable((hyper, ds, ds, None), raw), cache       # (hyperbolic: only params.load reads a cache back)
+        assert not hmain._groupable(eucl, raw), cache
+        assert hmain._groupable(hyper, raw), cache       # (hyperbolic: only params.load reads a cache back)
         os.remove(f)
-    assert hmain._groupable((eucl, ds, ds, None), raw)
+    assert hmain._groupable(eucl, raw)
 
 
 def _p(v=256):
