@@ -779,6 +779,56 @@ __global__ __launch_bounds__(THREADS) void mobius_linear_fwd_kernel(const float*
   tile_store(out + r0 * N, N, ys, ldy, 16, N, valid);
 }
 
+// mobius_linear in every configuration (hyrnn_nets.py:13-35), and the bare Moebius matvec (project = 0, no bias, no non-linearity):
+// mx = x W^T (saved) ; out = chain(mx, |x|) -- rowops.h: mobius_chain_row.  Ys[16][ldy] holds mx and is rewritten in place; the
+// row norms of x come from its LDS tile.  Four rows per wave, one per group of 16 lanes, as head_rows_tile, in fp64 registers (rowops.h); a Euclidean bias is
+// mapped onto the ball once per wave, in registers, before the rows.
+__device__ __forceinline__ void mobius_chain_rows_tile(float* Ys, int ldy, const float* Xs, int ldx, int K, int N, const float* bias_g,
+                                                       int flags, int nonlin, int project) {
+  const int lane = threadIdx.x & 63, wave = wave_id(), nw = blockDim.x >> 6, sub = lane >> 4;
+  const MobiusCfg cfg{(flags & HYPAD_ML_HYPER_INPUT) != 0, bias_g != nullptr, project != 0, nonlin};
+  epl16_dispatch(N, [&](auto tag) {
+    using R = RowD<16, decltype(tag)::value>;
+    R b = {};
+    if (cfg.has_bias) {
+      b = rowd_load<R>(bias_g, N, lane);
+      if (!(flags & HYPAD_ML_HYPER_BIAS)) b = radial_map_d<true>(b);
+    }
+    for (int r0 = wave * 4; r0 < 16; r0 += nw * 4) {
+      const int r = r0 + sub;
+      double xraw = 0.0;
+      if (cfg.hyper_in) {
+        double s = 0.0;
+        for (int c = lane & 15; c < K; c += 16) { const double v = Xs[r * ldx + c]; s += v * v; }
+        xraw = sqrt(groupd_sum<16>(s));
+      }
+      const R o = mobius_chain_row(rowd_load<R>(Ys + r * ldy, N, lane), xraw, b, cfg);
+      rowd_store(Ys + r * ldy, o, N, lane);
+    }
+  });
+}
+__global__ __launch_bounds__(THREADS) void mobius_linear_ex_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                                        const float* __restrict__ bias, float* __restrict__ out,
+                                                                        float* __restrict__ mx_save, int64_t rows, int K, int N,
+                                                                        int flags, int nonlin, int project) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int ldx = ld_of(K), ldy = ld_of(N);
+  float* xs = smem;
+  float* ys = xs + 16 * ldx;
+  float* wst = ys + 16 * ldy;
+  const int64_t r0 = (int64_t)blockIdx.x * 16;
+  const int valid = (int)min((int64_t)16, rows - r0);
+  tile_load(xs, ldx, x + r0 * K, K, 16, K, valid);
+  __syncthreads();
+  gemm_nt<1, true>(xs, ldx, w, K, K, N, identity_map(), nullptr, nullptr, ys, ldy, 0, wst);
+  __syncthreads();
+  if (mx_save) tile_store(mx_save + r0 * N, N, ys, ldy, 16, N, valid);
+  __syncthreads();
+  mobius_chain_rows_tile(ys, ldy, xs, ldx, K, N, bias, flags, nonlin, project);
+  __syncthreads();
+  tile_store(out + r0 * N, N, ys, ldy, 16, N, valid);
+}
+
 // fused scoring forward (anomaly_detection.py:67-113 + utils/anomaly_detection_utils.py:58-66)
 __global__ __launch_bounds__(THREADS) void score_forward_kernel(const float* __restrict__ PE, const float* __restrict__ PD,
                                                                  const float* __restrict__ PC, const float* __restrict__ x,
@@ -1111,6 +1161,85 @@ int hypad_mobius_linear_bwd(const float* x, const float* w, const float* bias, c
   // grad_x = gu W ; grad_w = gu^T x
   return hypad_linear_act_bwd(x, w, nullptr, gu, gx, gw, nullptr, gw ? gb_rows /*scratch for grad_pre*/ : nullptr, rows, K, N,
                               HYPAD_ACT_NONE, s);
+}
+
+// ---- mobius_linear in every configuration; the bare matvec is the same pair of launches without bias, non-linearity and project
+static int mobius_ex_check(const float* w, int64_t rows, int K, int N, int flags, int nonlin, bool fwd) {
+  if (!w || rows < 0 || K <= 0 || N <= 0) return HYPAD_EINVAL;
+  if ((flags & ~(HYPAD_ML_HYPER_INPUT | HYPAD_ML_HYPER_BIAS)) || nonlin < HYPAD_NONLIN_NONE || nonlin > HYPAD_NONLIN_RELU) return HYPAD_EINVAL;
+  if (N > 64 * MAX_EPL) return HYPAD_EUNSUPPORTED;
+  // (the backward's LDS is that of hypad_linear_act_bwd: refused here, before the row kernel has written anything)
+  if ((size_t)(16 * (ld_of(K) + ld_of(N)) + (fwd ? WST : 0)) * sizeof(float) > 150 * 1024) return HYPAD_EUNSUPPORTED;
+  return HYPAD_OK;
+}
+static int mobius_ex_fwd(const float* x, const float* w, const float* bias, float* out, float* mx_save, int64_t rows, int K, int N,
+                         int flags, int nonlin, int project, hypad_stream_t s) {
+  int rc = mobius_ex_check(w, rows, K, N, flags, nonlin, true);
+  if (rc) return rc;
+  if (rows == 0) return HYPAD_OK;
+  if (!x || !out) return HYPAD_EINVAL;
+  size_t lds = (size_t)(16 * (ld_of(K) + ld_of(N)) + WST) * sizeof(float);
+  hipError_t e = allow_lds((const void*)mobius_linear_ex_fwd_kernel, lds);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(mobius_linear_ex_fwd_kernel, dim3(tiles16(rows)), dim3(THREADS), lds, (hipStream_t)s, x, w, bias, out, mx_save,
+                     rows, K, N, flags, nonlin, project);
+  HYPAD_CHECK_LAUNCH();
+  return HYPAD_OK;
+}
+static int mobius_ex_bwd(const float* x, const float* w, const float* bias, const float* mx_saved, const float* go, float* gx,
+                         float* gw, float* gbias, void* workspace, size_t workspace_bytes, int64_t rows, int K, int N, int flags,
+                         int nonlin, int project, hypad_stream_t s) {
+  int rc = mobius_ex_check(w, rows, K, N, flags, nonlin, false);
+  if (rc) return rc;
+  if (gbias && !bias) return HYPAD_EINVAL;
+  if (rows == 0) {                                         // an empty batch: zeros for the parameter gradients (hypad_mobius_linear_bwd)
+    rc = zero_floats(gbias, (size_t)N, s);
+    return rc ? rc : zero_floats(gw, (size_t)N * K, s);
+  }
+  if (!x || !mx_saved || !go) return HYPAD_EINVAL;
+  if (!workspace || workspace_bytes < hypad_mobius_linear_ex_workspace_bytes(rows, N)) return HYPAD_EWORKSPACE;
+  const bool hyper_in = (flags & HYPAD_ML_HYPER_INPUT) != 0, hyper_bias = (flags & HYPAD_ML_HYPER_BIAS) != 0;
+  float* gmx = (float*)workspace;                          // (rows, N)
+  float* gb_rows = gmx + (size_t)rows * N;                 // (rows, N): per-row bias gradients, then grad_pre scratch
+  float* gxn = gb_rows + (size_t)rows * N;                 // (rows): dL/d|x|
+  float* gball = gxn + rows;                               // (N): the gradient of the mapped bias
+  rc = mobius_chain_bwd_launch(x, mx_saved, bias, go, gmx, gbias ? gb_rows : nullptr, hyper_in ? gxn : nullptr, rows, K, N, hyper_in,
+                               hyper_bias, nonlin, project, s);
+  if (rc) return rc;
+  if (gbias) {
+    rc = hypad_column_sum(gb_rows, hyper_bias ? gbias : gball, rows, N, s);
+    if (rc) return rc;
+    if (!hyper_bias) {                                     // bias -> expmap0(bias), once
+      rc = hypad_expmap0_bwd(bias, gball, gbias, 1, N, s);
+      if (rc) return rc;
+    }
+  }
+  // grad_x = gmx W ; grad_w = gmx^T x
+  rc = hypad_linear_act_bwd(x, w, nullptr, gmx, gx, gw, nullptr, gw ? gb_rows : nullptr, rows, K, N, HYPAD_ACT_NONE, s);
+  if (rc || !hyper_in || !gx) return rc;
+  return norm_grad_add_launch(x, gxn, gx, rows, K, s);     // grad_x += dL/d|x| x / |x|
+}
+
+size_t hypad_mobius_linear_ex_workspace_bytes(int64_t rows, int out_dim) {
+  return ((size_t)rows * out_dim * 2 + (size_t)rows + (size_t)out_dim) * sizeof(float);
+}
+int hypad_mobius_linear_ex_fwd(const float* x, const float* w, const float* bias, float* out, float* mx_save, int64_t rows, int K,
+                               int N, int flags, int nonlin, hypad_stream_t s) {
+  return mobius_ex_fwd(x, w, bias, out, mx_save, rows, K, N, flags, nonlin, 1, s);
+}
+int hypad_mobius_linear_ex_bwd(const float* x, const float* w, const float* bias, const float* mx_saved, const float* go,
+                               float* gx, float* gw, float* gbias, void* workspace, size_t workspace_bytes, int64_t rows, int K,
+                               int N, int flags, int nonlin, hypad_stream_t s) {
+  return mobius_ex_bwd(x, w, bias, mx_saved, go, gx, gw, gbias, workspace, workspace_bytes, rows, K, N, flags, nonlin, 1, s);
+}
+int hypad_mobius_matvec_fwd(const float* x, const float* w, float* out, float* mx_save, int64_t rows, int K, int N,
+                            hypad_stream_t s) {
+  return mobius_ex_fwd(x, w, nullptr, out, mx_save, rows, K, N, HYPAD_ML_HYPER_INPUT, HYPAD_NONLIN_NONE, 0, s);
+}
+int hypad_mobius_matvec_bwd(const float* x, const float* w, const float* mx_saved, const float* go, float* gx, float* gw,
+                            void* workspace, size_t workspace_bytes, int64_t rows, int K, int N, hypad_stream_t s) {
+  return mobius_ex_bwd(x, w, nullptr, mx_saved, go, gx, gw, nullptr, workspace, workspace_bytes, rows, K, N, HYPAD_ML_HYPER_INPUT,
+                       HYPAD_NONLIN_NONE, 0, s);
 }
 
 int hypad_score_forward(const float* enc, const float* dec, const float* cx, const float* x, float* hyper, float* eucl,

@@ -201,6 +201,54 @@ __global__ __launch_bounds__(THREADS) void head_rows_bwd(const float* __restrict
   }
 }
 
+// Row backward of mobius_linear in any configuration / of the bare matvec (rowops.h: mobius_chain_row_bwd): one wave per row of
+// the saved mx = x W^T, in fp64 registers; |x| is taken from the row of x again.  A Euclidean bias is mapped onto the ball once per wave.
+__device__ __forceinline__ float row_sumsq(const float* __restrict__ p, int n, int lane) {
+  float s = 0.f;
+  for (int c = lane; c < n; c += 64) { const float v = p[c]; s += v * v; }
+  return wave_sum(s);
+}
+__global__ __launch_bounds__(THREADS) void mobius_chain_rows_bwd(const float* __restrict__ x, const float* __restrict__ mx,
+                                                                  const float* __restrict__ bias, const float* __restrict__ go,
+                                                                  float* __restrict__ gmx, float* __restrict__ gb_rows,
+                                                                  float* __restrict__ gxn, int64_t rows, int K, int N, int hyper_in,
+                                                                  int hyper_bias, int nonlin, int project) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave0 = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
+  const int64_t stride = (int64_t)gridDim.x * WAVES;
+  const MobiusCfg cfg{hyper_in != 0, bias != nullptr, project != 0, nonlin};
+  using R = RowD<64, MAX_EPL>;
+  R b = {};
+  if (cfg.has_bias) {
+    b = rowd_load<R>(bias, N, lane);
+    if (!hyper_bias) b = radial_map_d<true>(b);
+  }
+  for (int64_t r = wave0; r < rows; r += stride) {
+    double xraw = 0.0;
+    if (cfg.hyper_in) {
+      double s = 0.0;
+      for (int c = lane; c < K; c += 64) { const double v = x[r * K + c]; s += v * v; }
+      xraw = sqrt(groupd_sum<64>(s));
+    }
+    R du, db = {};
+    const double gn = mobius_chain_row_bwd(rowd_load<R>(mx + r * N, N, lane), xraw, b, cfg, rowd_load<R>(go + r * N, N, lane), du, db);
+    rowd_store(gmx + r * N, du, N, lane);
+    if (gb_rows) rowd_store(gb_rows + r * N, db, N, lane);
+    if (gxn && lane == 0) gxn[r] = (float)gn;
+  }
+}
+// grad_x += dL/d|x| x / |x|: what the norm inside the matvec sends back to its row (a row at |x| = 0 carries dL/d|x| = 0)
+__global__ __launch_bounds__(THREADS) void norm_grad_add_rows(const float* __restrict__ x, const float* __restrict__ gxn,
+                                                               float* __restrict__ gx, int64_t rows, int K) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave0 = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
+  const int64_t stride = (int64_t)gridDim.x * WAVES;
+  for (int64_t r = wave0; r < rows; r += stride) {
+    const float coef = gxn[r] / fmaxf(sqrtf(row_sumsq(x + r * K, K, lane)), MIN_NORM);
+    for (int c = lane; c < K; c += 64) gx[r * K + c] += coef * x[r * K + c];
+  }
+}
+
 template <int EPL>
 __global__ __launch_bounds__(THREADS) void rowdist_rows(const float* __restrict__ u, const float* __restrict__ v,
                                                          float* __restrict__ dist, int64_t rows, int dim) {
@@ -343,6 +391,23 @@ int launch_unary(const float* a, const float* g, float* out, int64_t rows, int d
 }
 
 }  // namespace
+
+namespace hypad {
+
+int mobius_chain_bwd_launch(const float* x, const float* mx, const float* bias, const float* go, float* gmx, float* gb_rows, float* gxn,
+                            int64_t rows, int K, int N, bool hyper_in, bool hyper_bias, int nonlin, int project, void* stream) {
+  hipLaunchKernelGGL(mobius_chain_rows_bwd, dim3(row_grid(rows)), dim3(THREADS), 0, (hipStream_t)stream, x, mx, bias, go, gmx, gb_rows,
+                     gxn, rows, K, N, (int)hyper_in, (int)hyper_bias, nonlin, project);
+  HYPAD_CHECK_LAUNCH();
+  return HYPAD_OK;
+}
+int norm_grad_add_launch(const float* x, const float* gxn, float* gx, int64_t rows, int K, void* stream) {
+  hipLaunchKernelGGL(norm_grad_add_rows, dim3(row_grid(rows)), dim3(THREADS), 0, (hipStream_t)stream, x, gxn, gx, rows, K);
+  HYPAD_CHECK_LAUNCH();
+  return HYPAD_OK;
+}
+
+}  // namespace hypad
 
 extern "C" {
 

@@ -178,6 +178,221 @@ __device__ __forceinline__ void head_row_bwd(const R& u, const R& bias, const R&
   du = expmap0_row_bwd(u, dp);
 }
 
+// ---- mobius_linear in any configuration (hyrnn_nets.py:13-58): the row chain after mx = x W^T, carried in fp64 registers.
+// Why fp64: the matvec scaling leaves a row at norm tanh(|mx| / |x| artanh |x|) -- 1 - 1e-5 for an input a layer before this one
+// projected to the rim -- and whatever follows (logmap0 of the non-linearity, the Moebius add) takes 1 - norm from that row again.
+// In fp32 the last bit of the row's sum of squares decides three digits of 1 - norm: out moves by 1e-5 and grad_x by 1e-3 of its
+// size with nothing but the order of a sum (docs/history/mobius_modes.md).  The chain lives in registers from the load of mx to
+// the store of the result, so carrying it in fp64 costs no memory traffic; mx, the bias, the results and every buffer stay fp32.
+// Same formulas and clamps as the fp32 row functions above (MIN_NORM under a norm, TANH_CLAMP, 1 - ARTANH_EPS, BALL_MAXNORM);
+// on a clamp nothing flows back through the clamped quantity, as autograd gives the reference.
+template <int G_, int EPL_>
+struct RowD {
+  static constexpr int G = G_, EPL = EPL_;
+  double v[EPL_];
+};
+#define HYPAD_ROW_EACH for (int e = 0; e < R::EPL; ++e)
+template <class R>
+__device__ __forceinline__ R rowd_load(const float* p, int dim, int lane) {
+  R r;
+#pragma unroll
+  HYPAD_ROW_EACH { int c = (lane & (R::G - 1)) + R::G * e; r.v[e] = c < dim ? (double)p[c] : 0.0; }
+  return r;
+}
+template <class R>
+__device__ __forceinline__ void rowd_store(float* p, const R& r, int dim, int lane) {
+#pragma unroll
+  HYPAD_ROW_EACH { int c = (lane & (R::G - 1)) + R::G * e; if (c < dim) p[c] = (float)r.v[e]; }
+}
+template <int G>
+__device__ __forceinline__ double groupd_sum(double s) {
+#pragma unroll
+  for (int off = G >> 1; off > 0; off >>= 1) s += __shfl_xor(s, off, WAVE);
+  return s;
+}
+template <class R>
+__device__ __forceinline__ double rowd_dot(const R& a, const R& b) {
+  double s = 0.0;
+#pragma unroll
+  HYPAD_ROW_EACH s += a.v[e] * b.v[e];
+  return groupd_sum<R::G>(s);
+}
+__device__ __forceinline__ double tanh_clamped_d(double x) { return tanh(fmin(x, (double)TANH_CLAMP)); }
+__device__ __forceinline__ double tanh_prime_d(double x, double t) { return x <= (double)TANH_CLAMP ? 1.0 - t * t : 0.0; }
+constexpr double ARTANH_TOP = 1.0 - 1e-7;                       // math_.py:58
+__device__ __forceinline__ double artanh_clamped_d(double x) { x = fmin(x, ARTANH_TOP); return 0.5 * (log1p(x) - log1p(-x)); }
+__device__ __forceinline__ double artanh_prime_d(double x) { return x <= ARTANH_TOP ? 1.0 / ((1.0 - x) * (1.0 + x)) : 0.0; }
+
+// y = f(|u|) u with f(n) = g(n) / n: expmap0 (g = tanh) and logmap0 (g = artanh) and their common backward
+template <bool EXP, class R>
+__device__ __forceinline__ R radial_map_d(const R& u) {
+  const double n = fmax(sqrt(rowd_dot(u, u)), (double)MIN_NORM);
+  const double f = (EXP ? tanh_clamped_d(n) : artanh_clamped_d(n)) / n;
+  R o;
+#pragma unroll
+  HYPAD_ROW_EACH o.v[e] = f * u.v[e];
+  return o;
+}
+template <bool EXP, class R>
+__device__ __forceinline__ R radial_map_bwd_d(const R& u, const R& go) {
+  const double raw = sqrt(rowd_dot(u, u));
+  const double n = fmax(raw, (double)MIN_NORM);
+  const double g = EXP ? tanh_clamped_d(n) : artanh_clamped_d(n);
+  const double gp = EXP ? tanh_prime_d(n, g) : artanh_prime_d(n);
+  const double f = g / n, dfdn = (gp * n - g) / (n * n);
+  const double s = raw >= (double)MIN_NORM ? rowd_dot(go, u) * dfdn / n : 0.0;
+  R du;
+#pragma unroll
+  HYPAD_ROW_EACH du.v[e] = f * go.v[e] + s * u.v[e];
+  return du;
+}
+// mobius_add (math_.py:536-555)
+template <class R>
+__device__ __forceinline__ R mobius_add_d(const R& x, const R& y) {
+  const double x2 = rowd_dot(x, x), y2 = rowd_dot(y, y), xy = rowd_dot(x, y);
+  const double A = 1.0 + 2.0 * xy + y2, Bc = 1.0 - x2, rD = 1.0 / fmax(1.0 + 2.0 * xy + x2 * y2, (double)MIN_NORM);
+  R m;
+#pragma unroll
+  HYPAD_ROW_EACH m.v[e] = (A * x.v[e] + Bc * y.v[e]) * rD;
+  return m;
+}
+template <class R>
+__device__ __forceinline__ void mobius_add_bwd_d(const R& x, const R& y, const R& dm, R& dx, R& dy) {
+  const double x2 = rowd_dot(x, x), y2 = rowd_dot(y, y), xy = rowd_dot(x, y);
+  const double A = 1.0 + 2.0 * xy + y2, Bc = 1.0 - x2, Draw = 1.0 + 2.0 * xy + x2 * y2;
+  const double rD = 1.0 / fmax(Draw, (double)MIN_NORM);
+  R m, dN;
+#pragma unroll
+  HYPAD_ROW_EACH { m.v[e] = (A * x.v[e] + Bc * y.v[e]) * rD; dN.v[e] = dm.v[e] * rD; }
+  const double dD = Draw >= (double)MIN_NORM ? -rowd_dot(dm, m) * rD : 0.0;
+  const double dA = rowd_dot(dN, x), dBc = rowd_dot(dN, y);
+  const double dxy = 2.0 * dA + 2.0 * dD, dx2 = -dBc + y2 * dD, dy2 = dA + x2 * dD;
+#pragma unroll
+  HYPAD_ROW_EACH {
+    dx.v[e] = A * dN.v[e] + 2.0 * dx2 * x.v[e] + dxy * y.v[e];
+    dy.v[e] = Bc * dN.v[e] + 2.0 * dy2 * y.v[e] + dxy * x.v[e];
+  }
+}
+// project (math_.py:340-352), the fp32 eps
+template <class R>
+__device__ __forceinline__ R project_d(const R& x) {
+  const double n = fmax(sqrt(rowd_dot(x, x)), (double)MIN_NORM);
+  R o = x;
+  if (n > (double)BALL_MAXNORM) {
+    const double sc = (double)BALL_MAXNORM / n;
+#pragma unroll
+    HYPAD_ROW_EACH o.v[e] = x.v[e] * sc;
+  }
+  return o;
+}
+template <class R>
+__device__ __forceinline__ R project_bwd_d(const R& x, const R& go) {
+  const double raw = sqrt(rowd_dot(x, x));
+  const double n = fmax(raw, (double)MIN_NORM);
+  if (!(n > (double)BALL_MAXNORM)) return go;
+  const double s = raw >= (double)MIN_NORM ? rowd_dot(x, go) / (n * n) : 0.0, sc = (double)BALL_MAXNORM / n;
+  R gx;
+#pragma unroll
+  HYPAD_ROW_EACH gx.v[e] = sc * (go.v[e] - x.v[e] * s);
+  return gx;
+}
+
+// Moebius matrix-vector product, the part after mx = x W^T (hyrnn_nets.py:42-58; math_.py:1308-1323): tanh(|mx| / |x| artanh |x|)
+// mx / |mx|.  xraw = |x| of the row the product came from, before its clamp.  A row of mx that is exactly zero gives the zero row
+// (the reference's `cond`) and gets zero gradients.
+template <class R>
+__device__ __forceinline__ bool rowd_all_zero(const R& a) {
+  double nz = 0.0;
+#pragma unroll
+  HYPAD_ROW_EACH nz += a.v[e] != 0.0 ? 1.0 : 0.0;
+  return groupd_sum<R::G>(nz) == 0.0;
+}
+template <class R>
+__device__ __forceinline__ R mobius_matvec_row(const R& mx, double xraw) {
+  const double xn = fmax(xraw, (double)MIN_NORM);
+  const double mn = fmax(sqrt(rowd_dot(mx, mx)), (double)MIN_NORM);
+  const double s = rowd_all_zero(mx) ? 0.0 : tanh_clamped_d(mn / xn * artanh_clamped_d(xn)) / mn;
+  R o;
+#pragma unroll
+  HYPAD_ROW_EACH o.v[e] = s * mx.v[e];
+  return o;
+}
+// d mx and (returned) dL/d|x|
+template <class R>
+__device__ __forceinline__ double mobius_matvec_row_bwd(const R& mx, double xraw, const R& go, R& dmx) {
+  const double xn = fmax(xraw, (double)MIN_NORM);
+  const double mraw = sqrt(rowd_dot(mx, mx));
+  const double mn = fmax(mraw, (double)MIN_NORM);
+  const double a = artanh_clamped_d(xn), q = a / xn, arg = mn / xn * a;
+  const double t = tanh_clamped_d(arg), tp = tanh_prime_d(arg, t);
+  const bool cond = rowd_all_zero(mx);
+  const double s = cond ? 0.0 : t / mn;
+  const double gm = cond ? 0.0 : rowd_dot(go, mx);             // d L / d s
+  const double dsdmn = (tp * q * mn - t) / (mn * mn);
+  const double c = mraw >= (double)MIN_NORM ? gm * dsdmn / mn : 0.0;
+#pragma unroll
+  HYPAD_ROW_EACH dmx.v[e] = s * go.v[e] + c * mx.v[e];
+  const double dqdxn = (artanh_prime_d(xn) * xn - a) / (xn * xn);
+  return xraw >= (double)MIN_NORM ? gm * tp * dqdxn : 0.0;     // (d s / d q = tp)
+}
+
+// mobius_fn_apply (math_.py:1431-1469): expmap0(f(logmap0(x))) for the two functions the layer takes
+enum { NONLIN_NONE = 0, NONLIN_TANH = 1, NONLIN_RELU = 2 };
+template <int NONLIN, class R>
+__device__ __forceinline__ R mobius_fn_row(const R& x) {
+  R l = radial_map_d<false>(x);
+#pragma unroll
+  HYPAD_ROW_EACH l.v[e] = NONLIN == NONLIN_TANH ? tanh(l.v[e]) : fmax(l.v[e], 0.0);
+  return radial_map_d<true>(l);
+}
+template <int NONLIN, class R>
+__device__ __forceinline__ R mobius_fn_row_bwd(const R& x, const R& go) {
+  const R l = radial_map_d<false>(x);
+  R f;
+#pragma unroll
+  HYPAD_ROW_EACH f.v[e] = NONLIN == NONLIN_TANH ? tanh(l.v[e]) : fmax(l.v[e], 0.0);
+  R df = radial_map_bwd_d<true>(f, go);
+#pragma unroll
+  HYPAD_ROW_EACH df.v[e] *= NONLIN == NONLIN_TANH ? 1.0 - f.v[e] * f.v[e] : (l.v[e] > 0.0 ? 1.0 : 0.0);
+  return radial_map_bwd_d<false>(x, df);
+}
+
+// The chain (hyrnn_nets.py:23-35): matvec scaling or expmap0, the optional Moebius bias add, the optional non-linearity, project.
+// `b` is the bias ON THE BALL (a Euclidean bias is mapped by the caller, once).
+struct MobiusCfg { bool hyper_in, has_bias, project; int nonlin; };
+template <class R>
+__device__ __forceinline__ R mobius_chain_row(const R& mx, double xraw, const R& b, const MobiusCfg c) {
+  R o = c.hyper_in ? mobius_matvec_row(mx, xraw) : radial_map_d<true>(mx);
+  if (c.has_bias) o = mobius_add_d(o, b);
+  if (c.nonlin == NONLIN_TANH) o = mobius_fn_row<NONLIN_TANH>(o);
+  else if (c.nonlin == NONLIN_RELU) o = mobius_fn_row<NONLIN_RELU>(o);
+  return c.project ? project_d(o) : o;
+}
+// everything but mx is recomputed (as head_row_bwd does); returns dL/d|x| (0 for a Euclidean input)
+template <class R>
+__device__ __forceinline__ double mobius_chain_row_bwd(const R& mx, double xraw, const R& b, const MobiusCfg c, const R& go, R& dmx, R& db) {
+  const R p = c.hyper_in ? mobius_matvec_row(mx, xraw) : radial_map_d<true>(mx);
+  const R m = c.has_bias ? mobius_add_d(p, b) : p;
+  R d = go;
+  if (c.project) {
+    R f = m;
+    if (c.nonlin == NONLIN_TANH) f = mobius_fn_row<NONLIN_TANH>(m);
+    else if (c.nonlin == NONLIN_RELU) f = mobius_fn_row<NONLIN_RELU>(m);
+    d = project_bwd_d(f, d);
+  }
+  if (c.nonlin == NONLIN_TANH) d = mobius_fn_row_bwd<NONLIN_TANH>(m, d);
+  else if (c.nonlin == NONLIN_RELU) d = mobius_fn_row_bwd<NONLIN_RELU>(m, d);
+  if (c.has_bias) {
+    R dp;
+    mobius_add_bwd_d(p, b, d, dp, db);
+    d = dp;
+  }
+  if (c.hyper_in) return mobius_matvec_row_bwd(mx, xraw, d, dmx);
+  dmx = radial_map_bwd_d<true>(mx, d);
+  return 0.0;
+}
+#undef HYPAD_ROW_EACH
+
 // ---- row-wise Poincare distance (train.py:226-230)
 template <class R>
 __device__ __forceinline__ float rowdist_row(const R& u, const R& v) {
@@ -206,6 +421,13 @@ __device__ __forceinline__ float rowdist_row_bwd(const R& u, const R& v, float g
   }
   return acoshf(xt);
 }
+
+// Host launchers of ops_hyper.hip that the layer entry points of ops_dense.hip call (not exported; arguments checked by the caller):
+// the row backward of mobius_chain_row -- g_mx (rows, N), the per-row bias gradients and dL/d|x| per row (either may be null) -- and
+// grad_x += dL/d|x| x / |x|.
+int mobius_chain_bwd_launch(const float* x, const float* mx, const float* bias, const float* go, float* gmx, float* gb_rows, float* gxn,
+                            int64_t rows, int K, int N, bool hyper_in, bool hyper_bias, int nonlin, int project, void* stream);
+int norm_grad_add_launch(const float* x, const float* gxn, float* gx, int64_t rows, int K, void* stream);
 
 // f(integral_constant<int, EPL>) with the 16-lanes-per-row EPL that fits `dim` (wave-uniform branch)
 template <class F>

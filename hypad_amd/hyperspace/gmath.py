@@ -98,6 +98,22 @@ def mobius_add(x, y, *, k=None, dim=-1):
     return _MobiusAdd.apply(x, y)
 
 
+def mobius_fn_apply(fn, x, *args, k=None, dim=-1, **kwargs):
+    """expmap0(fn(logmap0(x)))  (math_.py:1431-1469): the two maps are the HIP kernels above (first-order gradients, as theirs);
+    ``fn`` is the caller's own function of the tangent vector.  Inside mobius_linear, tanh and relu run fused in the layer's
+    kernels instead (hyrnn_nets.mobius_linear)."""
+    _check_k(k)
+    if dim != -1 and dim != x.dim() - 1:
+        raise NotImplementedError("mobius_fn_apply: only the last dimension (dim = -1) is implemented")
+    return expmap0(fn(logmap0(x), *args, **kwargs))
+
+
+def mobius_matvec(m, x, *, k=None, dim=-1):
+    """math_.py:1308-1323: see hyrnn_nets.mobius_matvec (one HIP launch, differentiable in m and x)."""
+    from .hyrnn_nets import mobius_matvec as _matvec
+    return _matvec(m, x, k=-1.0 if k is None else k, dim=dim)
+
+
 class _RowDist(torch.autograd.Function):
     @staticmethod
     def forward(ctx, u, v):

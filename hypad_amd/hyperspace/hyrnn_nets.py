@@ -1,7 +1,9 @@
-"""MobiusLinear / mobius_linear on the GPU (reference: hyperspace/hyrnn_nets.py:13-35, :154-200).
+"""MobiusLinear / mobius_linear / mobius_matvec on the GPU (reference: hyperspace/hyrnn_nets.py:13-58, :154-200).
 
-Only the configuration the hot path uses is implemented: Euclidean input, ball-valued bias, no
-non-linearity, k = -1, fp32 (models/tadgan.py:43-52).  Anything else raises.
+Every configuration of the layer runs as one fused HIP forward launch and a HIP backward: Euclidean or ball-valued
+input (the latter through the Moebius matrix-vector product), ball-valued, Euclidean or no bias, and no
+non-linearity, tanh or relu.  The configuration the hot path uses (Euclidean input, ball-valued bias, no
+non-linearity: models/tadgan.py:43-52) keeps its own entry points.  k = -1 and fp32 only; anything else raises.
 """
 import math
 
@@ -67,11 +69,116 @@ class _MobiusLinearFn(torch.autograd.Function):
         return gx.view(ctx.xshape), gw, gb
 
 
+def _rows_of(x, weight, what):
+    x = _C.require_cuda(x.to(torch.float32).contiguous(), "input")
+    w = _C.require_cuda(weight.contiguous(), "weight")
+    if w.dim() != 2 or x.dim() < 1 or x.shape[-1] != w.shape[1]:
+        raise _C.HypadError(f"{what}: weight must be (out_features, in_features) and the input (..., in_features), got "
+                            f"{tuple(w.shape)} and {tuple(x.shape)}")
+    return x, x.reshape(-1, x.shape[-1]), w
+
+
+class _MobiusLinearExFn(torch.autograd.Function):
+    """mobius_linear in any configuration (hypad_mobius_linear_ex_*).  Saved for the backward: x, the parameters and mx = x W^T."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, flags, nonlin):
+        x, x2, w = _rows_of(x, weight, "mobius_linear")
+        b = None if bias is None else _C.require_cuda(bias.contiguous(), "bias")
+        rows, k, n = x2.shape[0], x2.shape[1], w.shape[0]
+        out = torch.empty(rows, n, device=x.device, dtype=torch.float32)
+        mx = torch.empty(rows, n, device=x.device, dtype=torch.float32)
+        _C.check(_C.lib.hypad_mobius_linear_ex_fwd(_C.ptr(x2), _C.ptr(w), _C.ptr(b), _C.ptr(out), _C.ptr(mx), rows, k, n, flags, nonlin,
+                                                   _C.stream()), "mobius_linear_ex_fwd")
+        ctx.save_for_backward(x2, w, mx, *(() if b is None else (b,)))
+        ctx.xshape, ctx.flags, ctx.nonlin = x.shape, flags, nonlin
+        return out.view(*x.shape[:-1], n)
+
+    @staticmethod
+    @_C.first_order_only
+    def backward(ctx, go):
+        x2, w, mx, *rest = ctx.saved_tensors
+        b = rest[0] if rest else None
+        rows, k, n = x2.shape[0], x2.shape[1], w.shape[0]
+        go2 = go.to(torch.float32).contiguous().reshape(rows, n)
+        gx = torch.empty_like(x2)
+        gw = torch.empty_like(w)
+        gb = None if b is None else torch.empty_like(b)
+        nbytes = _C.lib.hypad_mobius_linear_ex_workspace_bytes(rows, n)
+        ws = torch.empty(max(nbytes // 4, 1), device=x2.device, dtype=torch.float32)
+        _C.check(_C.lib.hypad_mobius_linear_ex_bwd(_C.ptr(x2), _C.ptr(w), _C.ptr(b), _C.ptr(mx), _C.ptr(go2), _C.ptr(gx), _C.ptr(gw),
+                                                   _C.ptr(gb), _C.ptr(ws), nbytes, rows, k, n, ctx.flags, ctx.nonlin, _C.stream()),
+                 "mobius_linear_ex_bwd")
+        return gx.view(ctx.xshape), gw, gb, None, None
+
+
+class _MobiusMatvecFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, m, x):
+        x, x2, w = _rows_of(x, m, "mobius_matvec")
+        rows, k, n = x2.shape[0], x2.shape[1], w.shape[0]
+        out = torch.empty(rows, n, device=x.device, dtype=torch.float32)
+        mx = torch.empty(rows, n, device=x.device, dtype=torch.float32)
+        _C.check(_C.lib.hypad_mobius_matvec_fwd(_C.ptr(x2), _C.ptr(w), _C.ptr(out), _C.ptr(mx), rows, k, n, _C.stream()),
+                 "mobius_matvec_fwd")
+        ctx.save_for_backward(x2, w, mx)
+        ctx.xshape = x.shape
+        return out.view(*x.shape[:-1], n)
+
+    @staticmethod
+    @_C.first_order_only
+    def backward(ctx, go):
+        x2, w, mx = ctx.saved_tensors
+        rows, k, n = x2.shape[0], x2.shape[1], w.shape[0]
+        go2 = go.to(torch.float32).contiguous().reshape(rows, n)
+        gx = torch.empty_like(x2)
+        gw = torch.empty_like(w)
+        nbytes = _C.lib.hypad_mobius_linear_ex_workspace_bytes(rows, n)
+        ws = torch.empty(max(nbytes // 4, 1), device=x2.device, dtype=torch.float32)
+        _C.check(_C.lib.hypad_mobius_matvec_bwd(_C.ptr(x2), _C.ptr(w), _C.ptr(mx), _C.ptr(go2), _C.ptr(gx), _C.ptr(gw), _C.ptr(ws), nbytes,
+                                                rows, k, n, _C.stream()), "mobius_matvec_bwd")
+        return gw, gx.view(ctx.xshape)
+
+
+_SUPPORTED = ("supported: hyperbolic_input and hyperbolic_bias True or False, bias a vector or None, nonlin None, torch.tanh, "
+              "torch.relu or torch.nn.functional.relu, k = -1, fp32, a 2-D weight and dim = -1")
+
+
+def _check_k(k, what):
+    if abs(float(k) + 1.0) > 1e-12:
+        raise NotImplementedError(f"{what}: curvature k = {float(k)} is not implemented; {_SUPPORTED}")
+
+
+def mobius_matvec(m, x, *, k, dim=-1):
+    """M (x) x for ball-valued rows of x (reference: hyperspace/hyrnn_nets.py:38-58): one HIP launch forward, differentiable in
+    m and x (first order)."""
+    _check_k(k, "mobius_matvec")
+    if dim != -1 and dim != x.dim() - 1:
+        raise NotImplementedError(f"mobius_matvec: dim = {dim} is not implemented; {_SUPPORTED}")
+    if m.dim() != 2:
+        raise NotImplementedError(f"mobius_matvec: a batched m of {m.dim()} dimensions is not implemented; {_SUPPORTED}")
+    return _MobiusMatvecFn.apply(m, x)
+
+
+def _nonlin_code(nonlin):
+    if nonlin is None:
+        return _C.NONLIN_NONE
+    if nonlin is torch.tanh:
+        return _C.NONLIN_TANH
+    if nonlin is torch.relu or nonlin is torch.nn.functional.relu:
+        return _C.NONLIN_RELU
+    raise NotImplementedError(f"mobius_linear: nonlin = {nonlin!r} has no HIP kernel; {_SUPPORTED}")
+
+
 def mobius_linear(input, weight, bias=None, hyperbolic_input=True, hyperbolic_bias=True, nonlin=None, k=-1.0):
-    if hyperbolic_input or not hyperbolic_bias or nonlin is not None or bias is None or abs(float(k) + 1.0) > 1e-12:
-        raise NotImplementedError("mobius_linear: only hyperbolic_input=False, hyperbolic_bias=True, nonlin=None, k=-1 "
-                                  "(the configuration of models/tadgan.py:43-52) runs on the HIP path")
-    return _MobiusLinearFn.apply(input, weight, bias)
+    _check_k(k, "mobius_linear")
+    code = _nonlin_code(nonlin)
+    if weight.dim() != 2:
+        raise NotImplementedError(f"mobius_linear: a batched weight of {weight.dim()} dimensions is not implemented; {_SUPPORTED}")
+    if not hyperbolic_input and hyperbolic_bias and bias is not None and code == _C.NONLIN_NONE:
+        return _MobiusLinearFn.apply(input, weight, bias)        # the configuration of models/tadgan.py:43-52, as before
+    flags = (_C.ML_HYPER_INPUT if hyperbolic_input else 0) | (_C.ML_HYPER_BIAS if hyperbolic_bias else 0)
+    return _MobiusLinearExFn.apply(input, weight, bias, flags, code)
 
 
 def _expmap0_host(u):
@@ -84,7 +191,7 @@ class MobiusLinear(nn.Linear):
     def __init__(self, *args, hyperbolic_input=True, hyperbolic_bias=True, nonlin=None, k=-1.0, fp64_hyper=True, **kwargs):
         super().__init__(*args, **kwargs)
         if fp64_hyper:
-            raise NotImplementedError("fp64_hyper=True: the reference's hot path uses fp32 (models/tadgan.py:51)")
+            raise NotImplementedError(f"fp64_hyper=True: the reference's hot path uses fp32 (models/tadgan.py:51); {_SUPPORTED}")
         if self.bias is not None and hyperbolic_bias:
             self.ball = PoincareBall(c=abs(float(k)))
             with torch.no_grad():

@@ -91,6 +91,34 @@ int hypad_mobius_linear_bwd(const float* x, const float* weight, const float* bi
                             const float* grad_out, float* grad_x, float* grad_weight, float* grad_bias,
                             void* workspace, size_t workspace_bytes,
                             int64_t rows, int in_dim, int out_dim, hypad_stream_t stream);
+/* mobius_matvec  hyperspace/hyrnn_nets.py:38-58 (math_.py:1308-1323): out = M (x) x for ball-valued rows x (rows, in_dim) and
+ * weight M (out_dim, in_dim) -- tanh(|mx| / |x| artanh |x|) mx / |mx| with mx = x M^T, the zero row where mx is exactly zero.
+ * No bias, no non-linearity, no project.  mx_save (rows, out_dim) receives mx for the backward (may be NULL).
+ * bwd: grad_x and grad_weight may each be NULL; workspace: hypad_mobius_linear_ex_workspace_bytes(rows, out_dim).  rows == 0 as
+ * hypad_mobius_linear_bwd. */
+int hypad_mobius_matvec_fwd(const float* x, const float* weight, float* out, float* mx_save,
+                            int64_t rows, int in_dim, int out_dim, hypad_stream_t stream);
+int hypad_mobius_matvec_bwd(const float* x, const float* weight, const float* mx_saved, const float* grad_out,
+                            float* grad_x, float* grad_weight, void* workspace, size_t workspace_bytes,
+                            int64_t rows, int in_dim, int out_dim, hypad_stream_t stream);
+/* mobius_linear in every configuration  hyperspace/hyrnn_nets.py:13-35 (+ mobius_fn_apply math_.py:1431-1469):
+ *   flags & HYPAD_ML_HYPER_INPUT  x lies on the ball: mobius_matvec(weight, x) (:23-24); otherwise expmap0(x W^T) (:26-27)
+ *   bias (out_dim), NULL = none   on the ball with HYPAD_ML_HYPER_BIAS, otherwise Euclidean and mapped with expmap0 (:28-31)
+ *   nonlin                        expmap0(f(logmap0(.))) for f = tanh / relu (:32-33)
+ * then project (:34).  One forward launch; mx_save (rows, out_dim) = x W^T is all the backward keeps (may be NULL).
+ * The row chain after x W^T runs in fp64 registers (a row the matvec scaling leaves at 1 - 1e-5 has no digits of 1 - norm to
+ * spare in fp32); every buffer is fp32.  The same holds for hypad_mobius_matvec_*.
+ * bwd: grad_x, grad_weight and grad_bias may each be NULL (grad_bias must be NULL without a bias); every argument is validated
+ * before anything is launched.  rows == 0 as hypad_mobius_linear_bwd.  The same limits as hypad_mobius_linear_*. */
+enum { HYPAD_ML_HYPER_INPUT = 1, HYPAD_ML_HYPER_BIAS = 2 };
+enum { HYPAD_NONLIN_NONE = 0, HYPAD_NONLIN_TANH = 1, HYPAD_NONLIN_RELU = 2 };
+size_t hypad_mobius_linear_ex_workspace_bytes(int64_t rows, int out_dim);
+int hypad_mobius_linear_ex_fwd(const float* x, const float* weight, const float* bias, float* out, float* mx_save,
+                               int64_t rows, int in_dim, int out_dim, int flags, int nonlin, hypad_stream_t stream);
+int hypad_mobius_linear_ex_bwd(const float* x, const float* weight, const float* bias, const float* mx_saved,
+                               const float* grad_out, float* grad_x, float* grad_weight, float* grad_bias,
+                               void* workspace, size_t workspace_bytes,
+                               int64_t rows, int in_dim, int out_dim, int flags, int nonlin, hypad_stream_t stream);
 /* inline row-wise Poincare distance  train.py:226-230; utils/anomaly_detection_utils.py:58-66,167-175 */
 int hypad_poincare_rowdist_fwd(const float* u, const float* v, float* dist, int64_t rows, int dim, hypad_stream_t stream);
 int hypad_poincare_rowdist_bwd(const float* u, const float* v, const float* grad_dist, float* grad_u, float* grad_v,
