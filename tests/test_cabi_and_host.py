@@ -360,3 +360,92 @@ def test_error_kernels_refuse_score_windows_without_an_instantiation_before_any_
         assert lib.hypad_area_error(p, p, p, n64(40), sw, None) == EINVAL, sw
     assert lib.hypad_dtw_error(p, p, p, n64(-1), 10, None) == EINVAL and lib.hypad_area_error(p, p, None, n64(4), 10, None) == EINVAL
     assert lib.hypad_dtw_error(p, p, p, n64(0), 10, None) == OK and lib.hypad_area_error(p, p, p, n64(0), 10, None) == OK
+
+
+def test_statistics_entry_points_refuse_bad_arguments_before_any_launch(lib):
+    """No GPU needed (fake pointers): the rolling mean, the z-scores, the quantiles and their segmented copies return HYPAD_EINVAL,
+    HYPAD_EUNSUPPORTED or HYPAD_EWORKSPACE from their argument checks, which come before the first HIP call (on a machine without a
+    device anything later returns a HIP error code instead).  An empty series is HYPAD_OK for hypad_rolling_mean alone."""
+    buf = (ctypes.c_double * 4096)()
+    p, n64, sz, dbl = ctypes.cast(buf, ctypes.c_void_p), ctypes.c_int64, ctypes.c_size_t, ctypes.c_double
+    OK, EINVAL, EWORKSPACE, EUNSUPPORTED = 0, -1, -2, -3
+    big = 1 << 40
+    for name in ("hypad_rolling_workspace_bytes", "hypad_quantile_workspace_bytes", "hypad_critic_score_workspace_bytes", "hypad_quantiles_signals_workspace_bytes",
+                 "hypad_zscore_clip_signals_workspace_bytes", "hypad_critic_score_signals_workspace_bytes", "hypad_rec_scores_signals_workspace_bytes",
+                 "hypad_critic_chain_signals_workspace_bytes"):
+        getattr(lib, name).restype = sz
+    qs = lambda *v: (dbl * len(v))(*v)
+    offs = lambda *v: (n64 * len(v))(*v)
+    # hypad_rolling_mean(in, sub, out, t, window, origin, workspace, workspace_bytes, stream)
+    roll = lambda a=p, o=p, t=100, w=40, origin=0, ws=p, nb=big: lib.hypad_rolling_mean(a, None, o, n64(t), w, n64(origin), ws, sz(nb), None)
+    assert roll(a=None) == EINVAL and roll(o=None) == EINVAL and roll(t=-1) == EINVAL and roll(w=0) == EINVAL and roll(w=-3) == EINVAL and roll(origin=-1) == EINVAL
+    assert roll(t=0) == OK and roll(t=0, w=3, ws=None, nb=0) == OK and roll(t=0, ws=None, nb=0) == OK
+    need = lib.hypad_rolling_workspace_bytes(n64(100))
+    assert roll(ws=None) == EWORKSPACE and roll(nb=need - 1) == EWORKSPACE and roll(w=33, nb=need - 1) == EWORKSPACE
+    assert lib.hypad_rolling_workspace_bytes(n64(0)) == 0 and lib.hypad_rolling_workspace_bytes(n64(-5)) == 0
+    # ... whose workspace holds the chunk sums and counts of roll_counts(t, origin) at every origin: restated from the two shifts
+    for t in range(1, 601):
+        n1 = max(((o + t - 1) >> 4) - (o >> 4) + 1 for o in range(512))
+        n2 = max(((o + t - 1) >> 8) - (o >> 8) + 1 for o in range(512))
+        cap1, cap2 = t // 16 + 3, t // 256 + 3                # (the slots hypad_rolling_mean lays out: sums, then counts)
+        assert n1 <= cap1 and n2 <= cap2 and lib.hypad_rolling_workspace_bytes(n64(t)) >= (cap1 + cap2) * (8 + 4), t
+    # hypad_zscore_clip(in, out, t, ws, bytes, stream) / hypad_critic_zscore(in, q25, q75, out, t, ws, bytes, stream)
+    stats = 256 * 5 * 8
+    zs = lambda a=p, o=p, t=100, ws=p, nb=stats: lib.hypad_zscore_clip(a, o, n64(t), ws, sz(nb), None)
+    cz = lambda a=p, o=p, t=100, ws=p, nb=stats: lib.hypad_critic_zscore(a, dbl(-1.0), dbl(1.0), o, n64(t), ws, sz(nb), None)
+    for call in (zs, cz):
+        assert call(a=None) == EINVAL and call(o=None) == EINVAL and call(t=0) == EINVAL and call(t=-1) == EINVAL
+        assert call(ws=None) == EWORKSPACE and call(nb=stats - 1) == EWORKSPACE
+    # hypad_quantiles(in, n, q, nq, out, ws, bytes, stream)
+    qneed = lib.hypad_quantile_workspace_bytes()
+    qu = lambda a=p, n=100, q=qs(0.25, 0.75), nq=2, o=p, ws=p, nb=qneed: lib.hypad_quantiles(a, n64(n), q, nq, o, ws, sz(nb), None)
+    assert qu(a=None) == EINVAL and qu(q=None) == EINVAL and qu(o=None) == EINVAL and qu(n=0) == EINVAL and qu(n=-1) == EINVAL and qu(nq=0) == EINVAL
+    for bad in (-1e-9, 1.0 + 1e-9, float("nan"), float("inf")):
+        assert qu(q=qs(0.5, bad)) == EINVAL and qu(q=qs(bad), nq=1) == EINVAL, bad
+    assert qu(q=qs(0.1, 0.2, 0.3), nq=3) == EUNSUPPORTED and qu(n=(1 << 31) + 1) == EUNSUPPORTED
+    assert qu(ws=None) == EWORKSPACE and qu(nb=qneed - 1) == EWORKSPACE
+    # hypad_critic_score(in, out, t, ws, bytes, stream)
+    cneed = lib.hypad_critic_score_workspace_bytes()
+    assert cneed == 64 + stats + qneed
+    cs = lambda a=p, o=p, t=100, ws=p, nb=cneed: lib.hypad_critic_score(a, o, n64(t), ws, sz(nb), None)
+    assert cs(a=None) == EINVAL and cs(o=None) == EINVAL and cs(t=0) == EINVAL and cs(t=(1 << 31) + 1) == EUNSUPPORTED
+    assert cs(ws=None) == EWORKSPACE and cs(nb=cneed - 1) == EWORKSPACE
+    # the segmented copies: the offsets first (n_signals < 1, NULL, a first offset that is not 0, an empty segment)
+    ro, W = offs(0, 120, 300), 10
+    bad_tables = ((0, ro), (2, None), (2, offs(1, 120, 300)), (2, offs(0, 120, 120)))
+    # hypad_quantiles_signals(in, n_signals, row_off, window, q, nq, out, ws, bytes, stream)
+    sneed = lib.hypad_quantiles_signals_workspace_bytes(2)
+    assert lib.hypad_quantiles_signals_workspace_bytes(0) == 0 and sneed > 0
+    qss = lambda a=p, k=2, r=ro, w=W, q=qs(0.25, 0.75), nq=2, o=p, ws=p, nb=sneed: lib.hypad_quantiles_signals(a, k, r, w, q, nq, o, ws, sz(nb), None)
+    assert all(qss(k=k, r=r) == EINVAL for k, r in bad_tables)
+    assert qss(a=None) == EINVAL and qss(q=None) == EINVAL and qss(o=None) == EINVAL and qss(w=0) == EINVAL and qss(nq=0) == EINVAL and qss(q=qs(0.5, 1.5)) == EINVAL
+    assert qss(q=qs(0.1, 0.2, 0.3), nq=3) == EUNSUPPORTED and qss(r=offs(0, 120, 121 + (1 << 31))) == EUNSUPPORTED
+    assert qss(ws=None) == EWORKSPACE and qss(nb=sneed - 1) == EWORKSPACE
+    # hypad_zscore_clip_signals(in, out, n_signals, seg_off, ws, bytes, stream)
+    zneed = lib.hypad_zscore_clip_signals_workspace_bytes(2)
+    assert zneed == 2 * stats and lib.hypad_zscore_clip_signals_workspace_bytes(0) == 0
+    zss = lambda a=p, o=p, k=2, r=ro, ws=p, nb=zneed: lib.hypad_zscore_clip_signals(a, o, k, r, ws, sz(nb), None)
+    assert all(zss(k=k, r=r) == EINVAL for k, r in bad_tables) and zss(a=None) == EINVAL and zss(o=None) == EINVAL
+    assert zss(ws=None) == EWORKSPACE and zss(nb=zneed - 1) == EWORKSPACE
+    # hypad_critic_score_signals(modes, out, n_signals, row_off, window, ws, bytes, stream)
+    csneed = lib.hypad_critic_score_signals_workspace_bytes(2, ro, W)
+    assert csneed > cneed and lib.hypad_critic_score_signals_workspace_bytes(2, ro, 0) == 0 and lib.hypad_critic_score_signals_workspace_bytes(0, ro, W) == 0
+    css = lambda a=p, o=p, k=2, r=ro, w=W, ws=p, nb=csneed: lib.hypad_critic_score_signals(a, o, k, r, w, ws, sz(nb), None)
+    assert all(css(k=k, r=r) == EINVAL for k, r in bad_tables) and css(a=None) == EINVAL and css(o=None) == EINVAL and css(w=0) == EINVAL
+    assert css(ws=None) == EWORKSPACE and css(nb=csneed - 1) == EWORKSPACE
+    # hypad_rec_scores_signals(kinds, true, median, out_point, out_area, out_dtw, n_signals, row_off, window, score_window, ws, bytes, stream)
+    rneed = lib.hypad_rec_scores_signals_workspace_bytes(2, ro, W)
+    assert rneed > 0 and lib.hypad_rec_scores_signals_workspace_bytes(2, ro, 0) == 0
+    rss = lambda kinds=7, y=p, m=p, op=p, oa=p, od=p, k=2, r=ro, w=W, sw=10, ws=p, nb=rneed: lib.hypad_rec_scores_signals(kinds, y, m, op, oa, od, k, r, w, sw, ws, sz(nb), None)
+    assert all(rss(k=k, r=r) == EINVAL for k, r in bad_tables)
+    assert rss(kinds=0) == EINVAL and rss(kinds=8) == EINVAL and rss(y=None) == EINVAL and rss(m=None) == EINVAL and rss(w=0) == EINVAL
+    assert rss(op=None) == EINVAL and rss(oa=None) == EINVAL and rss(od=None) == EINVAL and rss(kinds=1, oa=None, od=None, sw=0, nb=0, ws=None) == EWORKSPACE
+    assert rss(sw=1) == EINVAL and rss(kinds=2, sw=1) == EINVAL and rss(sw=12) == EUNSUPPORTED and rss(kinds=3, sw=12, nb=rneed - 1) == EWORKSPACE
+    assert rss(ws=None) == EWORKSPACE and rss(nb=rneed - 1) == EWORKSPACE
+    # hypad_critic_chain_signals(critic, modes_out, out, n_signals, row_off, window, ws, bytes, stream)
+    chneed = lib.hypad_critic_chain_signals_workspace_bytes(2, ro, W)
+    assert chneed > 0 and lib.hypad_critic_chain_signals_workspace_bytes(2, ro, 0) == 0
+    chs = lambda a=p, mo=None, o=p, k=2, r=ro, w=W, ws=p, nb=chneed: lib.hypad_critic_chain_signals(a, mo, o, k, r, w, ws, sz(nb), None)
+    assert all(chs(k=k, r=r) == EINVAL for k, r in bad_tables) and chs(a=None) == EINVAL and chs(o=None) == EINVAL and chs(w=0) == EINVAL
+    assert chs(w=257) == EUNSUPPORTED and chs(r=offs(0, 120, 121 + (1 << 31))) == EUNSUPPORTED
+    assert chs(ws=None) == EWORKSPACE and chs(nb=chneed - 1) == EWORKSPACE and chs(mo=p, nb=chneed - 1) == EWORKSPACE
