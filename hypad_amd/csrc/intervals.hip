@@ -301,6 +301,13 @@ __global__ __launch_bounds__(BT) void fa_window_kernel(const double* __restrict_
   const int keep = last + 1;
   // 6. _compute_scores :1240-1269, into the item's (dead) list arrays
   const double denom = st.mean + st.sd;
+  // A covered window is one run (0, L - 1), and its sentinel is (-1, -1, 0).  The reference's stable sort (:1196-1199) puts the sentinel
+  // in front of a run whose maximum is <= 0; (0 - max) / 0 is +inf or NaN, never below min_percent, so the prune keeps exactly the
+  // sentinel's row and drops the run behind it.
+  if (!any && !(undkey(~a[0]) > 0.0)) {
+    if (tid == 0) { pos[0] = (int)w.start - 1; rid[0] = (int)w.start - 1; lv[0] = (0.0 - thr) / denom; *icnt = clipped ? -2 : 1; }
+    return;
+  }
   for (int i = tid; i < keep; i += BT) {
     const int r = (int)b[i];
     pos[i] = rs[r] + (int)w.start;
@@ -354,7 +361,8 @@ __global__ __launch_bounds__(BT) void fa_merge_kernel(char* __restrict__ ws, FaT
   const int P = (int)pow2ceil(C);
   u64* a = P <= LDS_SORT ? s_a : (u64*)(base + l.g_sa);
   unsigned* b = P <= LDS_SORT ? s_b : (unsigned*)(base + l.g_sb);
-  for (int j = tid; j < P; j += BT) { a[j] = j < C ? (u64)gs[j] : ~0ULL; b[j] = j < C ? (unsigned)j : ~0u; }
+  // (the key is start + 1: the sentinel's row of a signal's first window starts at -1)
+  for (int j = tid; j < P; j += BT) { a[j] = j < C ? (u64)(gs[j] + 1LL) : ~0ULL; b[j] = j < C ? (unsigned)j : ~0u; }
   bitonic_sort(a, b, P);
   // a row opens a group when it starts beyond the largest stop so far + 1 (:1296)
   long long far = -1, groups = 0;
@@ -362,7 +370,7 @@ __global__ __launch_bounds__(BT) void fa_merge_kernel(char* __restrict__ ws, FaT
     const int j = b0 + tid;
     const bool in_l = j < C;
     const long long before = block_scan(in_l && j > 0 ? (long long)ge[b[j - 1]] : -1LL, OpMax(), s_scan, far);
-    const bool first = in_l && (j == 0 || (long long)a[j] > before + 1);
+    const bool first = in_l && (j == 0 || (long long)a[j] - 1 > before + 1);
     const long long incl = block_scan(first ? 1LL : 0LL, OpSum(), s_scan, groups);
     if (first) gfirst[incl - 1] = j;
   }

@@ -664,7 +664,9 @@ def find_anomalies_signals(scores, seg_off, index_list=None, window_size_portion
     device; ``seg_off``: the host offsets of the signals' segments in it -- ``row_off`` for hyperbolic results, ``t_off`` for Euclidean
     ones.  ``window_size`` / ``window_step_size``: one value or one per signal; the portions give each signal's own
     int(np.ceil(n * portion)) as find_anomalies computes them.  ``index_list``: per signal the index its positions are looked up in
-    (None: the positions themselves).  ``capacity``: table rows per signal of the first attempt; a signal with more intervals makes
+    (None: the positions themselves).  A window covered entirely by one padded run whose maximum is not positive reports the
+    reference's sentinel row instead, at position window_start - 1; for a signal's first window that is -1, which the lookup reads
+    as index[-1] exactly as find_anomalies does.  ``capacity``: table rows per signal of the first attempt; a signal with more intervals makes
     the call run once more with room for the largest count.
     Returns a list of (n_i, 3) float64 arrays [index[start], index[stop], score], one per signal: interval bounds equal
     find_anomalies', scores up to the order of the fp64 sums.  Raises ZeroDivisionError where find_anomalies does (touching

@@ -87,6 +87,20 @@ def test_argument_errors():
             _C.check(rc, "find_anomalies_signals")
 
 
+def test_unsupported_sizes_are_refused_by_the_bytes_function_and_by_the_call():
+    # a segment beyond 32-bit positions, and a window of more than 65 535 reduction chunks (the grid's y extent): no workspace size
+    # (nothing to allocate), HYPAD_EUNSUPPORTED from the call before any launch
+    chunk = 4096
+    for off, size, step in (((0, (1 << 31)), (5,), (5,)), ((0, 700, 700 + (1 << 31)), (231, 5), (24, 5)),
+                            ((0, 65536 * chunk), (65536 * chunk,), (chunk,)), ((0, 65536 * chunk + 9), (65535 * chunk + 1,), (7,))):
+        for lower in (0, 1):
+            assert _bytes(off, size, step, lower) == 0
+            assert _call(off=off, size=size, step=step, lower=lower) == EUNSUPPORTED
+    assert _bytes((0, (1 << 31) - 1), (5,), (1 << 30,)) > 0                           # INT_MAX values are positions still
+    assert _bytes((0, 65536 * chunk), (65535 * chunk,), (65535 * chunk,)) > 0        # 65 535 chunks are a grid still
+    assert _call(capacity=-3) == EINVAL and _call(pad=-(1 << 40)) == EINVAL           # (beside capacity 0 and padding -1 above)
+
+
 def test_workspace_grows_with_the_group():
     prev = 0
     for n in (1, 2, 5, 32, 64, 65, 70, 130):

@@ -15,72 +15,9 @@ import pytest
 import torch
 
 from helpers import csv_signals, load
+from intervals_ref import RTOL, _sizes, check_precondition, host, series
 
 pytestmark = pytest.mark.gpu
-
-RTOL = 1e-9
-GAP = 1e-6
-
-
-def series(n, spikes, width, seed, plateau=False):
-    """Noise plus spikes, as tests/golden/gen_fixtures.py makes the interval fixtures."""
-    r = np.random.default_rng(seed)
-    e = 1.0 + 0.1 * np.abs(r.standard_normal(n))
-    for k in range(spikes):
-        c = int(r.integers(0, n))
-        w = int(r.integers(1, width + 1))
-        e[c: c + w] += r.uniform(0.8, 3.0) if not plateau else 2.0
-    return e
-
-
-def _sizes(n, kw):
-    size = kw.get("window_size") or n
-    if kw.get("window_size_portion"):
-        size = int(np.ceil(n * kw["window_size_portion"]))
-    step = kw.get("window_step_size") or size
-    if kw.get("window_step_size_portion"):
-        step = int(np.ceil(size * kw["window_step_size_portion"]))
-    return size, step
-
-
-def _windows(e, kw):
-    size, step = _sizes(e.size, kw)
-    start = end = 0
-    while end < e.size:
-        end = start + size
-        w = e[start:end]
-        yield w
-        if kw.get("lower_threshold"):
-            yield w.mean() - (w - w.mean())
-        start += step
-
-
-def check_precondition(e, kw):
-    """No value within GAP (relative) of its window's threshold, no prune ratio within GAP of min_percent.  A window with a NaN has
-    no threshold (nothing to be near to); an exactly constant window of an integer value sums exactly in any order, so its mean is
-    that value and its standard deviation 0 on both sides -- nothing lies above the threshold, which equals the value."""
-    from hypad_amd.utils import intervals as iv
-    e = np.asarray(e, dtype=np.float64)
-    minp, pad = kw.get("min_percent", 0.1), kw.get("anomaly_padding", 50)
-    for w in _windows(e, kw):
-        if w.size == 0 or np.isnan(w).any():
-            continue
-        if (w == w[0]).all():
-            assert w[0] == np.round(w[0]) and abs(w[0]) * w.size < 2.0 ** 53
-            continue
-        thr = iv._fixed_threshold(w)
-        assert np.abs(w - thr).min() > GAP * abs(thr), ("threshold gap", np.abs(w - thr).min() / abs(thr))
-        seqs, below = iv._find_sequences(w, thr, pad)
-        me = iv._get_max_errors(w, seqs, below)[:, 2]
-        if me.size > 1:
-            ratio = (me[:-1] - me[1:]) / me[:-1]
-            assert np.abs(ratio - minp).min() > GAP, ("prune gap", np.abs(ratio - minp).min())
-
-
-def host(e, kw, index=None):
-    from hypad_amd.utils import intervals as iv
-    index = np.arange(e.size) if index is None else index
-    return np.asarray(iv.find_anomalies(e, index, **dict(kw, fixed_threshold=True)), dtype=np.float64).reshape(-1, 3)
 
 
 def device(segs, kw, index_list=None, seg_off=None, scores=None, **extra):
