@@ -47,6 +47,7 @@ NET_ENCODER, NET_DECODER, NET_CRITIC_X, NET_CRITIC_Z = 0, 1, 2, 3
 ACT_NONE, ACT_TANH, ACT_LEAKY02 = 0, 1, 2
 ML_HYPER_INPUT, ML_HYPER_BIAS = 1, 2                # HYPAD_ML_*
 NONLIN_NONE, NONLIN_TANH, NONLIN_RELU = 0, 1, 2    # HYPAD_NONLIN_*
+D2P_SIGNED, D2P_SCALED = 1, 2                       # HYPAD_D2P_*
 COMB = {"sum": 0, "mult": 1, "uncertainty": 2, "critic": 3, "critic_uncertainty": 4, "sum_uncertainty": 5, "rec": 6,
         "rec_uncertainty": 7, "eucl_mult": 8, "eucl_sum": 9}
 
@@ -127,6 +128,9 @@ _SIGS = {
     "hypad_mobius_linear_ex_workspace_bytes": (c_size_t, [c_int64, c_int]),
     "hypad_mobius_linear_ex_fwd": (c_int, [P, P, P, P, P, c_int64, c_int, c_int, c_int, c_int, P]),
     "hypad_mobius_linear_ex_bwd": (c_int, [P, P, P, P, P, P, P, P, P, c_size_t, c_int64, c_int, c_int, c_int, c_int, P]),
+    "hypad_dist2plane_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "hypad_dist2plane_fwd": (c_int, [P, P, P, P, P, c_int64, c_int, c_int, c_int, P]),
+    "hypad_dist2plane_bwd": (c_int, [P, P, P, P, P, P, P, P, P, P, P, c_size_t, c_int64, c_int, c_int, c_int, P]),
     "hypad_poincare_rowdist_fwd": (c_int, [P, P, P, c_int64, c_int, P]),
     "hypad_poincare_rowdist_bwd": (c_int, [P, P, P, P, P, c_int64, c_int, P]),
     "hypad_hyper_loss_fwd": (c_int, [P, P, P, c_int64, c_int, c_int, P]),

@@ -4,6 +4,7 @@ Drop-in for the geoopt functions the reference's hot path reaches through
 ``geoopt.manifolds.stereographic.math`` (vendored at /root/reference/math_.py): expmap0 (:1132-1136),
 logmap0 (:1267-1270), mobius_add (:536-555), project (:340-352), plus the inline row-wise distance of
 train.py:226-230 and the hyperbolic loss of train.py:232.  Each is one HIP kernel forward and one backward.
+dist2plane (:1599-1666) is the function behind hyrnn_nets.MobiusDist2Hyperplane: one HIP launch forward, a HIP backward.
 """
 import torch
 
@@ -112,6 +113,65 @@ def mobius_matvec(m, x, *, k=None, dim=-1):
     """math_.py:1308-1323: see hyrnn_nets.mobius_matvec (one HIP launch, differentiable in m and x)."""
     from .hyrnn_nets import mobius_matvec as _matvec
     return _matvec(m, x, k=-1.0 if k is None else k, dim=dim)
+
+
+class _Dist2Plane(torch.autograd.Function):
+    """hypad_dist2plane_*: x (..., K) against p, a (N, K) -> (..., N), times exp(log_scale) (N) inside the kernel where given.
+    Nothing but the operands is saved: the backward recomputes the two products."""
+
+    @staticmethod
+    def forward(ctx, x, p, a, log_scale, flags):
+        x, x2 = _rows(x)
+        p = _C.require_cuda(p.contiguous(), "p")
+        a = _C.require_cuda(a.contiguous(), "a")
+        ls = None if log_scale is None else _C.require_cuda(log_scale.contiguous(), "log_scale")
+        rows, k, n = x2.shape[0], x2.shape[1], p.shape[0]
+        out = torch.empty(rows, n, device=x.device, dtype=torch.float32)
+        _C.check(_C.lib.hypad_dist2plane_fwd(_C.ptr(x2), _C.ptr(p), _C.ptr(a), _C.ptr(ls), _C.ptr(out), rows, k, n, flags, _C.stream()),
+                 "dist2plane_fwd")
+        ctx.save_for_backward(x2, p, a, *(() if ls is None else (ls,)))
+        ctx.xshape, ctx.flags = x.shape, flags
+        return out.view(*x.shape[:-1], n)
+
+    @staticmethod
+    @_C.first_order_only
+    def backward(ctx, go):
+        x2, p, a, *rest = ctx.saved_tensors
+        ls = rest[0] if rest else None
+        rows, k, n = x2.shape[0], x2.shape[1], p.shape[0]
+        go2 = go.to(torch.float32).contiguous().reshape(rows, n)
+        need = ctx.needs_input_grad
+        gx = torch.empty_like(x2) if need[0] else None
+        gp = torch.empty_like(p) if need[1] else None
+        ga = torch.empty_like(a) if need[2] else None
+        gs = torch.empty_like(ls) if ls is not None and need[3] else None
+        nbytes = _C.lib.hypad_dist2plane_workspace_bytes(rows, k, n)
+        ws = torch.empty(max(nbytes // 4, 1), device=x2.device, dtype=torch.float32)
+        _C.check(_C.lib.hypad_dist2plane_bwd(_C.ptr(x2), _C.ptr(p), _C.ptr(a), _C.ptr(ls), None, _C.ptr(go2), _C.ptr(gx), _C.ptr(gp),
+                                             _C.ptr(ga), _C.ptr(gs), _C.ptr(ws), nbytes, rows, k, n, ctx.flags, _C.stream()), "dist2plane_bwd")
+        return None if gx is None else gx.view(ctx.xshape), gp, ga, gs, None
+
+
+_D2P_SUPPORTED = ("supported: k = -1, dim = -1, fp32, x of shape (..., 1, K) against 2-D p and a of shape (N, K) (the layer's calling "
+                  "pattern, hyperspace/hyrnn_nets.py:233-236), K <= 256")
+
+
+def dist2plane(x, p, a, *, k=None, keepdim=False, signed=False, scaled=False, dim=-1):
+    """Geodesic distance of x to the hyperplanes through p with normals a (math_.py:1599-1666) at k = -1, for the layer's calling
+    pattern: x (..., 1, K) against p, a (N, K) -> (..., N), or (..., N, 1) with keepdim.  One HIP launch forward; first-order
+    differentiable in x, p and a."""
+    if k is not None and abs(float(k) + 1.0) > 1e-12:
+        raise NotImplementedError(f"dist2plane: curvature k = {float(k)} is not implemented; {_D2P_SUPPORTED}")
+    if dim != -1 and dim != x.dim() - 1:
+        raise NotImplementedError(f"dist2plane: dim = {dim} is not implemented; {_D2P_SUPPORTED}")
+    if (p.dim() != 2 or a.shape != p.shape or x.dim() < 2 or x.shape[-2] != 1 or x.shape[-1] != p.shape[-1]):
+        raise NotImplementedError(f"dist2plane: x {tuple(x.shape)} against p {tuple(p.shape)} and a {tuple(a.shape)} is not implemented; "
+                                  f"{_D2P_SUPPORTED}")
+    if p.shape[-1] > 256:
+        raise NotImplementedError(f"dist2plane: K = {p.shape[-1]} is not implemented; {_D2P_SUPPORTED}")
+    flags = (_C.D2P_SIGNED if signed else 0) | (_C.D2P_SCALED if scaled else 0)
+    out = _Dist2Plane.apply(x.squeeze(-2), p, a, None, flags)
+    return out.unsqueeze(-1) if keepdim else out
 
 
 class _RowDist(torch.autograd.Function):

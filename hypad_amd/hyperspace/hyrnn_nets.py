@@ -1,4 +1,5 @@
-"""MobiusLinear / mobius_linear / mobius_matvec on the GPU (reference: hyperspace/hyrnn_nets.py:13-58, :154-200).
+"""MobiusLinear / mobius_linear / mobius_matvec and MobiusDist2Hyperplane on the GPU (reference: hyperspace/hyrnn_nets.py:13-58,
+:154-200, :210-245).
 
 Every configuration of the layer runs as one fused HIP forward launch and a HIP backward: Euclidean or ball-valued
 input (the latter through the Moebius matrix-vector product), ball-valued, Euclidean or no bias, and no
@@ -19,6 +20,10 @@ class PoincareBall:
     def __init__(self, c=1.0):
         self.c = torch.tensor(float(c))
         self.k = -self.c
+
+
+class Sphere:
+    """Marker for unit-norm parameter rows (the reference's geoopt.manifolds.Sphere(): hyrnn_nets.py:217)."""
 
 
 class ManifoldParameter(nn.Parameter):
@@ -207,3 +212,38 @@ class MobiusLinear(nn.Linear):
     def forward(self, input):
         return mobius_linear(input.float(), weight=self.weight, bias=self.bias, hyperbolic_input=self.hyperbolic_input,
                              nonlin=self.nonlin, hyperbolic_bias=self.hyperbolic_bias, k=float(self.k))
+
+
+class MobiusDist2Hyperplane(nn.Module):
+    """The hyperbolic read-out layer (reference: hyperspace/hyrnn_nets.py:210-245): the signed geodesic distance of every ball-valued
+    input row to ``out_features`` hyperplanes of the ball -- through ``point`` with normal ``tangent`` -- times ``exp(scale)``; the
+    counterpart of the logits of an nn.Linear.  One fused HIP launch forward and a HIP backward, ``scale`` inside the kernel.
+
+    Curvature: k = -1, the Poincare ball.  The reference's module passes ``k=self.ball.c`` = +1 to dist2plane, a call written for an
+    older geoopt whose argument was ``c``; with the vendored math_.py that selects the spherical formulas, which is not what a layer
+    of the ball means.  This layer computes k = -1 and accepts no other k.
+
+    ``point`` and ``tangent`` are tagged ManifoldParameters (ball / Sphere), as in the reference.  hypad_amd.optim.RiemannianAdam does
+    not know how to update them yet and refuses them; the layer trains with Euclidean optimisers (torch.optim.SGD / Adam) meanwhile.
+    """
+
+    def __init__(self, in_features, out_features, k=-1.0, fp64_hyper=False):
+        super().__init__()
+        _check_k(k, "MobiusDist2Hyperplane")
+        if fp64_hyper:
+            raise NotImplementedError(f"fp64_hyper=True: the HIP kernels are fp32; {_SUPPORTED}")
+        self.in_features, self.out_features, self.fp64_hyper = in_features, out_features, fp64_hyper
+        self.ball, self.sphere = PoincareBall(c=abs(float(k))), Sphere()
+        self.scale = nn.Parameter(torch.zeros(out_features))
+        point = _expmap0_host(torch.randn(out_features, in_features) / 4)                # hyrnn_nets.py:219-220
+        tangent = torch.randn(out_features, in_features)
+        tangent = tangent / tangent.norm(dim=-1, keepdim=True)                           # Sphere.proj_ (:225)
+        self.point = ManifoldParameter(point, manifold=self.ball)
+        self.tangent = ManifoldParameter(tangent, manifold=self.sphere)
+
+    def forward(self, input):
+        from .gmath import _Dist2Plane
+        return _Dist2Plane.apply(input.float(), self.point, self.tangent, self.scale, _C.D2P_SIGNED)
+
+    def extra_repr(self):
+        return f"in_features={self.in_features}, out_features={self.out_features}"

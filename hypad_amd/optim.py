@@ -15,6 +15,19 @@ def _is_ball(p):
     return getattr(p, "manifold", None) is not None
 
 
+def _check_ball_vector(p):
+    """The Riemannian step (hypad_radam_step) updates a tagged parameter as ONE point of the ball with numel coordinates.  That is
+    right for the 1-D ball biases of MobiusLinear and wrong for anything else -- MobiusDist2Hyperplane's ``point`` is out_features
+    points, its ``tangent`` lies on a sphere -- so anything else is refused, not silently updated as one vector."""
+    if not _is_ball(p):
+        return
+    from .hyperspace.hyrnn_nets import PoincareBall
+    if p.dim() != 1 or not isinstance(p.manifold, PoincareBall):
+        raise NotImplementedError(f"RiemannianAdam: a {type(p.manifold).__name__} parameter of shape {tuple(p.shape)} has no Riemannian update "
+                                  "yet (supported: 1-D PoincareBall vectors); train MobiusDist2Hyperplane's point / tangent with a "
+                                  "Euclidean optimiser (torch.optim.SGD / Adam, hypad_amd.optim.Adam)")
+
+
 class _Base(torch.optim.Optimizer):
     riemannian = False
 
@@ -38,6 +51,8 @@ class _Base(torch.optim.Optimizer):
             for p in group["params"]:
                 if p.grad is None:
                     continue
+                if self.riemannian:
+                    _check_ball_vector(p)
                 _C.require_cuda(p.data, "parameter")
                 g = _C.require_cuda(p.grad.contiguous(), "gradient")
                 st = self._state(p)

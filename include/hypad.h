@@ -119,6 +119,25 @@ int hypad_mobius_linear_ex_bwd(const float* x, const float* weight, const float*
                                const float* grad_out, float* grad_x, float* grad_weight, float* grad_bias,
                                void* workspace, size_t workspace_bytes,
                                int64_t rows, int in_dim, int out_dim, int flags, int nonlin, hypad_stream_t stream);
+/* MobiusDist2Hyperplane / dist2plane  hyperspace/hyrnn_nets.py:210-245, math_.py:1645-1666 (_mobius_add :537-555, arsin_k :266-290)
+ * at k = -1: out (rows, out_dim) = the geodesic distance of every ball-valued row of x (rows, in_dim) to the out_dim hyperplanes of
+ * the ball through the points p (out_dim, in_dim) with the normals a (out_dim, in_dim),
+ *   asinh(2 s' / clamp_abs((1 - |(-p) (+) x|^2) |a|)),  s' = <(-p) (+) x, a> with HYPAD_D2P_SIGNED, its absolute value without,
+ * times |a| with HYPAD_D2P_SCALED, times exp(log_scale[n]) where log_scale (out_dim) is given (NULL: none; the layer's `scale`,
+ * hyrnn_nets.py:237).  One launch; nothing is saved for the backward.
+ * bwd: `out` is the forward's result (may be NULL: the backward recomputes what it needs); grad_x, grad_p, grad_a and grad_log_scale
+ * may each be NULL (grad_log_scale must be NULL without a log_scale).  Sums over rows are added in a fixed order: two runs give the
+ * same bits.  rows == 0 writes zero parameter gradients.  Every argument is validated before anything is launched: HYPAD_EINVAL for
+ * a NULL operand, a non-positive size or an unknown flag, HYPAD_EUNSUPPORTED for in_dim > 256 (bwd: also where
+ * hypad_linear_act_bwd refuses out_dim' = 2 out_dim), HYPAD_EWORKSPACE below hypad_dist2plane_workspace_bytes. */
+enum { HYPAD_D2P_SIGNED = 1, HYPAD_D2P_SCALED = 2 };
+size_t hypad_dist2plane_workspace_bytes(int64_t rows, int in_dim, int out_dim);
+int hypad_dist2plane_fwd(const float* x, const float* p, const float* a, const float* log_scale /* NULL: none */, float* out,
+                         int64_t rows, int in_dim, int out_dim, int flags, hypad_stream_t stream);
+int hypad_dist2plane_bwd(const float* x, const float* p, const float* a, const float* log_scale, const float* out,
+                         const float* grad_out, float* grad_x, float* grad_p, float* grad_a, float* grad_log_scale,
+                         void* workspace, size_t workspace_bytes,
+                         int64_t rows, int in_dim, int out_dim, int flags, hypad_stream_t stream);
 /* inline row-wise Poincare distance  train.py:226-230; utils/anomaly_detection_utils.py:58-66,167-175 */
 int hypad_poincare_rowdist_fwd(const float* u, const float* v, float* dist, int64_t rows, int dim, hypad_stream_t stream);
 int hypad_poincare_rowdist_bwd(const float* u, const float* v, const float* grad_dist, float* grad_u, float* grad_v,
