@@ -428,6 +428,11 @@ __device__ __forceinline__ float rowdist_row_bwd(const R& u, const R& v, float g
 int mobius_chain_bwd_launch(const float* x, const float* mx, const float* bias, const float* go, float* gmx, float* gb_rows, float* gxn,
                             int64_t rows, int K, int N, bool hyper_in, bool hyper_bias, int nonlin, int project, void* stream);
 int norm_grad_add_launch(const float* x, const float* gxn, float* gx, int64_t rows, int K, void* stream);
+// lstm_t1_lds.hip, for hypad_lstm_bidir_fwd (the same arguments, checked by the caller): the weights-stationary forwards of the T = 1
+// bidirectional LSTM layer.  An error code; or HYPAD_OK with *launched true: the layer ran; or HYPAD_OK with *launched false: not a
+// shape of these kernels (fewer than 2 048 rows, hidden > 64, input > 128), nothing was launched and the caller runs the streamed form.
+int lstm_t1_lds_launch(const float* x, const float* wf, const float* bif, const float* bhf, const float* wr, const float* bir,
+                       const float* bhr, float* out, float* gates_save, int64_t rows, int K, int H, void* stream, bool* launched);
 
 // f(integral_constant<int, EPL>) with the 16-lanes-per-row EPL that fits `dim` (wave-uniform branch)
 template <class F>

@@ -232,6 +232,18 @@ def test_shared_kernel_bodies_are_included_by_two_kernels():
     assert all(len(k) >= 2 for k in users.values()), {f: sorted(k) for f, k in users.items() if len(k) < 2}
 
 
+def test_every_translation_unit_is_built():
+    """The weights-stationary T = 1 LSTM forwards have their own file (csrc/lstm_t1_lds.hip), which hypad_lstm_bidir_fwd of
+    ops_dense.hip calls into: it is in the product library's source list, and so is every other csrc/*.hip but the development
+    library's diag.hip (a file left out would only show as an undefined symbol when the library is loaded)."""
+    import glob
+    from hypad_amd import build
+    assert "lstm_t1_lds.hip" in build.SOURCES
+    on_disk = {os.path.basename(p) for p in glob.glob(os.path.join(ROOT, "hypad_amd", "csrc", "*.hip"))}
+    assert on_disk - {"diag.hip"} == {s for s in build.SOURCES if s.endswith(".hip")}
+    assert on_disk == {s for s in build.DEV_SOURCES if s.endswith(".hip")}
+
+
 def test_no_scratch_in_the_kernels_the_baseline_configs_run():
     """Code-object metadata of the built gfx950 objects (hypad_amd.build.kernel_metadata: the notes hipcc wrote): the kernels the BASELINE
     configs launch -- every compile-time instantiation of configs[0..2]'s shape (window 100, latent 20, batch 64), the generator / dW / scoring
