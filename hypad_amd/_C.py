@@ -131,6 +131,11 @@ _SIGS = {
     "hypad_dist2plane_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
     "hypad_dist2plane_fwd": (c_int, [P, P, P, P, P, c_int64, c_int, c_int, c_int, P]),
     "hypad_dist2plane_bwd": (c_int, [P, P, P, P, P, P, P, P, P, P, P, c_size_t, c_int64, c_int, c_int, c_int, P]),
+    "hypad_mobius_pointwise_mul_fwd": (c_int, [P, P, P, c_int64, c_int, c_int64, P]),
+    "hypad_mobius_pointwise_mul_bwd": (c_int, [P, P, P, P, P, c_int64, c_int, c_int64, P]),
+    "hypad_mobius_gru_workspace_bytes": (c_size_t, [c_int, c_int64, c_int, c_int]),
+    "hypad_mobius_gru_fwd": (c_int, [P] * 7 + [c_void_p, c_size_t, c_int, c_int64, c_int, c_int, c_int, P]),
+    "hypad_mobius_gru_bwd": (c_int, [P] * 14 + [c_void_p, c_size_t, c_int, c_int64, c_int, c_int, c_int, P]),
     "hypad_poincare_rowdist_fwd": (c_int, [P, P, P, c_int64, c_int, P]),
     "hypad_poincare_rowdist_bwd": (c_int, [P, P, P, P, P, c_int64, c_int, P]),
     "hypad_hyper_loss_fwd": (c_int, [P, P, P, c_int64, c_int, c_int, P]),

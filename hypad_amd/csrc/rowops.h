@@ -307,11 +307,12 @@ __device__ __forceinline__ bool rowd_all_zero(const R& a) {
   HYPAD_ROW_EACH nz += a.v[e] != 0.0 ? 1.0 : 0.0;
   return groupd_sum<R::G>(nz) == 0.0;
 }
+// The scaling the matvec and the point-wise product share: tanh(|m| / |x| artanh |x|) m / |m|; `zero` = the reference's `cond`.
 template <class R>
-__device__ __forceinline__ R mobius_matvec_row(const R& mx, double xraw) {
+__device__ __forceinline__ R mobius_scaled_row(const R& mx, double xraw, bool zero) {
   const double xn = fmax(xraw, (double)MIN_NORM);
   const double mn = fmax(sqrt(rowd_dot(mx, mx)), (double)MIN_NORM);
-  const double s = rowd_all_zero(mx) ? 0.0 : tanh_clamped_d(mn / xn * artanh_clamped_d(xn)) / mn;
+  const double s = zero ? 0.0 : tanh_clamped_d(mn / xn * artanh_clamped_d(xn)) / mn;
   R o;
 #pragma unroll
   HYPAD_ROW_EACH o.v[e] = s * mx.v[e];
@@ -319,13 +320,12 @@ __device__ __forceinline__ R mobius_matvec_row(const R& mx, double xraw) {
 }
 // d mx and (returned) dL/d|x|
 template <class R>
-__device__ __forceinline__ double mobius_matvec_row_bwd(const R& mx, double xraw, const R& go, R& dmx) {
+__device__ __forceinline__ double mobius_scaled_row_bwd(const R& mx, double xraw, bool cond, const R& go, R& dmx) {
   const double xn = fmax(xraw, (double)MIN_NORM);
   const double mraw = sqrt(rowd_dot(mx, mx));
   const double mn = fmax(mraw, (double)MIN_NORM);
   const double a = artanh_clamped_d(xn), q = a / xn, arg = mn / xn * a;
   const double t = tanh_clamped_d(arg), tp = tanh_prime_d(arg, t);
-  const bool cond = rowd_all_zero(mx);
   const double s = cond ? 0.0 : t / mn;
   const double gm = cond ? 0.0 : rowd_dot(go, mx);             // d L / d s
   const double dsdmn = (tp * q * mn - t) / (mn * mn);
@@ -334,6 +334,74 @@ __device__ __forceinline__ double mobius_matvec_row_bwd(const R& mx, double xraw
   HYPAD_ROW_EACH dmx.v[e] = s * go.v[e] + c * mx.v[e];
   const double dqdxn = (artanh_prime_d(xn) * xn - a) / (xn * xn);
   return xraw >= (double)MIN_NORM ? gm * tp * dqdxn : 0.0;     // (d s / d q = tp)
+}
+template <class R>
+__device__ __forceinline__ R mobius_matvec_row(const R& mx, double xraw) { return mobius_scaled_row(mx, xraw, rowd_all_zero(mx)); }
+template <class R>
+__device__ __forceinline__ double mobius_matvec_row_bwd(const R& mx, double xraw, const R& go, R& dmx) {
+  return mobius_scaled_row_bwd(mx, xraw, rowd_all_zero(mx), go, dmx);
+}
+
+// mobius_pointwise_mul (math_.py:1361-1371): the same scaling of wx = w * x, the zero row where every |w_e x_e| <= 1e-8 (the
+// reference's `isclose` against zero).  The backward sends dL/d|x| back into x itself.
+template <class R>
+__device__ __forceinline__ bool rowd_all_close_to_zero(const R& a) {
+  double nz = 0.0;
+#pragma unroll
+  HYPAD_ROW_EACH nz += fabs(a.v[e]) > 1e-8 ? 1.0 : 0.0;
+  return groupd_sum<R::G>(nz) == 0.0;
+}
+template <class R>
+__device__ __forceinline__ R mobius_pointwise_mul_d(const R& w, const R& x) {
+  R wx;
+#pragma unroll
+  HYPAD_ROW_EACH wx.v[e] = w.v[e] * x.v[e];
+  return mobius_scaled_row(wx, sqrt(rowd_dot(x, x)), rowd_all_close_to_zero(wx));
+}
+template <class R>
+__device__ __forceinline__ void mobius_pointwise_mul_bwd_d(const R& w, const R& x, const R& go, R& dw, R& dx) {
+  R wx, dwx;
+#pragma unroll
+  HYPAD_ROW_EACH wx.v[e] = w.v[e] * x.v[e];
+  const double xraw = sqrt(rowd_dot(x, x));
+  const double c = mobius_scaled_row_bwd(wx, xraw, rowd_all_close_to_zero(wx), go, dwx) / fmax(xraw, (double)MIN_NORM);
+#pragma unroll
+  HYPAD_ROW_EACH { dw.v[e] = dwx.v[e] * x.v[e]; dx.v[e] = dwx.v[e] * w.v[e] + c * x.v[e]; }
+}
+
+// The GRU gate sigmoid(logmap0(y)) (hyrnn_nets.py:81-82).  (Columns past the row's end come out as 0.5: every use multiplies them
+// with a zero of the other operand before a sum is taken.)
+template <class R>
+__device__ __forceinline__ R sigmoid_logmap0_d(const R& y) {
+  R g = radial_map_d<false>(y);
+#pragma unroll
+  HYPAD_ROW_EACH g.v[e] = 1.0 / (1.0 + exp(-g.v[e]));
+  return g;
+}
+template <class R>
+__device__ __forceinline__ R sigmoid_logmap0_bwd_d(const R& y, const R& dg) {
+  const R g = sigmoid_logmap0_d(y);
+  R dl;
+#pragma unroll
+  HYPAD_ROW_EACH dl.v[e] = dg.v[e] * g.v[e] * (1.0 - g.v[e]);
+  return radial_map_bwd_d<false>(y, dl);
+}
+
+// one_rnn_transform (hyrnn_nets.py:61-65) after the two products: ((W (x) h) (+) (U (x) x)) (+) b, and its backward -- the product
+// gradients, the bias gradient and dL/d|h|, dL/d|x|.
+template <class R>
+__device__ __forceinline__ R rnn_transform_row(const R& mh, double hraw, const R& mx, double xraw, const R& b) {
+  return mobius_add_d(mobius_add_d(mobius_matvec_row(mh, hraw), mobius_matvec_row(mx, xraw)), b);
+}
+template <class R>
+__device__ __forceinline__ void rnn_transform_row_bwd(const R& mh, double hraw, const R& mx, double xraw, const R& b, const R& dy, R& dmh,
+                                                      R& dmx, R& db, double& ghn, double& gxn) {
+  const R wh = mobius_matvec_row(mh, hraw), ux = mobius_matvec_row(mx, xraw);
+  R ds, dwh, dux;
+  mobius_add_bwd_d(mobius_add_d(wh, ux), b, dy, ds, db);
+  mobius_add_bwd_d(wh, ux, ds, dwh, dux);
+  ghn = mobius_matvec_row_bwd(mh, hraw, dwh, dmh);
+  gxn = mobius_matvec_row_bwd(mx, xraw, dux, dmx);
 }
 
 // mobius_fn_apply (math_.py:1431-1469): expmap0(f(logmap0(x))) for the two functions the layer takes

@@ -5,6 +5,7 @@ Drop-in for the geoopt functions the reference's hot path reaches through
 logmap0 (:1267-1270), mobius_add (:536-555), project (:340-352), plus the inline row-wise distance of
 train.py:226-230 and the hyperbolic loss of train.py:232.  Each is one HIP kernel forward and one backward.
 dist2plane (:1599-1666) is the function behind hyrnn_nets.MobiusDist2Hyperplane: one HIP launch forward, a HIP backward.
+mobius_pointwise_mul (:1328-1371) is the gate product of the Moebius GRU (hyrnn_nets.mobius_gru_cell), here on its own.
 """
 import torch
 
@@ -97,6 +98,51 @@ def mobius_add(x, y, *, k=None, dim=-1):
     if y.dim() < x.dim():
         y = y.reshape(1, -1)
     return _MobiusAdd.apply(x, y)
+
+
+class _MobiusPointwiseMul(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, w, x):
+        x, x2 = _rows(x)
+        w, w2 = _rows(w)
+        out = torch.empty_like(x2)
+        _C.check(_C.lib.hypad_mobius_pointwise_mul_fwd(_C.ptr(w2), _C.ptr(x2), _C.ptr(out), x2.shape[0], x2.shape[1], w2.shape[0], _C.stream()),
+                 "mobius_pointwise_mul_fwd")
+        ctx.save_for_backward(w2, x2)
+        ctx.ws, ctx.xs = w.shape, x.shape
+        return out.view(x.shape)
+
+    @staticmethod
+    @_C.first_order_only
+    def backward(ctx, go):
+        w2, x2 = ctx.saved_tensors
+        go2 = go.to(torch.float32).contiguous().reshape(x2.shape)
+        gw, gx = torch.empty_like(x2), torch.empty_like(x2)
+        _C.check(_C.lib.hypad_mobius_pointwise_mul_bwd(_C.ptr(w2), _C.ptr(x2), _C.ptr(go2), _C.ptr(gw), _C.ptr(gx), x2.shape[0], x2.shape[1],
+                                                       w2.shape[0], _C.stream()), "mobius_pointwise_mul_bwd")
+        if w2.shape[0] == 1 and x2.shape[0] != 1:
+            red = torch.empty(1, x2.shape[1], device=x2.device, dtype=torch.float32)
+            _C.check(_C.lib.hypad_column_sum(_C.ptr(gw), _C.ptr(red), x2.shape[0], x2.shape[1], _C.stream()))
+            gw = red
+        return gw.view(ctx.ws), gx.view(ctx.xs)
+
+
+_PMUL_SUPPORTED = "supported: k = -1, dim = -1, fp32, w of the shape of x or one row of it, rows of at most 256 elements"
+
+
+def mobius_pointwise_mul(w, x, *, k=None, dim=-1):
+    """diag(w) (x) x for ball-valued rows of x (math_.py:1328-1371) at k = -1: one HIP launch forward and one backward, first-order
+    differentiable in w and x.  w has the shape of x, or is a single row broadcast over the rows of x."""
+    if k is not None and abs(float(k) + 1.0) > 1e-12:
+        raise NotImplementedError(f"mobius_pointwise_mul: curvature k = {float(k)} is not implemented; {_PMUL_SUPPORTED}")
+    if dim != -1 and dim != x.dim() - 1:
+        raise NotImplementedError(f"mobius_pointwise_mul: dim = {dim} is not implemented; {_PMUL_SUPPORTED}")
+    one_row = w.dim() >= 1 and w.numel() == w.shape[-1]
+    if x.dim() < 1 or w.dim() < 1 or w.shape[-1] != x.shape[-1] or (w.shape != x.shape and not one_row):
+        raise NotImplementedError(f"mobius_pointwise_mul: w {tuple(w.shape)} against x {tuple(x.shape)} is not implemented; {_PMUL_SUPPORTED}")
+    if x.shape[-1] > 256:
+        raise NotImplementedError(f"mobius_pointwise_mul: rows of {x.shape[-1]} elements are not implemented; {_PMUL_SUPPORTED}")
+    return _MobiusPointwiseMul.apply(w.reshape(1, -1) if one_row and w.shape != x.shape else w, x)
 
 
 def mobius_fn_apply(fn, x, *args, k=None, dim=-1, **kwargs):

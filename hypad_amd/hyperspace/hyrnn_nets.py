@@ -1,10 +1,14 @@
-"""MobiusLinear / mobius_linear / mobius_matvec and MobiusDist2Hyperplane on the GPU (reference: hyperspace/hyrnn_nets.py:13-58,
-:154-200, :210-245).
+"""MobiusLinear / mobius_linear / mobius_matvec, the Moebius GRU and MobiusDist2Hyperplane on the GPU (reference:
+hyperspace/hyrnn_nets.py:13-58, :61-151, :154-200, :210-245).
 
 Every configuration of the layer runs as one fused HIP forward launch and a HIP backward: Euclidean or ball-valued
 input (the latter through the Moebius matrix-vector product), ball-valued, Euclidean or no bias, and no
 non-linearity, tanh or relu.  The configuration the hot path uses (Euclidean input, ball-valued bias, no
 non-linearity: models/tadgan.py:43-52) keeps its own entry points.  k = -1 and fp32 only; anything else raises.
+
+The GRU (one_rnn_transform, mobius_gru_cell, mobius_gru_loop) carries a hidden state on the ball through time: one GEMM for the input
+projection of all steps, one launch for the whole recurrence, one persistent launch for back-propagation through time
+(csrc/mobius_gru.hip).  The reference file has no module around it, and neither has this one.
 """
 import math
 
@@ -184,6 +188,123 @@ def mobius_linear(input, weight, bias=None, hyperbolic_input=True, hyperbolic_bi
         return _MobiusLinearFn.apply(input, weight, bias)        # the configuration of models/tadgan.py:43-52, as before
     flags = (_C.ML_HYPER_INPUT if hyperbolic_input else 0) | (_C.ML_HYPER_BIAS if hyperbolic_bias else 0)
     return _MobiusLinearExFn.apply(input, weight, bias, flags, code)
+
+
+def one_rnn_transform(W, h, U, x, b, k):
+    """((W (x) h) (+) (U (x) x)) (+) b (reference: hyperspace/hyrnn_nets.py:61-65), composed from the differentiable HIP ops."""
+    from . import gmath
+    _check_k(k, "one_rnn_transform")
+    return gmath.mobius_add(gmath.mobius_add(mobius_matvec(W, h, k=k), mobius_matvec(U, x, k=k), k=k), b, k=k)
+
+
+_GRU_SUPPORTED = ("supported: k = -1, fp32, nonlin None, torch.tanh, torch.relu or torch.nn.functional.relu, input (steps, rows, in) -- the "
+                  "cell: (rows, in) -- with a hidden state (rows, hidden), weight_ih (3 hidden, in), weight_hh (3 hidden, hidden), bias "
+                  "(3, hidden), in and hidden at most 256; batch_sizes: positive, not increasing, summing to the packed rows")
+
+
+class _MobiusGRUFn(torch.autograd.Function):
+    """hypad_mobius_gru_*: x (steps, rows, in) and h0 (rows, hidden) on the ball -> the hidden states (steps, rows, hidden).  Saved for
+    the backward: the operands, the result and the six products per (step, row)."""
+
+    @staticmethod
+    def forward(ctx, x, h0, w_ih, w_hh, bias, nonlin):
+        x, h0, w_ih, w_hh, bias = (_C.require_cuda(t.to(torch.float32).contiguous(), n)
+                                   for t, n in ((x, "input"), (h0, "hidden state"), (w_ih, "weight_ih"), (w_hh, "weight_hh"), (bias, "bias")))
+        steps, rows, i, h = x.shape[0], x.shape[1], x.shape[2], h0.shape[1]
+        out = torch.empty(steps, rows, h, device=x.device, dtype=torch.float32)
+        train = any(ctx.needs_input_grad)                   # inference: nothing is saved
+        saved = torch.empty(steps, rows, 6 * h, device=x.device, dtype=torch.float32) if train else None
+        nbytes = _C.lib.hypad_mobius_gru_workspace_bytes(steps, rows, i, h)
+        ws = torch.empty(max(nbytes // 4, 1), device=x.device, dtype=torch.float32)
+        _C.check(_C.lib.hypad_mobius_gru_fwd(_C.ptr(x), _C.ptr(h0), _C.ptr(w_ih), _C.ptr(w_hh), _C.ptr(bias), _C.ptr(out), _C.ptr(saved),
+                                             _C.ptr(ws), nbytes, steps, rows, i, h, nonlin, _C.stream()), "mobius_gru_fwd")
+        if train:
+            ctx.save_for_backward(x, h0, w_ih, w_hh, bias, out, saved)
+        ctx.nonlin = nonlin
+        return out
+
+    @staticmethod
+    @_C.first_order_only
+    def backward(ctx, go):
+        x, h0, w_ih, w_hh, bias, out, saved = ctx.saved_tensors
+        steps, rows, i, h = x.shape[0], x.shape[1], x.shape[2], h0.shape[1]
+        go = go.to(torch.float32).contiguous()
+        grads = [torch.empty_like(t) if need else None for t, need in zip((x, h0, w_ih, w_hh, bias), ctx.needs_input_grad)]
+        nbytes = _C.lib.hypad_mobius_gru_workspace_bytes(steps, rows, i, h)
+        ws = torch.empty(max(nbytes // 4, 1), device=x.device, dtype=torch.float32)
+        _C.check(_C.lib.hypad_mobius_gru_bwd(_C.ptr(x), _C.ptr(h0), _C.ptr(w_ih), _C.ptr(w_hh), _C.ptr(bias), _C.ptr(out), _C.ptr(saved),
+                                             _C.ptr(go), None, *(_C.ptr(g) for g in grads), _C.ptr(ws), nbytes, steps, rows, i, h, ctx.nonlin,
+                                             _C.stream()), "mobius_gru_bwd")
+        return (*grads, None)
+
+
+def _gru_code(nonlin):
+    try:
+        return _nonlin_code(nonlin)
+    except NotImplementedError:
+        raise NotImplementedError(f"mobius_gru: nonlin = {nonlin!r} has no HIP kernel; {_GRU_SUPPORTED}") from None
+
+
+def _gru_check(x, hx, weight_ih, weight_hh, bias, k, what):
+    """Refuse, before any device call, what the kernels do not take.  x: (..., rows, in)."""
+    if abs(float(k) + 1.0) > 1e-12:
+        raise NotImplementedError(f"{what}: curvature k = {float(k)} is not implemented; {_GRU_SUPPORTED}")
+    ok = (hx.dim() == 2 and weight_ih.dim() == 2 and weight_hh.dim() == 2 and x.dim() >= 2
+          and weight_ih.shape == (3 * hx.shape[1], x.shape[-1]) and weight_hh.shape == (3 * hx.shape[1], hx.shape[1])
+          and tuple(bias.shape) == (3, hx.shape[1]) and hx.shape[1] > 0 and x.shape[-1] > 0)
+    if not ok:
+        raise NotImplementedError(f"{what}: input {tuple(x.shape)}, hidden state {tuple(hx.shape)}, weight_ih {tuple(weight_ih.shape)}, weight_hh "
+                                  f"{tuple(weight_hh.shape)} and bias {tuple(bias.shape)} do not fit together; {_GRU_SUPPORTED}")
+    if x.shape[-1] > 256 or hx.shape[1] > 256:
+        raise NotImplementedError(f"{what}: in = {x.shape[-1]}, hidden = {hx.shape[1]} is not implemented; {_GRU_SUPPORTED}")
+
+
+def mobius_gru_cell(input, hx, weight_ih, weight_hh, bias, k, nonlin=None):
+    """One step of the Moebius GRU (reference: hyperspace/hyrnn_nets.py:68-91): input (rows, in) and hx (rows, hidden) on the ball ->
+    the next hidden state.  The sequence kernels at steps = 1: one GEMM and one launch forward, first-order differentiable."""
+    code = _gru_code(nonlin)
+    _gru_check(input, hx, weight_ih, weight_hh, bias, k, "mobius_gru_cell")
+    if input.dim() != 2 or input.shape[0] != hx.shape[0]:
+        raise NotImplementedError(f"mobius_gru_cell: input {tuple(input.shape)} against a hidden state {tuple(hx.shape)}; {_GRU_SUPPORTED}")
+    return _MobiusGRUFn.apply(input.unsqueeze(0), hx, weight_ih, weight_hh, bias, code)[0]
+
+
+def mobius_gru_loop(input, h0, weight_ih, weight_hh, bias, k, batch_sizes=None, hyperbolic_input=False, hyperbolic_hidden_state0=False,
+                    nonlin=None):
+    """The Moebius GRU over a sequence (reference: hyperspace/hyrnn_nets.py:94-151): returns (outs, h_last).  input (steps, rows, in),
+    or with ``batch_sizes`` the packed (sum(batch_sizes), in); a Euclidean input or h0 goes through expmap0 first.  Equal-length rows
+    run as one autograd function on the sequence kernels (one launch for all steps, forward and backward); packed sequences run the
+    reference's own slicing loop over ``mobius_gru_cell``."""
+    from . import gmath
+    code = _gru_code(nonlin)
+    _gru_check(input, h0, weight_ih, weight_hh, bias, k, "mobius_gru_loop")
+    if batch_sizes is None:
+        if input.dim() != 3 or input.shape[1] != h0.shape[0] or input.shape[0] < 1:
+            raise NotImplementedError(f"mobius_gru_loop: input {tuple(input.shape)} against h0 {tuple(h0.shape)}; {_GRU_SUPPORTED}")
+    else:
+        sizes = [int(b) for b in batch_sizes]
+        if (input.dim() != 2 or not sizes or sizes[0] != h0.shape[0] or min(sizes) < 1 or sum(sizes) != input.shape[0]
+                or any(b > a for a, b in zip(sizes, sizes[1:]))):
+            raise NotImplementedError(f"mobius_gru_loop: batch_sizes {sizes} against input {tuple(input.shape)} and h0 {tuple(h0.shape)}; "
+                                      f"{_GRU_SUPPORTED}")
+    hx = h0 if hyperbolic_hidden_state0 else gmath.expmap0(h0, k=k)
+    if not hyperbolic_input:
+        input = gmath.expmap0(input, k=k)
+    if batch_sizes is None:
+        outs = _MobiusGRUFn.apply(input, hx, weight_ih, weight_hh, bias, code)
+        return outs, outs[-1]
+    outs, h_last = [], []                                    # hyrnn_nets.py:129-150
+    for t, n in enumerate(sizes):
+        ix, input = input[:n], input[n:]
+        hx = _MobiusGRUFn.apply(ix.unsqueeze(0), hx, weight_ih, weight_hh, bias, code)[0]
+        outs.append(hx)
+        if t + 1 < len(sizes):
+            hx, ht = hx[:sizes[t + 1]], hx[sizes[t + 1]:]
+            h_last.append(ht)
+        else:
+            h_last.append(hx)
+    h_last.reverse()
+    return torch.cat(outs), torch.cat(h_last)
 
 
 def _expmap0_host(u):

@@ -138,6 +138,37 @@ int hypad_dist2plane_bwd(const float* x, const float* p, const float* a, const f
                          const float* grad_out, float* grad_x, float* grad_p, float* grad_a, float* grad_log_scale,
                          void* workspace, size_t workspace_bytes,
                          int64_t rows, int in_dim, int out_dim, int flags, hypad_stream_t stream);
+/* gmath.mobius_pointwise_mul  math_.py:1361-1371 at k = -1: tanh(|w x| / |x| artanh |x|) w x / |w x| for ball-valued rows x, the
+ * zero row where every |w_e x_e| <= 1e-8 (the reference's isclose against zero); evaluated in fp64 registers, buffers fp32.
+ * w_rows == 1 broadcasts w over the rows of x; then grad_w is the (rows, dim) matrix of per-row contributions, to be column-summed
+ * by the caller (hypad_column_sum), as hypad_mobius_add_bwd's grad_y.  dim <= 256. */
+int hypad_mobius_pointwise_mul_fwd(const float* w, const float* x, float* out, int64_t rows, int dim, int64_t w_rows, hypad_stream_t stream);
+int hypad_mobius_pointwise_mul_bwd(const float* w, const float* x, const float* grad_out, float* grad_w, float* grad_x,
+                                   int64_t rows, int dim, int64_t w_rows, hypad_stream_t stream);
+/* The Moebius GRU  hyperspace/hyrnn_nets.py:61-151 (one_rnn_transform :61-65, mobius_gru_cell :68-91, the equal-length branch of
+ * mobius_gru_loop :113-127) at k = -1.  x (steps, rows, in_dim) and h0 (rows, hidden) on the ball, w_ih (3 hidden, in_dim),
+ * w_hh (3 hidden, hidden), bias (3, hidden) on the ball, chunk order r, h, z; out (steps, rows, hidden) = the hidden state after
+ * every step (the last one is h_last); no project anywhere, as in the reference.  steps = 1 is the cell.  nonlin: HYPAD_NONLIN_*
+ * on h~ (:87-88).  Forward: one GEMM for x W_ih^T of all steps and ONE launch for the recurrence; the row chains run in fp64
+ * registers, every buffer and every MFMA product is fp32.  saved (steps, rows, 6 hidden) receives the products
+ * [mx_r | mx_h | mx_z | mh_r | mh_z | m_rh] for the backward (NULL: inference).
+ * bwd: one persistent launch walks the steps in reverse, then dense contractions over steps * rows rows.  grad_out
+ * (steps, rows, hidden); grad_h_last (rows, hidden) is added to the last step's (NULL: none); grad_x, grad_h0, grad_w_ih, grad_w_hh
+ * and grad_bias may each be NULL.  No atomics: two runs give the same bits.  rows == 0 launches no row kernel and writes zero
+ * parameter gradients (the row buffers and the workspace may then be NULL).
+ * workspace: hypad_mobius_gru_workspace_bytes(steps, rows, in_dim, hidden) = 4 steps rows (14 hidden + 1) bytes, for both calls.
+ * Every argument is validated before anything is launched: HYPAD_EINVAL for a NULL operand, a non-positive size or an unknown
+ * nonlin; HYPAD_EUNSUPPORTED for in_dim or hidden > 256, steps * rows >= 2^31, or LDS that does not fit (also where
+ * hypad_linear_act_fwd / _bwd refuse 3 hidden outputs); HYPAD_EWORKSPACE below the workspace size. */
+size_t hypad_mobius_gru_workspace_bytes(int steps, int64_t rows, int in_dim, int hidden);
+int hypad_mobius_gru_fwd(const float* x, const float* h0, const float* w_ih, const float* w_hh, const float* bias, float* out,
+                         float* saved /* NULL: inference */, void* workspace, size_t workspace_bytes,
+                         int steps, int64_t rows, int in_dim, int hidden, int nonlin, hypad_stream_t stream);
+int hypad_mobius_gru_bwd(const float* x, const float* h0, const float* w_ih, const float* w_hh, const float* bias, const float* out,
+                         const float* saved, const float* grad_out, const float* grad_h_last /* NULL: none */,
+                         float* grad_x, float* grad_h0, float* grad_w_ih, float* grad_w_hh, float* grad_bias,
+                         void* workspace, size_t workspace_bytes,
+                         int steps, int64_t rows, int in_dim, int hidden, int nonlin, hypad_stream_t stream);
 /* inline row-wise Poincare distance  train.py:226-230; utils/anomaly_detection_utils.py:58-66,167-175 */
 int hypad_poincare_rowdist_fwd(const float* u, const float* v, float* dist, int64_t rows, int dim, hypad_stream_t stream);
 int hypad_poincare_rowdist_bwd(const float* u, const float* v, const float* grad_dist, float* grad_u, float* grad_v,
