@@ -20,11 +20,38 @@ def _f32c(t, name):
     return _C.require_cuda(t.to(torch.float32).contiguous(), name)
 
 
+def _sh(t):
+    return None if t is None else tuple(t.shape)
+
+
+def _check_linear(x, weight, bias):
+    """The entry points take (rows, k, n) once: operands that do not fit are refused here, before any device tensor is asked for."""
+    if x.dim() != 2 or weight.dim() != 2 or x.shape[1] != weight.shape[1] or _sh(bias) != (weight.shape[0],):
+        raise _C.HypadError(f"linear_act: input {_sh(x)}, weight {_sh(weight)} and bias {_sh(bias)} do not fit together: "
+                            "(rows, in), (out, in) and (out,)")
+
+
+def _check_lstm(what, x, ndim, w_ih, w_hh, b_ih, b_hh, w_ih_r, w_hh_r, b_ih_r, b_hh_r, states=()):
+    """x -- (rows, in) at ndim 2, (T, rows, in) at ndim 3 -- against nn.LSTM's eight tensors of one bidirectional layer, and h0 / c0
+    (``states``, each (2, rows, H) or None) against both: refused before any device tensor is asked for."""
+    h4 = w_ih.shape[0] if w_ih.dim() == 2 else -1
+    ok = (x.dim() == ndim and h4 > 0 and h4 % 4 == 0 and x.shape[-1] == w_ih.shape[1] and _sh(w_ih_r) == _sh(w_ih)
+          and _sh(w_hh) == _sh(w_hh_r) == (h4, h4 // 4) and all(_sh(b) == (h4,) for b in (b_ih, b_hh, b_ih_r, b_hh_r)))
+    if not ok:
+        raise _C.HypadError(f"{what}: input {_sh(x)} against weight_ih {_sh(w_ih)} / {_sh(w_ih_r)}, weight_hh {_sh(w_hh)} / {_sh(w_hh_r)} and biases "
+                            f"{[_sh(b) for b in (b_ih, b_hh, b_ih_r, b_hh_r)]}: expected {'(T, rows, in)' if ndim == 3 else '(rows, in)'}, "
+                            "(4H, in), (4H, H) and (4H,)")
+    for name, t in zip(("h0", "c0"), states):
+        if t is not None and _sh(t) != (2, x.shape[-2], h4 // 4):
+            raise _C.HypadError(f"{what}: {name} {_sh(t)} against an input {_sh(x)} and hidden size {h4 // 4}: expected {(2, x.shape[-2], h4 // 4)}")
+
+
 class _LinearAct(torch.autograd.Function):
     """y = act(x W^T + b): nn.Linear + nn.Tanh / nn.LeakyReLU(0.2)."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, act):
+        _check_linear(x, weight, bias)
         x, w, b = _f32c(x, "input"), _f32c(weight, "weight"), _f32c(bias, "bias")
         rows, k, n = x.shape[0], x.shape[1], w.shape[0]
         y = torch.empty(rows, n, device=x.device, dtype=torch.float32)
@@ -53,6 +80,7 @@ class _LstmBidirT1(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, wf, whf, bif, bhf, wr, whr, bir, bhr):
+        _check_lstm("lstm_layer", x, 2, wf, whf, bif, bhf, wr, whr, bir, bhr)
         x = _f32c(x, "input")
         ps = [_f32c(t, "lstm parameter") for t in (wf, bif, bhf, wr, bir, bhr)]
         rows, k, h = x.shape[0], x.shape[1], wf.shape[0] // 4
@@ -145,6 +173,7 @@ class _LstmBidirSeq(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, h0, c0, wif, whf, bif, bhf, wir, whr, bir, bhr):
+        _check_lstm("lstm_seq", x, 3, wif, whf, bif, bhf, wir, whr, bir, bhr, (h0, c0))
         x = _f32c(x, "input")
         ps = [_f32c(t, "lstm parameter") for t in (wif, whf, bif, bhf, wir, whr, bir, bhr)]
         T, rows, k = x.shape
@@ -201,6 +230,9 @@ def lstm_seq_forward(x, lstm, layer=0, hx=None):
     form: one MFMA GEMM for the input projections of all steps + a persistent recurrence kernel (csrc/lstm_seq.hip)."""
     if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in lstm.parameters())):
         raise _C.HypadError("lstm_seq_forward is the inference form: wrap the call in torch.no_grad(), or use lstm_seq (back-propagation through time)")
+    names = ("weight_ih", "weight_hh", "bias_ih", "bias_hh")
+    _check_lstm("lstm_seq_forward", x, 3, *(getattr(lstm, n + f"_l{layer}") for n in names),
+                *(getattr(lstm, n + f"_l{layer}_reverse") for n in names), states=(None, None) if hx is None else hx)
     x = _f32c(x, "input")
     T, rows, k = x.shape
     g = lambda n: _f32c(getattr(lstm, n + f"_l{layer}").detach(), n)

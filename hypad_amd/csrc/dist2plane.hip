@@ -281,6 +281,14 @@ __global__ __launch_bounds__(THREADS) void d2p_finish_rows(const float* __restri
   }
 }
 
+// wcat (2N, K) = [P ; A], nk = N K floats each.  A kernel, not two hipMemcpyAsync: a call may be captured into a graph, and this
+// library puts no non-kernel node between the kernels of a captured sequence (scoring.hip: launch_quantiles).
+__global__ __launch_bounds__(THREADS) void d2p_stack_kernel(const float* __restrict__ P, const float* __restrict__ A,
+                                                             float* __restrict__ wcat, size_t nk) {
+  for (size_t i = (size_t)blockIdx.x * THREADS + threadIdx.x; i < 2 * nk; i += (size_t)gridDim.x * THREADS)
+    wcat[i] = i < nk ? P[i] : A[i - nk];
+}
+
 struct D2PWorkspace {
   size_t wcat, wpart, ccat, cx2, part, total;                      // offsets in floats
   int slices;
@@ -373,9 +381,10 @@ int hypad_dist2plane_bwd(const float* x, const float* p, const float* a, const f
   const bool planes = grad_p || grad_a;
   if (grad_x) {
     // grad_x = [C_px | C_xa] [P ; A]
-    e = hipMemcpyAsync(ws + w.wcat, p, (size_t)N * K * sizeof(float), hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(ws + w.wcat + (size_t)N * K, a, (size_t)N * K * sizeof(float), hipMemcpyDeviceToDevice, st);
-    if (e != hipSuccess) return (int)e;
+    const size_t nk = (size_t)N * K;
+    const size_t blocks = (2 * nk + THREADS - 1) / THREADS;
+    hipLaunchKernelGGL(d2p_stack_kernel, dim3((unsigned)(blocks > 4096 ? 4096 : blocks)), dim3(THREADS), 0, st, p, a, ws + w.wcat, nk);
+    HYPAD_CHECK_LAUNCH();
     rc = hypad_linear_act_bwd(nullptr, ws + w.wcat, nullptr, ws + w.ccat, grad_x, nullptr, nullptr, nullptr, rows, K, 2 * N,
                               HYPAD_ACT_NONE, s);
     if (rc) return rc;

@@ -25,6 +25,21 @@ def _rows(t):
     return t, t.reshape(-1, t.shape[-1])
 
 
+def _rows_width(t):
+    """(rows, width) of t taken as rows of its last dimension, from the shape alone."""
+    rows = 1
+    for n in t.shape[:-1]:
+        rows *= n
+    return rows, t.shape[-1]
+
+
+def _same_shape(what, u, v):
+    """The row kernels take one (rows, dim) for both operands and broadcast nothing: refused here, before any device tensor is asked
+    for (the entry point would read v with u's sizes)."""
+    if u.dim() < 1 or u.shape != v.shape:
+        raise _C.HypadError(f"{what}: u {tuple(u.shape)} and v {tuple(v.shape)} must have the same shape (nothing is broadcast)")
+
+
 class _Unary(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, fwd, bwd):
@@ -65,11 +80,11 @@ def project(x, *, k=None, dim=-1, eps=-1.0):
 class _MobiusAdd(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, y):
+        if x.dim() < 1 or y.dim() < 1 or _rows_width(y)[0] not in (1, _rows_width(x)[0]) or y.shape[-1] != x.shape[-1]:
+            raise _C.HypadError(f"mobius_add: y {tuple(y.shape)} must have the rows of x {tuple(x.shape)} or a single (broadcast) row")
         x, x2 = _rows(x)
         y, y2 = _rows(y)
         yr = y2.shape[0]
-        if yr not in (1, x2.shape[0]) or y2.shape[1] != x2.shape[1]:
-            raise _C.HypadError("mobius_add: y must have the rows of x or a single (broadcast) row")
         out = torch.empty_like(x2)
         _C.check(_C.lib.hypad_mobius_add_fwd(_C.ptr(x2), _C.ptr(y2), _C.ptr(out), x2.shape[0], x2.shape[1], yr, _C.stream()))
         ctx.save_for_backward(x2, y2)
@@ -93,6 +108,8 @@ class _MobiusAdd(torch.autograd.Function):
 
 def mobius_add(x, y, *, k=None, dim=-1):
     _check_k(k)
+    if x.dim() < 1 or y.dim() < 1 or y.shape[-1] != x.shape[-1]:
+        raise _C.HypadError(f"mobius_add: x {tuple(x.shape)} and y {tuple(y.shape)} differ in their last dimension")
     if y.dim() == x.dim() and y.shape != x.shape:
         y = y.expand_as(x)
     if y.dim() < x.dim():
@@ -167,6 +184,11 @@ class _Dist2Plane(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, p, a, log_scale, flags):
+        if (p.dim() != 2 or a.shape != p.shape or x.dim() < 1 or x.shape[-1] != p.shape[1]
+                or (log_scale is not None and tuple(log_scale.shape) != (p.shape[0],))):
+            raise _C.HypadError(f"dist2plane: x {tuple(x.shape)} against p {tuple(p.shape)}, a {tuple(a.shape)}"
+                                + ("" if log_scale is None else f" and scale {tuple(log_scale.shape)}")
+                                + ": p and a must be (out_features, in_features), x (..., in_features), scale (out_features,)")
         x, x2 = _rows(x)
         p = _C.require_cuda(p.contiguous(), "p")
         a = _C.require_cuda(a.contiguous(), "a")
@@ -223,6 +245,7 @@ def dist2plane(x, p, a, *, k=None, keepdim=False, signed=False, scaled=False, di
 class _RowDist(torch.autograd.Function):
     @staticmethod
     def forward(ctx, u, v):
+        _same_shape("poincare_rowdist", u, v)
         u, u2 = _rows(u)
         v, v2 = _rows(v)
         out = torch.empty(u2.shape[0], device=u2.device, dtype=torch.float32)
@@ -250,6 +273,7 @@ def poincare_rowdist(u, v):
 class _HyperLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, u, v, batch):
+        _same_shape("hyperbolic_loss", u, v)
         u, u2 = _rows(u)
         v, v2 = _rows(v)
         out = torch.empty(1, device=u2.device, dtype=torch.float32)
@@ -263,8 +287,15 @@ class _HyperLoss(torch.autograd.Function):
     def backward(ctx, g):
         u2, v2 = ctx.saved_tensors
         gu, gv = torch.empty_like(u2), torch.empty_like(v2)
-        _C.check(_C.lib.hypad_hyper_loss_bwd(_C.ptr(u2), _C.ptr(v2), float(g), _C.ptr(gu), _C.ptr(gv), u2.shape[0], u2.shape[1],
-                                             ctx.batch, _C.stream()))
+        # The incoming gradient stays on the device (float(g) would make the host wait for the stream on every backward, and cannot be
+        # captured): g / batch per row, the same fp32 division hypad_hyper_loss_bwd does on the host, into the row-distance backward --
+        # the same kernel with gd[r] in place of its scalar.  (Both operands are tensors: torch divides by a host scalar by
+        # multiplying with its reciprocal, which is not the same bits.)
+        rows = u2.shape[0]
+        if rows == 0:
+            return gu.view(ctx.us), gv.view(ctx.vs), None
+        gd = g.to(torch.float32).reshape(1).expand(rows) / torch.full((rows,), float(ctx.batch), device=u2.device, dtype=torch.float32)
+        _C.check(_C.lib.hypad_poincare_rowdist_bwd(_C.ptr(u2), _C.ptr(v2), _C.ptr(gd), _C.ptr(gu), _C.ptr(gv), rows, u2.shape[1], _C.stream()))
         return gu.view(ctx.us), gv.view(ctx.vs), None
 
 

@@ -49,6 +49,7 @@ def _rebuild_manifold_parameter(data, manifold, requires_grad):
 class _MobiusLinearFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias):
+        _check_fit("mobius_linear", x, weight, bias)
         x = _C.require_cuda(x.to(torch.float32).contiguous(), "input")
         w = _C.require_cuda(weight.contiguous(), "weight")
         b = _C.require_cuda(bias.contiguous(), "bias")
@@ -78,12 +79,20 @@ class _MobiusLinearFn(torch.autograd.Function):
         return gx.view(ctx.xshape), gw, gb
 
 
-def _rows_of(x, weight, what):
+def _check_fit(what, x, weight, bias=None):
+    """Refuse, before any device tensor is asked for, operands whose shapes do not fit: the entry points take the sizes once and would
+    read the other operand past its end."""
+    if weight.dim() != 2 or x.dim() < 1 or x.shape[-1] != weight.shape[1]:
+        raise _C.HypadError(f"{what}: weight must be (out_features, in_features) and the input (..., in_features), got "
+                            f"{tuple(weight.shape)} and {tuple(x.shape)}")
+    if bias is not None and tuple(bias.shape) != (weight.shape[0],):
+        raise _C.HypadError(f"{what}: bias must be (out_features,), got {tuple(bias.shape)} against a weight {tuple(weight.shape)}")
+
+
+def _rows_of(x, weight, what, bias=None):
+    _check_fit(what, x, weight, bias)
     x = _C.require_cuda(x.to(torch.float32).contiguous(), "input")
     w = _C.require_cuda(weight.contiguous(), "weight")
-    if w.dim() != 2 or x.dim() < 1 or x.shape[-1] != w.shape[1]:
-        raise _C.HypadError(f"{what}: weight must be (out_features, in_features) and the input (..., in_features), got "
-                            f"{tuple(w.shape)} and {tuple(x.shape)}")
     return x, x.reshape(-1, x.shape[-1]), w
 
 
@@ -92,7 +101,7 @@ class _MobiusLinearExFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, flags, nonlin):
-        x, x2, w = _rows_of(x, weight, "mobius_linear")
+        x, x2, w = _rows_of(x, weight, "mobius_linear", bias)
         b = None if bias is None else _C.require_cuda(bias.contiguous(), "bias")
         rows, k, n = x2.shape[0], x2.shape[1], w.shape[0]
         out = torch.empty(rows, n, device=x.device, dtype=torch.float32)

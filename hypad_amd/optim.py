@@ -5,6 +5,9 @@
 oracle/radam.py for the rule and its pinning status).  Inside the fused training iterations the same update
 runs in the epilogue of the weight-gradient kernel; these classes exist for callers that bring their own
 ``.grad`` tensors, and to carry hyper-parameters / state for ``hypad_amd.train``.
+
+A step takes its step number by value, so a step captured into a graph would replay the same bias correction for ever: run the steps
+eagerly (on any stream), and capture only what comes before them.
 """
 import torch
 
