@@ -451,6 +451,24 @@ class _CheckpointWriter:
             raise e
 
 
+_FILE_STEMS = dict(enc="encoder", dec="decoder", cx="critic_x", cz="critic_z")      # checkpoint file names (train.py:381-385, 461-464), in engine.NETS order
+
+
+def _saves_checkpoint(first_epoch, e, n_epochs):
+    """train.py:381, cadence kept as is: epoch ``e`` of this call is the reference's ``actual_epoch = first_epoch + e + 1``; on resume
+    ``first_epoch`` is ``resume_epoch + 1`` and ``n_epochs`` the ALREADY REDUCED number of epochs (the reference's quirk)."""
+    return (first_epoch + e + 1) % 10 == 0 or (first_epoch + e + 1) == n_epochs - 1
+
+
+def _reference_engine(params, hyperbolic, n_signals, dev, seed, first_signal=0):
+    """The engine of ``n_signals`` models with the reference's optimizers (train.py:274-288: Adam at params.lr for the critics; for the
+    generator RiemannianAdam with weight decay and stabilisation when hyperbolic, plain Adam else) and the caller's epoch flags."""
+    eng = Engine(params.signal_shape, params.latent_space_dim, params.batch_size, hyperbolic, n_signals, dev, lr=params.lr, betas=(0.9, 0.999),
+                 gen_weight_decay=1e-5 if hyperbolic else 0.0, gen_stabilize=10 if hyperbolic else 0, seed=seed, first_signal=first_signal)
+    eng.epoch_flags = int(getattr(params, "epoch_flags", 0))      # hypad_epoch_io.flags (A/B forms of the critic phase; tests)
+    return eng
+
+
 def _per_iteration_wanted(train_loader, params):
     if getattr(params, "per_iteration", False) or os.environ.get("HYPAD_TRAIN_PER_ITERATION") == "1":
         return True
@@ -476,10 +494,8 @@ def train_tadgan(train_loader, encoder, decoder, critic_x, critic_z, n_epochs=20
     mods = {"enc": encoder, "dec": decoder, "cx": critic_x, "cz": critic_z}
     dev = encoder.arena().device
     resume = getattr(params, "resume", False)
-    eng = Engine(S, L, B, hyp, 1, dev, lr=params.lr, betas=(0.9, 0.999), gen_weight_decay=1e-5 if hyp else 0.0,          # train.py:274-288
-                 gen_stabilize=10 if hyp else 0, seed=torch.initial_seed() + _resume_salt(params.resume_epoch if resume else None))
+    eng = _reference_engine(params, hyp, 1, dev, torch.initial_seed() + _resume_salt(params.resume_epoch if resume else None))
     eng.adopt({k: m.arena() for k, m in mods.items()})
-    eng.epoch_flags = int(getattr(params, "epoch_flags", 0))      # hypad_epoch_io.flags (A/B forms of the critic phase; tests)
     n_critics = 5
     feed = EpochFeed(train_loader, B, S, L, n_critics, dev, index_path=not getattr(params, "stage_samples", False))
     nb = feed.nb
@@ -495,7 +511,7 @@ def train_tadgan(train_loader, encoder, decoder, critic_x, critic_z, n_epochs=20
         actual_epoch = params.resume_epoch + 1
     feed.last_epoch = n_epochs - 1
     state = {"repaired_until": -1}
-    saves = lambda e: ((actual_epoch + e + 1) % 10 == 0) or ((actual_epoch + e + 1) == (n_epochs - 1))      # train.py:381 (cadence kept as is)
+    saves = lambda e: _saves_checkpoint(actual_epoch, e, n_epochs)
 
     from . import streams as _streams
     copy_stream = _streams.beside([torch.cuda.current_stream()], dev)      # (a stream that shares the training stream's hardware queue would copy BEHIND the epoch, not under it)
@@ -560,8 +576,7 @@ def train_tadgan(train_loader, encoder, decoder, critic_x, critic_z, n_epochs=20
         hist.wall.append(time.perf_counter())
         if saves(e):
             ae = actual_epoch + e + 1
-            writer.submit(snaps.pop(e), {"enc": path + "/encoder_{}.pt".format(ae), "dec": path + "/decoder_{}.pt".format(ae),
-                                         "cx": path + "/critic_x_{}.pt".format(ae), "cz": path + "/critic_z_{}.pt".format(ae)})
+            writer.submit(snaps.pop(e), {k: path + "/{}_{}.pt".format(stem, ae) for k, stem in _FILE_STEMS.items()})
 
     try:
         for epoch in range(n_epochs):
@@ -730,6 +745,88 @@ def _resident_epoch_means(rows, n_critics, n_batches):
     return float(crit[0]), float(crit[1]), float(gl[0]), float(gl[1])
 
 
+class _ResidentGroup:
+    """One engine's share of a resident run: the model of train_tadgan_resident, or one launch group of train_signals_resident --
+    the ONE epoch pipeline both use, so that a signal trains to the same bits alone and inside a group.  ``enqueue`` queues an epoch
+    (host-drawn shuffles where they cannot be drawn inside the captured epoch, the graph replay, the losses and the counters into a
+    pinned buffer picked by epoch parity, an event, the device copy of a checkpoint epoch's weights); ``collect`` reads it back --
+    usually one epoch later, with the next epoch already queued behind it -- and repairs a resident critic launch that gave up.
+    ``x``, ``row_index`` and ``windows`` go to Engine.train_epoch_graph as they are, on every call (the graph key holds the buffers'
+    addresses): a (passes, n_batches * batch) plane with one window count, or a plane per model with a list of counts.
+    ``snapshot()``: the caller's device copy of this engine's weights (_CheckpointWriter.snapshot).  ``lane``: the stream the group's
+    launches go to (None: the current one)."""
+
+    def __init__(self, eng, x, row_index, windows, n_batches, snapshot, x_row_stride=0, n_critics=5):
+        self.eng, self.x, self.row_index, self.windows, self.x_row_stride = eng, x, row_index, windows, x_row_stride
+        self.n_batches, self.n_critics, self.snapshot, self.lane = n_batches, n_critics, snapshot, None
+        self.counts = list(windows) if isinstance(windows, (list, tuple)) else [windows]
+        # one uniform permutation per pass: drawn by the library inside the captured epoch where it can (<= 4096 windows:
+        # hypad_epoch_shuffles), else by one batched torch sort per model (argsort of uniform keys) into the plane the epoch reads
+        self.in_graph = max(self.counts) <= eng.SHUFFLE_MAX_WINDOWS
+        self.planes = row_index.view(len(self.counts), n_critics + 1, n_batches * eng.B)
+        self.gens = None if self.in_graph else [_host_shuffle_generator(eng.device, eng.seed, eng.first_signal + s) for s in range(len(self.counts))]
+        self.n = len(self.counts) * (2 * n_critics + 1) * n_batches * 4
+        self.back = [torch.empty(self.n + 8, dtype=torch.float32).pin_memory() for _ in range(2)]      # losses | counters (as bits), by epoch parity
+        self.done = [torch.cuda.Event() for _ in range(2)]
+        self.snaps, self.kept, self.repaired_until = {}, {}, -1      # kept: the host losses of repeated epochs
+
+    def on_lane(self):
+        return torch.cuda.stream(self.lane) if self.lane is not None else contextlib.nullcontext()
+
+    def enqueue(self, e, want_snapshot):
+        with self.on_lane():
+            if not self.in_graph:
+                for plane, c, gen in zip(self.planes, self.counts, self.gens):
+                    plane.copy_(torch.rand(self.n_critics + 1, c, device=self.eng.device, generator=gen).argsort(dim=1)[:, : plane.shape[1]])
+            # the epoch is a fixed launch sequence: captured once as a hipGraph, replayed every epoch (Engine.train_epoch_graph)
+            self.losses = self.eng.train_epoch_graph(self.x, self.row_index, self.n_batches, self.n_critics, True, x_row_stride=self.x_row_stride,
+                                                     shuffle_windows=self.windows if self.in_graph else 0)
+            b = self.back[e % 2]
+            b[: self.n].copy_(self.losses.view(-1), non_blocking=True)
+            b[self.n:].view(torch.int32).copy_(self.eng.counters, non_blocking=True)
+            self.done[e % 2].record()
+            if want_snapshot:
+                self.snaps[e] = self.snapshot()                      # epoch e's weights, before epoch e + 1 is queued (_CheckpointWriter)
+
+    def collect(self, e):
+        """Epoch e's losses on the host: ((models, iterations, 4) rows, whether a repair happened).  Did its resident critic launch
+        complete?  If one of its bounded waits gave up (a CU withheld by a CU mask / a shared device), the launches behind it -- the rest
+        of the epoch and the epoch queued behind it -- were no-ops: check_status restores the critics and repeats the queued epochs with
+        one launch per critic iteration, for good, on the group's own stream; the losses of each repeat are kept and a checkpoint epoch
+        among them is copied again, behind its repeat."""
+        self.done[e % 2].synchronize()
+        b, repaired = self.back[e % 2], False
+        if e > self.repaired_until:
+            if int(b[self.n:].view(torch.int32)[4]) != 0:            # status word of the resident critic launch (hypad_epoch_status)
+                def redo(i):
+                    self.kept[e + i] = self.losses.detach().cpu()    # (the repeat's losses: the buffer is the next repeat's too)
+                    if e + i in self.snaps:
+                        self.snaps[e + i] = self.snapshot()
+                with self.on_lane():
+                    self.eng.check_status(on_epoch=redo)
+                self.repaired_until, repaired = max(self.kept, default=e), True
+            else:
+                self.eng.confirm_epochs(1)                           # epoch e completed: one epoch less for a later repair to look at
+        rows = self.kept.pop(e) if e in self.kept else b[: self.n]
+        return rows.view(len(self.counts), -1, 4), repaired
+
+
+def _run_resident_epochs(groups, n_epochs, saves, finish):
+    """Every group's epoch e queued, then ``finish(e - 1)``: the host looks at an epoch's losses when the next epoch is already
+    queued behind it.  Groups whose shuffles are drawn on the host are finished epoch by epoch instead: a repair repeats epochs
+    from the buffers as they are then, so it must cover exactly the epoch just finished."""
+    pipelined = all(g.in_graph for g in groups)
+    for e in range(n_epochs):
+        for g in groups:
+            g.enqueue(e, saves(e))
+        if not pipelined:
+            finish(e)
+        elif e > 0:
+            finish(e - 1)
+    if pipelined and n_epochs > 0:
+        finish(n_epochs - 1)
+
+
 def train_tadgan_resident(dataset, encoder, decoder, critic_x, critic_z, n_epochs, params, path="", seed=None, log=print, first_signal=0):
     """train_tadgan (train.py:252-385) with everything on the device: the same epoch schedule -- 5 passes of
     (critic_x_iteration, critic_z_iteration) over the shuffled minibatches, then one pass of decoder_iteration -- as one
@@ -743,13 +840,11 @@ def train_tadgan_resident(dataset, encoder, decoder, critic_x, critic_z, n_epoch
     ``train_signals_resident`` group bit for bit."""
     B, S = params.batch_size, params.signal_shape
     dev = encoder.arena().device
-    eng = Engine(S, params.latent_space_dim, B, bool(params.hyperbolic), 1, dev, lr=params.lr,
-                 gen_weight_decay=1e-5 if params.hyperbolic else 0.0, gen_stabilize=10 if params.hyperbolic else 0,
-                 seed=(torch.initial_seed() if seed is None else seed)
-                 + _resume_salt(params.resume_epoch if getattr(params, "resume", False) else None), first_signal=first_signal)
+    resume = getattr(params, "resume", False)
+    eng = _reference_engine(params, bool(params.hyperbolic), 1, dev, (torch.initial_seed() if seed is None else seed)
+                            + _resume_salt(params.resume_epoch if resume else None), first_signal)
     mods = {"enc": encoder, "dec": decoder, "cx": critic_x, "cz": critic_z}
     eng.adopt({k: m.arena() for k, m in mods.items()})
-    eng.epoch_flags = int(getattr(params, "epoch_flags", 0))      # hypad_epoch_io.flags (A/B forms of the critic phase; tests)
     if hasattr(dataset, "window_view"):
         x, n_windows, stride = dataset.window_view(dev)
     else:
@@ -759,75 +854,29 @@ def train_tadgan_resident(dataset, encoder, decoder, critic_x, critic_z, n_epoch
     if n_batches < 1:
         raise _C.HypadError(f"{n_windows} windows do not fill one batch of {B}")
     n_critics = 5
-    gen = _host_shuffle_generator(dev, eng.seed, first_signal)
-    perm_buf = torch.empty(n_critics + 1, n_batches * B, dtype=torch.int32, device=dev)
     history = SimpleNamespace(cx=[], cz=[], dec=[], hyper=[], mse=[], repairs=0)      # repairs: resident critic launches that gave up and were repeated
-    actual_epoch = 0
-    if getattr(params, "resume", False):
+    first_epoch = 0
+    if resume:
         n_epochs = n_epochs - params.resume_epoch
-        actual_epoch = params.resume_epoch + 1
-    # one uniform permutation per pass: drawn by the library inside the captured epoch where it can (<= 4096 windows:
-    # hypad_epoch_shuffles), else by one batched torch sort (argsort of uniform keys) into the buffer the epoch reads
-    in_graph = n_windows <= eng.SHUFFLE_MAX_WINDOWS
-    iters = (2 * n_critics + 1) * n_batches
-    back = [torch.empty(iters * 4 + 8, dtype=torch.float32).pin_memory() for _ in range(2)]        # losses | counters (as bits), by epoch parity
-    done = [torch.cuda.Event() for _ in range(2)]
+        first_epoch = params.resume_epoch + 1
     writer = _CheckpointWriter(dev, mods)
-    snaps, state = {}, {"repaired_until": -1, "repaired": {}}
-    first_epoch = actual_epoch
-    saves = lambda e: bool(path) and (((first_epoch + e + 1) % 10 == 0) or ((first_epoch + e + 1) == (n_epochs - 1)))      # train.py:381 (cadence kept as is)
-
-    def enqueue(e):
-        if not in_graph:
-            perm = torch.rand(n_critics + 1, n_windows, device=dev, generator=gen).argsort(dim=1)[:, : n_batches * B]
-            perm_buf.copy_(perm)
-        # the epoch is a fixed launch sequence: captured once as a hipGraph, replayed every epoch (Engine.train_epoch_graph)
-        losses = eng.train_epoch_graph(x, perm_buf, n_batches, n_critics, True, x_row_stride=stride, shuffle_windows=n_windows if in_graph else 0)
-        b = back[e % 2]
-        b[: iters * 4].copy_(losses.view(-1), non_blocking=True)
-        b[iters * 4:].view(torch.int32).copy_(eng.counters, non_blocking=True)
-        done[e % 2].record()
-        if saves(e):
-            snaps[e] = writer.snapshot()                         # epoch e's weights, before epoch e + 1 is queued (_CheckpointWriter)
+    group = _ResidentGroup(eng, x, torch.empty(n_critics + 1, n_batches * B, dtype=torch.int32, device=dev), n_windows, n_batches, writer.snapshot, stride, n_critics)
+    saves = lambda e: bool(path) and _saves_checkpoint(first_epoch, e, n_epochs)
 
     def finish(e):
-        """Epoch e's losses on the host -- with its shuffles drawn inside the captured epoch the next epoch is already queued behind it.
-        Did its resident critic launch complete?  If one of its bounded waits gave up (a CU withheld by a CU mask / a shared device),
-        the launches behind it were no-ops: check_status restores the critics and repeats the queued epochs with one launch per critic
-        iteration, for good."""
-        done[e % 2].synchronize()
-        b = back[e % 2]
-        if e > state["repaired_until"]:
-            if int(b[iters * 4:].view(torch.int32)[4]) != 0:
-                def redo(i):
-                    state["repaired"][e + i] = eng._last_epoch["losses"].detach().cpu().view(-1)
-                    if e + i in snaps:
-                        snaps[e + i] = writer.snapshot()
-                eng.check_status(on_epoch=redo)
-                state["repaired_until"] = max(state["repaired"]) if state["repaired"] else e
-                history.repairs += 1
-            else:
-                eng.confirm_epochs(1)
-        rows = (state["repaired"].pop(e) if e in state["repaired"] else b[: iters * 4]).view(iters, 4)
-        cx_, cz_, dec_, aux_ = _resident_epoch_means(rows, n_critics, n_batches)      # (the reduction on the host: one copy per epoch)
+        rows, repaired = group.collect(e)
+        history.repairs += int(repaired)
+        cx_, cz_, dec_, aux_ = _resident_epoch_means(rows[0], n_critics, n_batches)      # (the reduction on the host: one copy per epoch)
         history.cx.append(cx_); history.cz.append(cz_); history.dec.append(dec_)
         (history.hyper if params.hyperbolic else history.mse).append(aux_)
         if log:
             log("epoch {}: critic x loss {:.3f} critic z loss {:.3f} decoder loss {:.3f} {} {:.5f}".format(
                 e, history.cx[-1], history.cz[-1], history.dec[-1], "hyperbolic loss" if params.hyperbolic else "mse", aux_))
         if saves(e):
-            ae = first_epoch + e + 1
-            writer.submit(snaps.pop(e), {k: path + "/{}_{}.pt".format(nm, ae) for k, nm in (("enc", "encoder"), ("dec", "decoder"), ("cx", "critic_x"), ("cz", "critic_z"))})
+            writer.submit(group.snaps.pop(e), {k: path + "/{}_{}.pt".format(stem, first_epoch + e + 1) for k, stem in _FILE_STEMS.items()})
 
     try:
-        for epoch in range(n_epochs):
-            enqueue(epoch)
-            if not in_graph:                        # host-drawn shuffles: a repair repeats epochs from the buffer as it is then -- one epoch at a time
-                finish(epoch)
-            elif epoch > 0:
-                finish(epoch - 1)
-        if in_graph and n_epochs > 0:
-            finish(n_epochs - 1)
+        _run_resident_epochs([group], n_epochs, saves, finish)
     finally:
         writer.close()                              # every checkpoint file is complete when the call returns
     return history
@@ -848,8 +897,8 @@ def train_resident(dataset, params, config_path=None, seed=None, log=print, firs
     if getattr(params, "resume", False):
         encoder, decoder, critic_x, critic_z = resume_ckpt(params)
     history = train_tadgan_resident(dataset, encoder, decoder, critic_x, critic_z, params.epochs, params, PATH, seed, log, first_signal)
-    for name, m in (("encoder", encoder), ("decoder", decoder), ("critic_x", critic_x), ("critic_z", critic_z)):
-        torch.save(m, PATH + "/{}.pt".format(name))
+    for stem, m in zip(_FILE_STEMS.values(), (encoder, decoder, critic_x, critic_z)):
+        torch.save(m, PATH + "/{}.pt".format(stem))
     return encoder, decoder, critic_x, critic_z, PATH, history
 
 
@@ -930,13 +979,12 @@ def train_signals_resident(datasets, params, names=None, seed=None, init_seed=No
     init_seed = seed if init_seed is None else int(init_seed)
     dev = torch.device("cuda", torch.cuda.current_device())
     n_critics, n_epochs = 5, params.epochs
-    engines = []
+    writer = _CheckpointWriter(dev, max_jobs=2)
+    groups = []                                                  # (_ResidentGroup, its signals' indices, their module objects)
     for first, members in plan:
         k = len(members)
         nb = counts[members[0]] // B
-        eng = Engine(S, L, B, hyp, k, dev, lr=params.lr, gen_weight_decay=1e-5 if hyp else 0.0, gen_stabilize=10 if hyp else 0, seed=seed,
-                     first_signal=first)
-        eng.epoch_flags = int(getattr(params, "epoch_flags", 0))      # hypad_epoch_io.flags (A/B forms of the critic phase; tests)
+        eng = _reference_engine(params, hyp, k, dev, seed, first)
         nmax = max(counts[i] for i in members)
         templates = []
         x = torch.zeros(k, nmax, S, dtype=torch.float32, device=dev)
@@ -953,12 +1001,9 @@ def train_signals_resident(datasets, params, names=None, seed=None, init_seed=No
                 if host.shape != eng.params[net].shape:
                     raise _C.HypadError(f"arena layout mismatch for {net}: {tuple(host.shape)} vs {tuple(eng.params[net].shape)}")
                 eng.params[net].copy_(host)
-        in_graph = nmax <= eng.SHUFFLE_MAX_WINDOWS
         ri = torch.empty(k, n_critics + 1, nb * B, dtype=torch.int32, device=dev)
-        gens = None if in_graph else [_host_shuffle_generator(dev, eng.seed, first + s) for s in range(k)]
-        engines.append(dict(eng=eng, members=members, nb=nb, x=x, ri=ri, in_graph=in_graph, gens=gens, counts=[counts[i] for i in members], templates=templates,
-                            back=[torch.empty(k * (2 * n_critics + 1) * nb * 4 + 8, dtype=torch.float32).pin_memory() for _ in range(2)],
-                            done=[torch.cuda.Event() for _ in range(2)], snaps={}))
+        groups.append((_ResidentGroup(eng, x, ri, [counts[i] for i in members], nb, lambda eng=eng: writer.snapshot(eng.params), 0, n_critics),
+                       members, templates))
     torch.manual_seed(seed)
     hist = {names[i]: SimpleNamespace(cx=[], cz=[], dec=[], hyper=[], mse=[], repairs=0) for _, ms in plan for i in ms}
     paths = {}
@@ -970,26 +1015,19 @@ def train_signals_resident(datasets, params, names=None, seed=None, init_seed=No
             if save:
                 os.makedirs(paths[names[i]], exist_ok=True)
 
-    NETS = ("enc", "dec", "cx", "cz")
-    FILES = dict(enc="encoder", dec="decoder", cx="critic_x", cz="critic_z")
-    writer = _CheckpointWriter(dev, max_jobs=2)
-    saves = lambda e: save and (((e + 1) % 10 == 0) or ((e + 1) == (n_epochs - 1)))        # train.py:381 (cadence kept as is; e + 1 = actual_epoch)
+    saves = lambda e: save and _saves_checkpoint(0, e, n_epochs)
     # Every group's epoch is one graph replay; its per-iteration losses and the counters come back in ONE copy per group -- looked at
-    # one epoch later, when the next epoch is already queued -- and each model's epoch means are taken from them on the host
-    # (_resident_epoch_means, slot by slot: the bits train_tadgan_resident gets for its one model).  The round-4 loop read 4 values
-    # per model and epoch with a synchronising float() each: 9.2 ms per epoch of 32 models against 6.0 for the launches alone.
-    # Groups whose shuffles are drawn on the host (signals beyond the in-graph sort's 4 096 windows) are finished epoch by epoch: a
-    # repair repeats epochs from the buffers as they are then.
-    pipelined = all(g["in_graph"] for g in engines)
+    # one epoch later, when the next epoch is already queued (_run_resident_epochs) -- and each model's epoch means are taken from them
+    # on the host (_resident_epoch_means, slot by slot: the bits train_tadgan_resident gets for its one model).  The round-4 loop read 4
+    # values per model and epoch with a synchronising float() each: 9.2 ms per epoch of 32 models against 6.0 for the launches alone.
     # Small groups -- signals of many different lengths leave plan_signal_groups with few models per batch count -- are latency-bound
     # one by one (an epoch of 4 models takes 3.2 ms, of 32 models 5.8): dealt over LANES (streams that really run beside each other,
     # hypad_amd/streams.py) their epochs overlap.  Measured, epochs of all groups: 8 groups of 4 models 25.5 -> 8.9 ms on four lanes, 8 x 1
     # model 23.2 -> 6.4, 4 x 8 models 13.3 -> 7.9 on two.  At most 16 models run at any time (their resident critic launches hold 8 CUs
     # per model and need the other half of the chip for their record producers), so a group of more than 8 models keeps the GPU alone.
-    from contextlib import nullcontext
-    biggest = max((len(g["members"]) for g in engines), default=1)
+    biggest = max((len(members) for _, members, _ in groups), default=1)
     active_limit = max(1, torch.cuda.get_device_properties(dev).multi_processor_count // 16)      # models whose critics fill half the CUs: 16 on an MI355X
-    n_lanes = max(1, min(4, active_limit // biggest, len(engines))) if len(engines) > 1 else 1
+    n_lanes = max(1, min(4, active_limit // biggest, len(groups))) if len(groups) > 1 else 1
     if getattr(params, "lanes", None) is not None:               # (A/B timing, tests)
         n_lanes = max(1, min(int(params.lanes), n_lanes))
     lane_streams = []
@@ -999,98 +1037,53 @@ def train_signals_resident(datasets, params, names=None, seed=None, init_seed=No
         here = torch.cuda.current_stream()
         for st in lane_streams:
             st.wait_stream(here)                                 # (the groups' data went up on this stream)
-    for i, g in enumerate(engines):
-        g["lane"] = lane_streams[i % n_lanes] if lane_streams else None
-        if lane_streams:
+        for i, (g, _, _) in enumerate(groups):
+            g.lane = lane_streams[i % n_lanes]
             # several resident critic launches at once: their workgroups in id order (dealt evenly over the XCDs, 16 per XCD at the 16-model
             # limit) instead of a critic's chunks packed onto one XCD -- packed, every launch would want the SAME first XCDs (32 workgroups
             # on a 32-CU XCD at the limit: no slack for whatever else the dispatcher put there).  Same bits (hypad.h: HYPAD_EPOCH_ID_ORDER).
-            g["eng"].epoch_flags |= _C.EPOCH_ID_ORDER
-    on_lane = lambda g: torch.cuda.stream(g["lane"]) if g["lane"] is not None else nullcontext()
+            g.eng.epoch_flags |= _C.EPOCH_ID_ORDER
 
-    def enqueue(e):
-        for g in engines:
-            with on_lane(g):
-                enqueue_group(g, e)
-
-    def enqueue_group(g, e):
-        eng = g["eng"]
-        if not g["in_graph"]:
-            for s_, c in enumerate(g["counts"]):
-                g["ri"][s_].copy_(torch.rand(n_critics + 1, c, device=dev, generator=g["gens"][s_]).argsort(dim=1)[:, : g["nb"] * B])
-        g["losses"] = eng.train_epoch_graph(g["x"], g["ri"], g["nb"], n_critics, True, shuffle_windows=g["counts"] if g["in_graph"] else 0)
-        b, n = g["back"][e % 2], g["losses"].numel()
-        b[:n].copy_(g["losses"].view(-1), non_blocking=True)
-        b[n:].view(torch.int32).copy_(eng.counters, non_blocking=True)
-        g["done"][e % 2].record()
-        if saves(e):
-            g["snaps"][e] = writer.snapshot(eng.params)          # epoch e's weights, before epoch e + 1 is queued
+    def files(members, templates, suffix):
+        return [(templates[slot][net], net, slot, paths[names[i]] + "/{}{}.pt".format(stem, suffix))
+                for slot, i in enumerate(members) for net, stem in _FILE_STEMS.items()]
 
     def finish(e):
-        for g in engines:
-            eng, k, nb = g["eng"], len(g["members"]), g["nb"]
-            g["done"][e % 2].synchronize()
-            b, n = g["back"][e % 2], g["losses"].numel()
-            if e > g.get("repaired_until", -1):
-                if int(b[n:].view(torch.int32)[4]) != 0:             # the resident critic launch gave up: this epoch and the one queued behind it were no-ops
-                    kept = {}
-
-                    def redo(i, g=g, e=e, kept=kept):
-                        kept[e + i] = g["losses"].detach().cpu()     # (the repeat's losses: the buffer is the next repeat's too)
-                        if e + i in g["snaps"]:
-                            g["snaps"][e + i] = writer.snapshot(g["eng"].params)
-                    with on_lane(g):                                 # (the repeats on the group's own stream, behind whatever it still holds)
-                        eng.check_status(on_epoch=redo)
-                    g["repaired"] = kept
-                    g["repaired_until"] = max(kept) if kept else e
-                    for i in g["members"]:                           # (every model of the group went through the repeat)
-                        hist[names[i]].repairs += 1
-                else:
-                    eng.confirm_epochs(1)
-            rows = g["repaired"][e].view(k, -1, 4) if e <= g.get("repaired_until", -1) and e in g.get("repaired", {}) else b[:n].view(k, -1, 4)
-            for slot, i in enumerate(g["members"]):
+        for g, members, templates in groups:
+            rows, repaired = g.collect(e)
+            for slot, i in enumerate(members):
                 h = hist[names[i]]
-                cx_, cz_, dec_, aux_ = _resident_epoch_means(rows[slot], n_critics, nb)
+                h.repairs += int(repaired)                           # (every model of the group went through the repeat)
+                cx_, cz_, dec_, aux_ = _resident_epoch_means(rows[slot], n_critics, g.n_batches)
                 h.cx.append(cx_); h.cz.append(cz_); h.dec.append(dec_)
                 (h.hyper if hyp else h.mse).append(aux_)
             if saves(e):
-                pick = [(g["templates"][slot][net], net, slot, paths[names[i]] + "/{}_{}.pt".format(FILES[net], e + 1))
-                        for slot, i in enumerate(g["members"]) for net in NETS]
-                writer.submit(g["snaps"].pop(e), None, pick)
+                writer.submit(g.snaps.pop(e), None, files(members, templates, "_{}".format(e + 1)))
         if log:
-            mine = [names[i] for g in engines for i in g["members"]]
+            mine = [names[i] for _, members, _ in groups for i in members]
             log("epoch {}: {} signal(s) on rank {}: mean critic x loss {:.3f} critic z loss {:.3f} decoder loss {:.3f}".format(
                 e, len(mine), rank, *(float(np.mean([getattr(hist[n], k)[-1] for n in mine])) if mine else float("nan") for k in ("cx", "cz", "dec"))))
 
     try:
-        for epoch in range(n_epochs):
-            enqueue(epoch)
-            if not pipelined:
-                finish(epoch)
-            elif epoch > 0:
-                finish(epoch - 1)
-        if pipelined and n_epochs > 0:
-            finish(n_epochs - 1)
+        _run_resident_epochs([g for g, _, _ in groups], n_epochs, saves, finish)
         # the final weights: into the signals' own module objects (the result), and -- train.py:461-464 -- their files
-        last = {}
-        for g in engines:
-            with on_lane(g):
-                last[id(g)] = writer.snapshot(g["eng"].params)
+        last = []
+        for g, _, _ in groups:
+            with g.on_lane():
+                last.append(g.snapshot())
         for st in lane_streams:
             torch.cuda.current_stream().wait_stream(st)         # (what follows on this stream reads the groups' weights)
         if save:
-            for g in engines:
-                writer.submit(last[id(g)], None, [(g["templates"][slot][net], net, slot, paths[names[i]] + "/{}.pt".format(FILES[net]))
-                                                  for slot, i in enumerate(g["members"]) for net in NETS])
+            for snap, (_, members, templates) in zip(last, groups):
+                writer.submit(snap, None, files(members, templates, ""))
     finally:
         writer.close()
-    local = {}
-    for g in engines:
-        snap = last[id(g)][0]
-        for slot, i in enumerate(g["members"]):
+    local, modules = {}, {}
+    for (snap, _), (_, members, templates) in zip(last, groups):
+        for slot, i in enumerate(members):
             mods = []
-            for net in NETS:
-                m = g["templates"][slot][net]
+            for net in _FILE_STEMS:
+                m = templates[slot][net]
                 if not next(m.parameters()).is_cuda:
                     m.to(dev)
                 m.arena().data.copy_(snap[net][slot])
@@ -1098,9 +1091,8 @@ def train_signals_resident(datasets, params, names=None, seed=None, init_seed=No
             h = hist[names[i]]
             local[names[i]] = {"path": paths[names[i]], "history": vars(h), "stream": stream[i], "rank": rank,
                                "final": {k: (getattr(h, k)[-1] if getattr(h, k) else None) for k in ("cx", "cz", "dec", "hyper", "mse")}}
-            g.setdefault("mods", {})[names[i]] = mods
+            modules[names[i]] = mods
     merged = par.gather_signal_metrics(local, process_group)
-    for g in engines:
-        for n, mods in g.get("mods", {}).items():
-            merged[n] = dict(merged[n], modules=mods)
+    for n, mods in modules.items():
+        merged[n] = dict(merged[n], modules=mods)
     return merged
