@@ -1,4 +1,4 @@
-// Shared definitions of the training kernels (train_iters.hip, critic_fused.hip): workspace layouts, kernel arguments,
+// Shared definitions of the training kernels (train_iters.hip, dw_adam.hip, critic_fused.hip): workspace layouts, kernel arguments,
 // LDS plans, Adam / Riemannian-Adam update rules.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -70,7 +70,7 @@ inline int64_t ws_pack_offset(const hypad_dims& d) {
   int64_t c = gen_ws(d.batch, d.signal_shape, d.latent_dim).total;
   return ((a > c ? a : c) + 63) & ~(int64_t)63;
 }
-// ... and the generator's dW + Adam work-item records follow the packed copies (train_iters.hip DwItem: 32 words per item, room for
+// ... and the generator's dW + Adam work-item records follow the packed copies (dw_adam.hip DwItem: 32 words per item, room for
 // DW_ITEM_CAP items; the launches read signal 0's copy): what a wave of that launch needs to know, prepared once per pack launch
 constexpr int DW_ITEM_WORDS = 32, DW_ITEM_CAP = 2048;
 inline int64_t ws_items_offset(const hypad_dims& d) {
@@ -259,6 +259,18 @@ int critic_phase_record_info(const hypad_dims& d, int n_iters, int critic, hypad
 // train_iters.hip: the pack launch (pack_generator_kernel) as the scoring forward pass uses it (score_forward.hip) -- the packed copies
 // of d.n_signals generators into a.ws + signal * a.ws_sig_stride + a.pk_off, with_critic: the padded critic_x image behind each
 int launch_pack_generator(const IterArgs& a, const hypad_dims& d, hipStream_t s, bool with_critic);
+
+// dw_adam.hip: the weight-gradient + Adam launch that closes an iteration of train_iters.hip.  `a`: the iteration's arguments as its other
+// launches take them (fill_args); each returns HYPAD_OK or the launch's error.
+bool dw_tables_fit(const hypad_dims& d);                                                        // the descriptor tables of these dimensions fit
+int launch_dw_critic(const IterArgs& a, int n_signals, hipStream_t s);                          // one critic (a.opt: 0 critic_x, 1 critic_z)
+int launch_dw_critic_pair(const IterArgs& ax, const IterArgs& az, int n_signals, hipStream_t s);   // critic_x || critic_z, blockIdx.z picks
+// the generator's work-item records into signal 0's workspace (behind every pack launch that generator steps follow), and a step's launch
+// over the models [a.sig0, a.sig0 + nsig) from them; with_decay = false: without the decay-only tensors, which launch_decay_steps advances
+// by `nsteps` steps at once.  flags: hypad_epoch_io.flags (HYPAD_EPOCH_DW_* pick the placement); reps: launches back to back (profiling)
+int launch_dw_items(const IterArgs& a, const hypad_dims& d, bool with_decay, hipStream_t s);
+int launch_dw_gen(const IterArgs& a, const hypad_dims& d, bool with_decay, int nsig, int flags, int reps, hipStream_t s);
+int launch_decay_steps(const IterArgs& a, const hypad_dims& d, int nsteps, hipStream_t s);
 
 }  // namespace train
 }  // namespace hypad
