@@ -48,6 +48,7 @@ ACT_NONE, ACT_TANH, ACT_LEAKY02 = 0, 1, 2
 ML_HYPER_INPUT, ML_HYPER_BIAS = 1, 2                # HYPAD_ML_*
 NONLIN_NONE, NONLIN_TANH, NONLIN_RELU = 0, 1, 2    # HYPAD_NONLIN_*
 D2P_SIGNED, D2P_SCALED = 1, 2                       # HYPAD_D2P_*
+MID_LINCOMB, MID_POSWEIGHT, MID_COADD = 1, 2, 4     # HYPAD_MID_*
 COMB = {"sum": 0, "mult": 1, "uncertainty": 2, "critic": 3, "critic_uncertainty": 4, "sum_uncertainty": 5, "rec": 6,
         "rec_uncertainty": 7, "eucl_mult": 8, "eucl_sum": 9}
 
@@ -133,6 +134,14 @@ _SIGS = {
     "hypad_dist2plane_bwd": (c_int, [P, P, P, P, P, P, P, P, P, P, P, c_size_t, c_int64, c_int, c_int, c_int, P]),
     "hypad_mobius_pointwise_mul_fwd": (c_int, [P, P, P, c_int64, c_int, c_int64, P]),
     "hypad_mobius_pointwise_mul_bwd": (c_int, [P, P, P, P, P, c_int64, c_int, c_int64, P]),
+    "hypad_mobius_scalar_mul_fwd": (c_int, [P, P, P, c_int64, c_int, c_int64, P]),
+    "hypad_mobius_scalar_mul_bwd": (c_int, [P, P, P, P, P, c_int64, c_int, c_int64, P]),
+    "hypad_weighted_midpoint_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int]),
+    "hypad_weighted_midpoint_fwd": (c_int, [P, P, c_int64, P, P, c_void_p, c_size_t, c_int64, c_int64, c_int, c_int, P]),
+    "hypad_weighted_midpoint_bwd": (c_int, [P, P, c_int64, P, P, P, P, c_void_p, c_size_t, c_int64, c_int64, c_int, c_int, P]),
+    "hypad_weighted_midpoint_bmm_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int]),
+    "hypad_weighted_midpoint_bmm_fwd": (c_int, [P, P, P, P, c_int64, c_int64, c_int64, c_int, c_int, P]),
+    "hypad_weighted_midpoint_bmm_bwd": (c_int, [P, P, P, P, P, P, c_void_p, c_size_t, c_int64, c_int64, c_int64, c_int, c_int, P]),
     "hypad_mobius_gru_workspace_bytes": (c_size_t, [c_int, c_int64, c_int, c_int]),
     "hypad_mobius_gru_fwd": (c_int, [P] * 7 + [c_void_p, c_size_t, c_int, c_int64, c_int, c_int, c_int, P]),
     "hypad_mobius_gru_bwd": (c_int, [P] * 14 + [c_void_p, c_size_t, c_int, c_int64, c_int, c_int, c_int, P]),

@@ -369,6 +369,82 @@ __device__ __forceinline__ void mobius_pointwise_mul_bwd_d(const R& w, const R& 
   HYPAD_ROW_EACH { dw.v[e] = dwx.v[e] * x.v[e]; dx.v[e] = dwx.v[e] * w.v[e] + c * x.v[e]; }
 }
 
+// mobius_scalar_mul (math_.py:853-858): tanh(r artanh |x|) x / |x| -- mobius_scaled_row's scaling with the scalar r in place of
+// |m| / |x|, built from the same clamped maps; r may be negative, so the tanh clamp is two-sided here.  The backward returns dL/dr.
+__device__ __forceinline__ double tanh_clamped2_d(double x) { return tanh(fmax(fmin(x, (double)TANH_CLAMP), -(double)TANH_CLAMP)); }
+__device__ __forceinline__ double tanh_prime2_d(double x, double t) { return fabs(x) <= (double)TANH_CLAMP ? 1.0 - t * t : 0.0; }
+template <class R>
+__device__ __forceinline__ R mobius_scalar_mul_d(double r, const R& x) {
+  const double n = fmax(sqrt(rowd_dot(x, x)), (double)MIN_NORM);
+  const double s = tanh_clamped2_d(r * artanh_clamped_d(n)) / n;
+  R o;
+#pragma unroll
+  HYPAD_ROW_EACH o.v[e] = s * x.v[e];
+  return o;
+}
+template <class R>
+__device__ __forceinline__ double mobius_scalar_mul_bwd_d(double r, const R& x, const R& go, R& dx) {
+  const double raw = sqrt(rowd_dot(x, x));
+  const double n = fmax(raw, (double)MIN_NORM);
+  const double a = artanh_clamped_d(n), u = r * a;
+  const double t = tanh_clamped2_d(u), tp = tanh_prime2_d(u, t);
+  const double s = t / n, gs = rowd_dot(go, x);                  // d L / d s
+  const double dsdn = (tp * r * artanh_prime_d(n) * n - t) / (n * n);
+  const double c = raw >= (double)MIN_NORM ? gs * dsdn / n : 0.0;
+#pragma unroll
+  HYPAD_ROW_EACH dx.v[e] = s * go.v[e] + c * x.v[e];
+  return gs * tp * a / n;
+}
+
+// The weighted gyromidpoint after its sums (math_.py:2051-2061,2084 and :2114-2122): t = nom / den', the halving
+// t / (1 + sqrt(1 - |t|^2)), mobius_scalar_mul by r (lincomb), project.  den' = max(den, 1e-10) in the bmm form, clamp_abs(den, 1e-10)
+// = den + 1e-10 (den is a sum of non-negative terms) in the reduce form.  Backward: g_nom = g_t / den', dL/d den (0 where the clamp or
+// the zero of |.| holds it) and dL/dr.
+struct MidpointCfg { bool halve, lincomb, project, clamp_abs; };
+constexpr double MIDPOINT_DEN_EPS = 1e-10;
+__device__ __forceinline__ double midpoint_den(double den, bool clamp_abs) {
+  return clamp_abs ? den + MIDPOINT_DEN_EPS : fmax(den, MIDPOINT_DEN_EPS);
+}
+template <class R>
+__device__ __forceinline__ R midpoint_tail_d(const R& nom, double den, double r, const MidpointCfg c) {
+  const double rd = 1.0 / midpoint_den(den, c.clamp_abs);
+  R a;
+#pragma unroll
+  HYPAD_ROW_EACH a.v[e] = nom.v[e] * rd;
+  if (c.halve) {
+    const double f = 1.0 / (1.0 + sqrt(1.0 - rowd_dot(a, a)));
+#pragma unroll
+    HYPAD_ROW_EACH a.v[e] *= f;
+  }
+  if (c.lincomb) a = mobius_scalar_mul_d(r, a);
+  return c.project ? project_d(a) : a;
+}
+template <class R>
+__device__ __forceinline__ void midpoint_tail_bwd_d(const R& nom, double den, double r, const MidpointCfg c, const R& go, R& gnom, double& gden,
+                                                    double& gr) {
+  const double rd = 1.0 / midpoint_den(den, c.clamp_abs);
+  R t, a;
+#pragma unroll
+  HYPAD_ROW_EACH t.v[e] = nom.v[e] * rd;
+  double f = 1.0, root = 1.0;
+  if (c.halve) { root = sqrt(1.0 - rowd_dot(t, t)); f = 1.0 / (1.0 + root); }
+#pragma unroll
+  HYPAD_ROW_EACH a.v[e] = t.v[e] * f;
+  R g = go;
+  gr = 0.0;
+  if (c.project) g = project_bwd_d(c.lincomb ? mobius_scalar_mul_d(r, a) : a, g);
+  if (c.lincomb) { R ga; gr = mobius_scalar_mul_bwd_d(r, a, g, ga); g = ga; }
+  if (c.halve) {                                                 // a = t f(|t|^2), f' = f^2 / (2 root)
+    const double s = rowd_dot(g, t) * f * f / root;              // 2 g_s2
+#pragma unroll
+    HYPAD_ROW_EACH g.v[e] = f * g.v[e] + s * t.v[e];
+  }
+#pragma unroll
+  HYPAD_ROW_EACH gnom.v[e] = g.v[e] * rd;
+  const bool flows = c.clamp_abs ? den > 0.0 : den >= MIDPOINT_DEN_EPS;
+  gden = flows ? -rowd_dot(g, t) * rd : 0.0;
+}
+
 // The GRU gate sigmoid(logmap0(y)) (hyrnn_nets.py:81-82).  (Columns past the row's end come out as 0.5: every use multiplies them
 // with a zero of the other operand before a sum is taken.)
 template <class R>

@@ -6,6 +6,9 @@ logmap0 (:1267-1270), mobius_add (:536-555), project (:340-352), plus the inline
 train.py:226-230 and the hyperbolic loss of train.py:232.  Each is one HIP kernel forward and one backward.
 dist2plane (:1599-1666) is the function behind hyrnn_nets.MobiusDist2Hyperplane: one HIP launch forward, a HIP backward.
 mobius_pointwise_mul (:1328-1371) is the gate product of the Moebius GRU (hyrnn_nets.mobius_gru_cell), here on its own.
+weighted_midpoint (:1953-2087) and weighted_midpoint_bmm (:2090-2122) turn many ball points into one -- pooling over dimensions of one
+tensor, and weights (..., N, M) against xs (..., M, D) for attention and aggregation; mobius_scalar_mul (:788-858) is their lincomb step
+and an op of its own.  HIP kernels forward and backward (docs/history/weighted_midpoint.md).
 """
 import torch
 
@@ -160,6 +163,212 @@ def mobius_pointwise_mul(w, x, *, k=None, dim=-1):
     if x.shape[-1] > 256:
         raise NotImplementedError(f"mobius_pointwise_mul: rows of {x.shape[-1]} elements are not implemented; {_PMUL_SUPPORTED}")
     return _MobiusPointwiseMul.apply(w.reshape(1, -1) if one_row and w.shape != x.shape else w, x)
+
+
+class _MobiusScalarMul(torch.autograd.Function):
+    """hypad_mobius_scalar_mul_*: r of one element, or of one element per row of x."""
+
+    @staticmethod
+    def forward(ctx, r, x):
+        x, x2 = _rows(x)
+        r1 = _C.require_cuda(r.to(torch.float32).contiguous().reshape(-1), "r")
+        out = torch.empty_like(x2)
+        _C.check(_C.lib.hypad_mobius_scalar_mul_fwd(_C.ptr(r1), _C.ptr(x2), _C.ptr(out), x2.shape[0], x2.shape[1], r1.shape[0], _C.stream()),
+                 "mobius_scalar_mul_fwd")
+        ctx.save_for_backward(r1, x2)
+        ctx.rs, ctx.xs = r.shape, x.shape
+        return out.view(x.shape)
+
+    @staticmethod
+    @_C.first_order_only
+    def backward(ctx, go):
+        r1, x2 = ctx.saved_tensors
+        rows = x2.shape[0]
+        go2 = go.to(torch.float32).contiguous().reshape(x2.shape)
+        gr = torch.empty(rows, device=x2.device, dtype=torch.float32) if ctx.needs_input_grad[0] else None
+        gx = torch.empty_like(x2) if ctx.needs_input_grad[1] else None
+        _C.check(_C.lib.hypad_mobius_scalar_mul_bwd(_C.ptr(r1), _C.ptr(x2), _C.ptr(go2), _C.ptr(gr), _C.ptr(gx), rows, x2.shape[1], r1.shape[0],
+                                                    _C.stream()), "mobius_scalar_mul_bwd")
+        if gr is not None and r1.shape[0] == 1 and rows != 1:      # one r for every row: the rows' contributions, added in a fixed order
+            red = torch.empty(1, device=x2.device, dtype=torch.float32)
+            _C.check(_C.lib.hypad_column_sum(_C.ptr(gr), _C.ptr(red), rows, 1, _C.stream()))
+            gr = red
+        return None if gr is None else gr.view(ctx.rs), None if gx is None else gx.view(ctx.xs)
+
+
+_SMUL_SUPPORTED = "supported: k = -1, dim = -1, fp32, r of one element or of shape x.shape[:-1] + (1,), rows of at most 256 elements"
+
+
+def mobius_scalar_mul(r, x, *, k=None, dim=-1):
+    """r (x) x = tanh(r artanh |x|) x / |x| for ball-valued rows of x (math_.py:788-858) at k = -1: one HIP launch forward and one
+    backward, first-order differentiable in r and x.  r is a tensor of one element (or a number) or holds one value per row of x,
+    shape x.shape[:-1] + (1,)."""
+    if k is not None and abs(float(k) + 1.0) > 1e-12:
+        raise NotImplementedError(f"mobius_scalar_mul: curvature k = {float(k)} is not implemented; {_SMUL_SUPPORTED}")
+    if dim != -1 and dim != x.dim() - 1:
+        raise NotImplementedError(f"mobius_scalar_mul: dim = {dim} is not implemented; {_SMUL_SUPPORTED}")
+    if x.dim() < 1 or x.shape[-1] > 256:
+        raise NotImplementedError(f"mobius_scalar_mul: x {tuple(x.shape)} is not implemented; {_SMUL_SUPPORTED}")
+    if not isinstance(r, torch.Tensor):
+        r = torch.tensor(float(r), dtype=torch.float32, device=x.device)
+    if r.numel() != 1 and tuple(r.shape) != tuple(x.shape[:-1]) + (1,):
+        raise NotImplementedError(f"mobius_scalar_mul: r {tuple(r.shape)} against x {tuple(x.shape)} is not implemented; {_SMUL_SUPPORTED}")
+    return _MobiusScalarMul.apply(r, x)
+
+
+class _WeightedMidpointBmm(torch.autograd.Function):
+    """hypad_weighted_midpoint_bmm_*: xs (batch, M, D), weights (batch, N, M) -> (batch, N, D); saves the operands and
+    [nom | den | alpha] (batch, N, D + 2)."""
+
+    @staticmethod
+    def forward(ctx, xs, weights, flags):
+        xs = _C.require_cuda(xs.contiguous(), "xs")
+        weights = _C.require_cuda(weights.contiguous(), "weights")
+        batch, m, d = xs.shape
+        n = weights.shape[1]
+        out = torch.empty(batch, n, d, device=xs.device, dtype=torch.float32)
+        train = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        saved = torch.empty(batch, n, d + 2, device=xs.device, dtype=torch.float32) if train else None
+        _C.check(_C.lib.hypad_weighted_midpoint_bmm_fwd(_C.ptr(xs), _C.ptr(weights), _C.ptr(out), _C.ptr(saved), batch, n, m, d, flags, _C.stream()),
+                 "weighted_midpoint_bmm_fwd")
+        if train:
+            ctx.save_for_backward(xs, weights, saved)
+        ctx.flags = flags
+        return out
+
+    @staticmethod
+    @_C.first_order_only
+    def backward(ctx, go):
+        xs, weights, saved = ctx.saved_tensors
+        batch, m, d = xs.shape
+        n = weights.shape[1]
+        go = go.to(torch.float32).contiguous()
+        gx = torch.empty_like(xs) if ctx.needs_input_grad[0] else None
+        gw = torch.empty_like(weights) if ctx.needs_input_grad[1] else None
+        nbytes = _C.lib.hypad_weighted_midpoint_bmm_workspace_bytes(batch, n, m, d)
+        ws = torch.empty(max(nbytes // 4, 1), device=xs.device, dtype=torch.float32)
+        _C.check(_C.lib.hypad_weighted_midpoint_bmm_bwd(_C.ptr(xs), _C.ptr(weights), _C.ptr(saved), _C.ptr(go), _C.ptr(gx), _C.ptr(gw), _C.ptr(ws),
+                                                        nbytes, batch, n, m, d, ctx.flags, _C.stream()), "weighted_midpoint_bmm_bwd")
+        return gx, gw, None
+
+
+_BMM_SUPPORTED = ("supported: k = -1, fp32, xs (..., M, D) against weights (..., N, M) with the same leading batch dimensions on both, or "
+                  "none on one of them, D <= 256")
+
+
+def weighted_midpoint_bmm(xs, weights, k, lincomb=False):
+    """The weighted Moebius gyromidpoint of the points xs (..., M, D) under every row of weights (..., N, M) -> (..., N, D)
+    (math_.py:2090-2122) at k = -1: the aggregation step of a hyperbolic attention or graph layer.  One HIP launch forward on fp32
+    MFMA; first-order differentiable in xs and weights.  Both operands carry the same leading batch dimensions, or one of them carries
+    none: that operand is expanded over the batch and materialised on the host, and the sum of its gradient over the batch is left
+    to autograd (the expand's backward)."""
+    if k is not None and abs(float(k) + 1.0) > 1e-12:
+        raise NotImplementedError(f"weighted_midpoint_bmm: curvature k = {float(k)} is not implemented; {_BMM_SUPPORTED}")
+    bx, bw = tuple(xs.shape[:-2]), tuple(weights.shape[:-2])
+    if (xs.dim() < 2 or weights.dim() < 2 or weights.shape[-1] != xs.shape[-2] or (bx != bw and bx != () and bw != ())
+            or xs.dtype != torch.float32 or weights.dtype != torch.float32):
+        raise NotImplementedError(f"weighted_midpoint_bmm: xs {tuple(xs.shape)} {xs.dtype} against weights {tuple(weights.shape)} "
+                                  f"{weights.dtype} is not implemented; {_BMM_SUPPORTED}")
+    if xs.shape[-1] > 256:
+        raise NotImplementedError(f"weighted_midpoint_bmm: D = {xs.shape[-1]} is not implemented; {_BMM_SUPPORTED}")
+    lead = bx or bw
+    if bx != lead:
+        xs = xs.expand(*lead, *xs.shape[-2:])
+    if bw != lead:
+        weights = weights.expand(*lead, *weights.shape[-2:])
+    out = _WeightedMidpointBmm.apply(xs.reshape(-1, *xs.shape[-2:]), weights.reshape(-1, *weights.shape[-2:]), _C.MID_LINCOMB if lincomb else 0)
+    return out.view(*lead, weights.shape[-2], xs.shape[-1])
+
+
+class _WeightedMidpoint(torch.autograd.Function):
+    """hypad_weighted_midpoint_*: xs (M, R, D), weights (M, R), of one element, or None -> (R, D); saves the operands and
+    [nom | den | alpha] (R, D + 2) in fp64."""
+
+    @staticmethod
+    def forward(ctx, xs, weights, flags):
+        xs = _C.require_cuda(xs.contiguous(), "xs")
+        m, r, d = xs.shape
+        w = None if weights is None else _C.require_cuda(weights.contiguous().reshape(-1), "weights")
+        wn = 0 if w is None else w.shape[0]
+        out = torch.empty(r, d, device=xs.device, dtype=torch.float32)
+        train = ctx.needs_input_grad[0] or (w is not None and ctx.needs_input_grad[1])
+        saved = torch.empty(r, d + 2, device=xs.device, dtype=torch.float64) if train else None
+        nbytes = _C.lib.hypad_weighted_midpoint_workspace_bytes(m, r, d)
+        ws = torch.empty(max(nbytes // 4, 1), device=xs.device, dtype=torch.float32)
+        _C.check(_C.lib.hypad_weighted_midpoint_fwd(_C.ptr(xs), _C.ptr(w), wn, _C.ptr(out), _C.ptr(saved), _C.ptr(ws), nbytes, m, r, d, flags,
+                                                    _C.stream()), "weighted_midpoint_fwd")
+        if train:
+            ctx.save_for_backward(xs, saved, *(() if w is None else (w,)))
+        ctx.flags, ctx.wshape = flags, None if weights is None else weights.shape
+        return out
+
+    @staticmethod
+    @_C.first_order_only
+    def backward(ctx, go):
+        xs, saved, *rest = ctx.saved_tensors
+        w = rest[0] if rest else None
+        m, r, d = xs.shape
+        go = go.to(torch.float32).contiguous()
+        gx = torch.empty_like(xs) if ctx.needs_input_grad[0] else None
+        gw = torch.empty_like(w) if w is not None and ctx.needs_input_grad[1] else None
+        nbytes = _C.lib.hypad_weighted_midpoint_workspace_bytes(m, r, d)
+        ws = torch.empty(max(nbytes // 4, 1), device=xs.device, dtype=torch.float32)
+        _C.check(_C.lib.hypad_weighted_midpoint_bwd(_C.ptr(xs), _C.ptr(w), 0 if w is None else w.shape[0], _C.ptr(saved), _C.ptr(go), _C.ptr(gx),
+                                                    _C.ptr(gw), _C.ptr(ws), nbytes, m, r, d, ctx.flags, _C.stream()), "weighted_midpoint_bwd")
+        return gx, None if gw is None else gw.view(ctx.wshape), None
+
+
+_MID_SUPPORTED = ("supported: k = -1, dim = -1, fp32, reducedim among the dimensions of xs before the last, weights None, of one element, or "
+                  "broadcastable to xs.shape[:-1], rows of at most 256 elements")
+
+
+def weighted_midpoint(xs, k, weights=None, reducedim=None, dim=-1, keepdim=False, lincomb=False, posweight=False, coadd=False):
+    """The weighted Moebius gyromidpoint (Einstein midpoint in Poincare coordinates) of the points of xs (..., D) over the dimensions
+    ``reducedim`` (default: all but the last) (math_.py:1953-2087) at k = -1: the pooling step that turns many ball points into one.
+    HIP kernels forward and backward (a wave per kept row, fp64 sums); first-order differentiable in xs and weights.  The reduced
+    dimensions are moved to the front and xs is flattened to (reduced, kept, D) -- a copy only where the layout needs one; weights
+    that broadcast against xs.shape[:-1] are expanded and materialised, which leaves the sum of their gradient to autograd."""
+    if k is not None and abs(float(k) + 1.0) > 1e-12:
+        raise NotImplementedError(f"weighted_midpoint: curvature k = {float(k)} is not implemented; {_MID_SUPPORTED}")
+    if xs.dim() < 1 or (dim != -1 and dim != xs.dim() - 1):
+        raise NotImplementedError(f"weighted_midpoint: dim = {dim} on xs {tuple(xs.shape)} is not implemented; {_MID_SUPPORTED}")
+    nd = xs.dim() - 1
+    if reducedim is None:
+        red = list(range(nd))
+    else:
+        red = [reducedim] if isinstance(reducedim, int) else list(reducedim)
+        red = sorted({int(a) + xs.dim() if int(a) < 0 else int(a) for a in red})
+        if len(red) != len([reducedim] if isinstance(reducedim, int) else list(reducedim)) or any(a < 0 or a >= nd for a in red):
+            raise NotImplementedError(f"weighted_midpoint: reducedim = {reducedim} on xs {tuple(xs.shape)} is not implemented; {_MID_SUPPORTED}")
+    if xs.dtype != torch.float32 or xs.shape[-1] > 256:
+        raise NotImplementedError(f"weighted_midpoint: xs {tuple(xs.shape)} {xs.dtype} is not implemented; {_MID_SUPPORTED}")
+    lead = tuple(xs.shape[:-1])
+    if weights is not None and weights.numel() != 1:
+        try:
+            fits = weights.dtype == torch.float32 and tuple(torch.broadcast_shapes(tuple(weights.shape), lead)) == lead
+        except RuntimeError:
+            fits = False
+        if not fits:
+            raise NotImplementedError(f"weighted_midpoint: weights {tuple(weights.shape)} {weights.dtype} against xs {tuple(xs.shape)} is not "
+                                      f"implemented; {_MID_SUPPORTED}")
+    kept = [a for a in range(nd) if a not in red]
+    m = 1
+    for a in red:
+        m *= xs.shape[a]
+    if m == 0:
+        raise NotImplementedError(f"weighted_midpoint: a midpoint of no points (xs {tuple(xs.shape)}, reducedim {red}) is not implemented")
+    r = 1
+    for a in kept:
+        r *= xs.shape[a]
+    order = red + kept
+    x3 = xs.permute(*order, nd).reshape(m, r, xs.shape[-1])
+    w2 = weights
+    if weights is not None and weights.numel() != 1:
+        w2 = weights.expand(lead).permute(*order).reshape(m, r)
+    flags = (_C.MID_LINCOMB if lincomb else 0) | (_C.MID_POSWEIGHT if posweight else 0) | (_C.MID_COADD if coadd else 0)
+    out = _WeightedMidpoint.apply(x3, w2, flags)
+    shape = [1 if a in red else xs.shape[a] for a in range(nd)] if keepdim else [xs.shape[a] for a in kept]
+    return out.view(*shape, xs.shape[-1])
 
 
 def mobius_fn_apply(fn, x, *args, k=None, dim=-1, **kwargs):

@@ -145,6 +145,58 @@ int hypad_dist2plane_bwd(const float* x, const float* p, const float* a, const f
 int hypad_mobius_pointwise_mul_fwd(const float* w, const float* x, float* out, int64_t rows, int dim, int64_t w_rows, hypad_stream_t stream);
 int hypad_mobius_pointwise_mul_bwd(const float* w, const float* x, const float* grad_out, float* grad_w, float* grad_x,
                                    int64_t rows, int dim, int64_t w_rows, hypad_stream_t stream);
+/* gmath.mobius_scalar_mul  math_.py:788-858 (_mobius_scalar_mul :853-858; tan_k, artan_k with the clamps of :51-59) at k = -1:
+ * tanh(r artanh |x|) x / |x| for ball-valued rows x, |x| clamped at 1e-15; evaluated in fp64 registers, buffers fp32.  r holds one
+ * value per row (r_rows == rows) or one value for every row (r_rows == 1).  bwd: grad_r (rows) receives the per-row dL/dr -- with
+ * r_rows == 1 the contributions to be summed by the caller (hypad_column_sum at dim = 1), as hypad_mobius_pointwise_mul_bwd's grad_w;
+ * grad_r and grad_x may each be NULL.  dim <= 256. */
+int hypad_mobius_scalar_mul_fwd(const float* r, const float* x, float* out, int64_t rows, int dim, int64_t r_rows, hypad_stream_t stream);
+int hypad_mobius_scalar_mul_bwd(const float* r, const float* x, const float* grad_out, float* grad_r, float* grad_x,
+                                int64_t rows, int dim, int64_t r_rows, hypad_stream_t stream);
+/* gmath.weighted_midpoint_bmm  math_.py:2090-2122 (_weighted_midpoint_bmm :2104-2122, _lambda_x :382-383, _project :340-352) at
+ * k = -1: the weighted Moebius gyromidpoint in its attention / aggregation form.  xs (batch, M, D) on the ball, weights
+ * (batch, N, M) of any sign, out (batch, N, D):
+ *   gamma_j = 2 / max(1 - |x_j|^2, 1e-15)    t_i = sum_j w_ij gamma_j x_j / max(sum_j |w_ij| (gamma_j - 1), 1e-10)
+ *   out_i = project(t_i / (1 + sqrt(1 - |t_i|^2))), with HYPAD_MID_LINCOMB project(mobius_scalar_mul(sum_j |w_ij|, .)).
+ * One launch: fp32 MFMA products from an xs chunk staged and scaled in LDS (1 - |x_j|^2 from an fp64 sum), the epilogue in fp64
+ * registers.  saved (batch, N, D + 2) receives [nom | den | alpha] for the backward (NULL: inference, the same bits in out).
+ * bwd: a row pass over the batch N output rows, then grad_weights (contraction over D) and grad_xs (contraction over N) in one launch
+ * each; either may be NULL and the other keeps its bits.  No atomics: two runs give the same bits.  N == 0 launches no row kernel and
+ * writes zeros to grad_xs.  workspace (bwd only): hypad_weighted_midpoint_bmm_workspace_bytes = 4 batch N (D + 2) bytes.
+ * Every argument is validated before anything is launched: HYPAD_EINVAL for a NULL operand, a non-positive size or an unknown flag;
+ * HYPAD_EUNSUPPORTED for D > 256, an element count of 2^31 or more, or LDS that does not fit; HYPAD_EWORKSPACE below the workspace size. */
+enum { HYPAD_MID_LINCOMB = 1, HYPAD_MID_POSWEIGHT = 2, HYPAD_MID_COADD = 4 };
+size_t hypad_weighted_midpoint_bmm_workspace_bytes(int64_t batch, int64_t N, int64_t M, int D);
+int hypad_weighted_midpoint_bmm_fwd(const float* xs, const float* weights, float* out, float* saved /* NULL: inference */,
+                                    int64_t batch, int64_t N, int64_t M, int D, int flags, hypad_stream_t stream);
+int hypad_weighted_midpoint_bmm_bwd(const float* xs, const float* weights, const float* saved, const float* grad_out,
+                                    float* grad_xs, float* grad_weights, void* workspace, size_t workspace_bytes,
+                                    int64_t batch, int64_t N, int64_t M, int D, int flags, hypad_stream_t stream);
+/* gmath.weighted_midpoint  math_.py:1953-2087 (_weighted_midpoint :2027-2087, _antipode :1940-1950, clamp_abs of geoopt.utils) at
+ * k = -1: the weighted Moebius gyromidpoint in its pooling form.  The host presents xs as (M, R, D): M reduced positions of R kept
+ * rows; weights (M, R) (w_count = M R), one value (w_count = 1), or NULL (w_count = 0: every weight 1); out (R, D):
+ *   t = sum_m w_m gamma_m x_m / (sum_m |w_m| (gamma_m - 1) + 1e-10)    out = t / (1 + sqrt(1 - |t|^2))
+ * HYPAD_MID_COADD skips the halving; HYPAD_MID_LINCOMB skips it and applies mobius_scalar_mul(alpha / 2, .) with alpha = sum_m w_m;
+ * HYPAD_MID_POSWEIGHT weighs the antipode -x_m with |w_m| where w_m < 0, which leaves t as it is and makes alpha = sum_m |w_m|.  No
+ * project.  A wave per kept row adds up the positions in fp64 registers; where R alone leaves the device idle, M is cut into slices
+ * -- their number a function of (M, R) alone -- whose partial sums a second launch adds in slice order.  saved (R, D + 2), fp64,
+ * receives [nom | den | alpha] (NULL: inference, the same bits in out): with one point carrying a row, grad_weights is the small
+ * difference of two large terms, which fp32 sums would leave no digits.
+ * bwd: a pass over the R kept rows, then one element-wise launch over the M R rows writes grad_xs (M, R, D) and grad_weights -- (M, R),
+ * or for a single weight the sum of the M R summands in a fixed order; either may be NULL (grad_weights must be NULL without
+ * weights).  No atomics: two runs give the same bits.  R == 0 launches no row kernel and writes a zero to a single weight's gradient.
+ * workspace: hypad_weighted_midpoint_workspace_bytes(M, R, D) at an 8-byte aligned address, for both calls (the forward touches it
+ * only when it slices).
+ * Every argument is validated before anything is launched: HYPAD_EINVAL for a NULL operand, a non-positive size, a w_count that is
+ * none of the three or an unknown flag; HYPAD_EUNSUPPORTED for D > 256 or M R (D + 2) >= 2^31; HYPAD_EWORKSPACE below the workspace
+ * size or off that alignment. */
+size_t hypad_weighted_midpoint_workspace_bytes(int64_t M, int64_t R, int D);
+int hypad_weighted_midpoint_fwd(const float* xs, const float* weights /* NULL: none */, int64_t w_count, float* out,
+                                double* saved /* NULL: inference */, void* workspace, size_t workspace_bytes,
+                                int64_t M, int64_t R, int D, int flags, hypad_stream_t stream);
+int hypad_weighted_midpoint_bwd(const float* xs, const float* weights, int64_t w_count, const double* saved, const float* grad_out,
+                                float* grad_xs, float* grad_weights, void* workspace, size_t workspace_bytes,
+                                int64_t M, int64_t R, int D, int flags, hypad_stream_t stream);
 /* The Moebius GRU  hyperspace/hyrnn_nets.py:61-151 (one_rnn_transform :61-65, mobius_gru_cell :68-91, the equal-length branch of
  * mobius_gru_loop :113-127) at k = -1.  x (steps, rows, in_dim) and h0 (rows, hidden) on the ball, w_ih (3 hidden, in_dim),
  * w_hh (3 hidden, hidden), bias (3, hidden) on the ball, chunk order r, h, z; out (steps, rows, hidden) = the hidden state after
