@@ -445,6 +445,72 @@ __device__ __forceinline__ void midpoint_tail_bwd_d(const R& nom, double den, do
   gden = flows ? -rowd_dot(g, t) * rd : 0.0;
 }
 
+// The geodesic distance (math_.py:861-975).  The pair map of dist_matmul (:942-947) from the three inner products:
+//   num = x2 - 2 xy + y2    den = max(1 - 2 xy + x2 y2, 1e-15)    u = num / den    s = sqrt(max(u, 1e-15))    out = 2 artanh(s)
+// Backward: a = dL/dnum and b = dL/dden of one pair under the incoming gradient g; g_u = g / (s (1 - s^2)), and nothing flows through
+// a clamp that holds (u below 1e-15, s above 1 - 1e-7, den below 1e-15).
+constexpr double DIST_EPS = 1e-15;
+__device__ __forceinline__ double dist_pair_d(double x2, double y2, double xy) {
+  const double num = x2 - 2.0 * xy + y2, den = fmax(1.0 - 2.0 * xy + x2 * y2, DIST_EPS);
+  return 2.0 * artanh_clamped_d(sqrt(fmax(num / den, DIST_EPS)));
+}
+__device__ __forceinline__ void dist_pair_bwd_d(double x2, double y2, double xy, double g, double& a, double& b) {
+  const double num = x2 - 2.0 * xy + y2, draw = 1.0 - 2.0 * xy + x2 * y2;
+  const double rden = 1.0 / fmax(draw, DIST_EPS);
+  const double u = num * rden, s = sqrt(fmax(u, DIST_EPS));
+  const double gu = (u >= DIST_EPS && s <= ARTANH_TOP) ? g / (s * (1.0 - s) * (1.0 + s)) : 0.0;
+  a = gu * rden;
+  b = draw >= DIST_EPS ? -gu * u * rden : 0.0;
+}
+// dist (:893-902): 2 artanh(|(-x) (+) y|), the norm without a clamp.  Two rows that are equal element by element are at distance 0
+// with gradient 0 (the norm's backward at 0, as torch defines it): decided from the rows themselves, because (-x) (+) x is only zero
+// up to the rounding of 1 - 2 |x|^2 + |x|^2 against 1 - |x|^2, and a gradient of size g through a norm of 1e-16 is noise.
+template <class R>
+__device__ __forceinline__ R rowd_neg(const R& x) {
+  R o;
+#pragma unroll
+  HYPAD_ROW_EACH o.v[e] = -x.v[e];
+  return o;
+}
+template <class R>
+__device__ __forceinline__ bool rowd_equal(const R& x, const R& y) {
+  double ne = 0.0;
+#pragma unroll
+  HYPAD_ROW_EACH ne += x.v[e] != y.v[e] ? 1.0 : 0.0;
+  return groupd_sum<R::G>(ne) == 0.0;
+}
+template <class R>
+__device__ __forceinline__ double dist_row_d(const R& x, const R& y) {
+  if (rowd_equal(x, y)) return 0.0;
+  const R m = mobius_add_d(rowd_neg(x), y);
+  return 2.0 * artanh_clamped_d(sqrt(rowd_dot(m, m)));
+}
+template <class R>
+__device__ __forceinline__ void dist_row_bwd_d(const R& x, const R& y, double g, R& dx, R& dy) {
+  const R nx = rowd_neg(x);
+  const R m = mobius_add_d(nx, y);
+  const double n = sqrt(rowd_dot(m, m));
+  const double c = (n > 0.0 && !rowd_equal(x, y)) ? 2.0 * g * artanh_prime_d(n) / n : 0.0;
+  R dm, dnx;
+#pragma unroll
+  HYPAD_ROW_EACH dm.v[e] = c * m.v[e];
+  mobius_add_bwd_d(nx, y, dm, dnx, dy);
+#pragma unroll
+  HYPAD_ROW_EACH dx.v[e] = -dnx.v[e];
+}
+// dist0 (:973-975): 2 artanh(|x|); the all-zero row gets gradient 0
+template <class R>
+__device__ __forceinline__ double dist0_row_d(const R& x) { return 2.0 * artanh_clamped_d(sqrt(rowd_dot(x, x))); }
+template <class R>
+__device__ __forceinline__ R dist0_row_bwd_d(const R& x, double g) {
+  const double n = sqrt(rowd_dot(x, x));
+  const double c = n > 0.0 ? 2.0 * g * artanh_prime_d(n) / n : 0.0;
+  R dx;
+#pragma unroll
+  HYPAD_ROW_EACH dx.v[e] = c * x.v[e];
+  return dx;
+}
+
 // The GRU gate sigmoid(logmap0(y)) (hyrnn_nets.py:81-82).  (Columns past the row's end come out as 0.5: every use multiplies them
 // with a zero of the other operand before a sum is taken.)
 template <class R>

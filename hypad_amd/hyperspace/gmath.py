@@ -9,6 +9,8 @@ mobius_pointwise_mul (:1328-1371) is the gate product of the Moebius GRU (hyrnn_
 weighted_midpoint (:1953-2087) and weighted_midpoint_bmm (:2090-2122) turn many ball points into one -- pooling over dimensions of one
 tensor, and weights (..., N, M) against xs (..., M, D) for attention and aggregation; mobius_scalar_mul (:788-858) is their lincomb step
 and an op of its own.  HIP kernels forward and backward (docs/history/weighted_midpoint.md).
+dist_matmul (:905-947) is the geodesic distance of every point of x from every point of y -- the score of hyperbolic attention --, dist
+(:861-902) and dist0 (:950-975) its row forms: HIP kernels forward and backward (docs/history/geodesic_distance.md).
 """
 import torch
 
@@ -369,6 +371,147 @@ def weighted_midpoint(xs, k, weights=None, reducedim=None, dim=-1, keepdim=False
     out = _WeightedMidpoint.apply(x3, w2, flags)
     shape = [1 if a in red else xs.shape[a] for a in range(nd)] if keepdim else [xs.shape[a] for a in kept]
     return out.view(*shape, xs.shape[-1])
+
+
+class _DistMatmul(torch.autograd.Function):
+    """hypad_dist_matmul_*: x (batch, N, D), y (batch, M, D) -> (batch, N, M); saves the operands alone."""
+
+    @staticmethod
+    def forward(ctx, x, y):
+        x = _C.require_cuda(x.contiguous(), "x")
+        y = _C.require_cuda(y.contiguous(), "y")
+        batch, n, d = x.shape
+        m = y.shape[1]
+        out = torch.empty(batch, n, m, device=x.device, dtype=torch.float32)
+        _C.check(_C.lib.hypad_dist_matmul_fwd(_C.ptr(x), _C.ptr(y), _C.ptr(out), batch, n, m, d, _C.stream()), "dist_matmul_fwd")
+        ctx.save_for_backward(x, y)
+        return out
+
+    @staticmethod
+    @_C.first_order_only
+    def backward(ctx, go):
+        x, y = ctx.saved_tensors
+        batch, n, d = x.shape
+        go = go.to(torch.float32).contiguous()
+        gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        gy = torch.empty_like(y) if ctx.needs_input_grad[1] else None
+        _C.check(_C.lib.hypad_dist_matmul_bwd(_C.ptr(x), _C.ptr(y), _C.ptr(go), _C.ptr(gx), _C.ptr(gy), batch, n, y.shape[1], d, _C.stream()),
+                 "dist_matmul_bwd")
+        return gx, gy
+
+
+_DISTMM_SUPPORTED = ("supported: k = -1, fp32, x (..., N, D) against y (..., D, M) with the same leading batch dimensions on both, or none on one "
+                     "of them, D <= 256, fewer than 2^31 distances")
+
+
+def dist_matmul(x, y, k):
+    """The geodesic distance of every point of x (..., N, D) from every point of y (..., D, M) -> (..., N, M) (math_.py:905-947) at
+    k = -1: the score of a hyperbolic attention layer, ``dist_matmul(q, keys.transpose(-1, -2), k)``.  One HIP launch forward on fp32
+    MFMA, one fused launch per gradient; first-order differentiable in x and y.  y is handed to the kernels as points (..., M, D): a y
+    that is the transposed view of such a tensor is passed as it is, any other is copied once.  Both operands carry the same leading
+    batch dimensions, or one of them carries none: that operand is expanded over the batch and materialised on the host, and the sum of
+    its gradient over the batch is left to autograd (the expand's backward)."""
+    if k is not None and abs(float(k) + 1.0) > 1e-12:
+        raise NotImplementedError(f"dist_matmul: curvature k = {float(k)} is not implemented; {_DISTMM_SUPPORTED}")
+    bx, by = tuple(x.shape[:-2]), tuple(y.shape[:-2])
+    if (x.dim() < 2 or y.dim() < 2 or y.shape[-2] != x.shape[-1] or (bx != by and bx != () and by != ())
+            or x.dtype != torch.float32 or y.dtype != torch.float32):
+        raise NotImplementedError(f"dist_matmul: x {tuple(x.shape)} {x.dtype} against y {tuple(y.shape)} {y.dtype} is not implemented; "
+                                  f"{_DISTMM_SUPPORTED}")
+    lead = bx or by
+    count = x.shape[-2] * y.shape[-1]
+    for n in lead:
+        count *= n
+    if x.shape[-1] > 256 or x.shape[-1] < 1 or count >= 2 ** 31:
+        raise NotImplementedError(f"dist_matmul: x {tuple(x.shape)} against y {tuple(y.shape)} is not implemented; {_DISTMM_SUPPORTED}")
+    yt = y.transpose(-1, -2)                                 # (..., M, D): contiguous already in the usual call
+    if bx != lead:
+        x = x.expand(*lead, *x.shape[-2:])
+    if by != lead:
+        yt = yt.expand(*lead, *yt.shape[-2:])
+    nb = 1
+    for n in lead:
+        nb *= n
+    out = _DistMatmul.apply(x.reshape(nb, *x.shape[-2:]), yt.reshape(nb, *yt.shape[-2:]))
+    return out.view(*lead, x.shape[-2], yt.shape[-2])
+
+
+class _Dist(torch.autograd.Function):
+    """hypad_dist_*: the rows of x and y (rows, D) -> (rows)."""
+
+    @staticmethod
+    def forward(ctx, x, y):
+        x = _C.require_cuda(x.contiguous(), "x")
+        y = _C.require_cuda(y.contiguous(), "y")
+        rows, d = x.shape
+        out = torch.empty(rows, device=x.device, dtype=torch.float32)
+        _C.check(_C.lib.hypad_dist_fwd(_C.ptr(x), _C.ptr(y), _C.ptr(out), rows, d, _C.stream()), "dist_fwd")
+        ctx.save_for_backward(x, y)
+        return out
+
+    @staticmethod
+    @_C.first_order_only
+    def backward(ctx, go):
+        x, y = ctx.saved_tensors
+        go = go.to(torch.float32).contiguous()
+        gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        gy = torch.empty_like(y) if ctx.needs_input_grad[1] else None
+        _C.check(_C.lib.hypad_dist_bwd(_C.ptr(x), _C.ptr(y), _C.ptr(go), _C.ptr(gx), _C.ptr(gy), x.shape[0], x.shape[1], _C.stream()), "dist_bwd")
+        return gx, gy
+
+
+class _Dist0(torch.autograd.Function):
+    """hypad_dist0_*: the rows of x (rows, D) -> (rows)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        x = _C.require_cuda(x.contiguous(), "x")
+        rows, d = x.shape
+        out = torch.empty(rows, device=x.device, dtype=torch.float32)
+        _C.check(_C.lib.hypad_dist0_fwd(_C.ptr(x), _C.ptr(out), rows, d, _C.stream()), "dist0_fwd")
+        ctx.save_for_backward(x)
+        return out
+
+    @staticmethod
+    @_C.first_order_only
+    def backward(ctx, go):
+        (x,) = ctx.saved_tensors
+        go = go.to(torch.float32).contiguous()
+        gx = torch.empty_like(x)
+        _C.check(_C.lib.hypad_dist0_bwd(_C.ptr(x), _C.ptr(go), _C.ptr(gx), x.shape[0], x.shape[1], _C.stream()), "dist0_bwd")
+        return gx
+
+
+_DIST_SUPPORTED = "supported: k = -1, dim = -1, fp32, x and y of the same shape (nothing is broadcast), rows of 1 to 256 elements"
+
+
+def _dist_refusals(what, x, k, dim):
+    if k is not None and abs(float(k) + 1.0) > 1e-12:
+        raise NotImplementedError(f"{what}: curvature k = {float(k)} is not implemented; {_DIST_SUPPORTED}")
+    if x.dim() < 1 or (dim != -1 and dim != x.dim() - 1):
+        raise NotImplementedError(f"{what}: dim = {dim} on x {tuple(x.shape)} is not implemented; {_DIST_SUPPORTED}")
+    if x.dtype != torch.float32 or x.shape[-1] > 256 or x.shape[-1] < 1:
+        raise NotImplementedError(f"{what}: x {tuple(x.shape)} {x.dtype} is not implemented; {_DIST_SUPPORTED}")
+
+
+def dist(x, y, *, k, keepdim=False, dim=-1):
+    """The geodesic distance 2 artanh(|(-x) (+) y|) of the rows of x from the rows of y (math_.py:861-902) at k = -1: one HIP launch
+    forward and one backward, a wave per row; first-order differentiable in x and y.  Rows that are equal element by element are at
+    distance 0 with gradient 0."""
+    _dist_refusals("dist", x, k, dim)
+    if y.shape != x.shape or y.dtype != torch.float32:
+        raise NotImplementedError(f"dist: y {tuple(y.shape)} {y.dtype} against x {tuple(x.shape)} is not implemented; {_DIST_SUPPORTED}")
+    rows = _rows_width(x)[0]
+    out = _Dist.apply(x.reshape(rows, x.shape[-1]), y.reshape(rows, y.shape[-1]))
+    return out.view(*x.shape[:-1], 1) if keepdim else out.view(x.shape[:-1])
+
+
+def dist0(x, *, k, keepdim=False, dim=-1):
+    """The geodesic distance 2 artanh(|x|) of the rows of x from the origin (math_.py:950-975) at k = -1: one HIP launch forward and
+    one backward; an all-zero row gets gradient 0."""
+    _dist_refusals("dist0", x, k, dim)
+    out = _Dist0.apply(x.reshape(_rows_width(x)[0], x.shape[-1]))
+    return out.view(*x.shape[:-1], 1) if keepdim else out.view(x.shape[:-1])
 
 
 def mobius_fn_apply(fn, x, *args, k=None, dim=-1, **kwargs):

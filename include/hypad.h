@@ -197,7 +197,30 @@ int hypad_weighted_midpoint_fwd(const float* xs, const float* weights /* NULL: n
 int hypad_weighted_midpoint_bwd(const float* xs, const float* weights, int64_t w_count, const double* saved, const float* grad_out,
                                 float* grad_xs, float* grad_weights, void* workspace, size_t workspace_bytes,
                                 int64_t M, int64_t R, int D, int flags, hypad_stream_t stream);
-/* The Moebius GRU  hyperspace/hyrnn_nets.py:61-151 (one_rnn_transform :61-65, mobius_gru_cell :68-91, the equal-length branch of
+/* gmath.dist_matmul  math_.py:905-947 (_dist_matmul :937-947; artan_k with the clamp of :57-59) at k = -1: the geodesic distance of
+ * every x_i from every y_j, the score of a hyperbolic attention layer.  x (batch, N, D), y (batch, M, D) -- row-major points: the
+ * caller transposes the reference's (batch, D, M) --, out and grad_out (batch, N, M):
+ *   num = |x|^2 - 2 <x, y> + |y|^2    den = max(1 - 2 <x, y> + |x|^2 |y|^2, 1e-15)    out = 2 artanh(min(sqrt(max(num / den, 1e-15)), 1 - 1e-7))
+ * One launch: <x, y> on fp32 MFMA from tiles staged in LDS, the norms as fp64 sums of the staged values, the epilogue in fp64
+ * registers.  bwd: one fused launch per gradient (the pair terms are recomputed tile by tile: no N x M intermediate, no workspace);
+ * grad_x or grad_y may be NULL and the other keeps its bits.  Nothing flows through a clamp that holds.  No atomics: two runs give the
+ * same bits.  batch, N or M == 0 launches nothing and writes zeros to the gradients.
+ * Every argument is validated before anything is launched: HYPAD_EINVAL for a NULL operand (x, y, out / grad_out) that has elements,
+ * a negative batch, N or M, or D <= 0; HYPAD_EUNSUPPORTED for D > 256, an element count of 2^31 or more, or LDS that does not fit. */
+int hypad_dist_matmul_fwd(const float* x, const float* y, float* out, int64_t batch, int64_t N, int64_t M, int D, hypad_stream_t stream);
+int hypad_dist_matmul_bwd(const float* x, const float* y, const float* grad_out, float* grad_x, float* grad_y,
+                          int64_t batch, int64_t N, int64_t M, int D, hypad_stream_t stream);
+/* gmath.dist  math_.py:861-902 (_dist :893-902, _mobius_add :536-555) at k = -1: 2 artanh(|(-x) (+) y|) of the rows of x and y
+ * (rows, dim), out and grad_out (rows); the norm has no clamp, artanh clamps at 1 - 1e-7.  A wave per row in fp64 registers.  Two
+ * rows that are equal element by element give distance 0 and gradient 0.  bwd: grad_x or grad_y may be NULL.
+ * gmath.dist0  math_.py:950-975 (_dist0 :973-975): 2 artanh(|x|), the distance from the origin; an all-zero row gets gradient 0.
+ * HYPAD_EINVAL for a NULL operand with rows > 0, rows < 0 or dim <= 0; HYPAD_EUNSUPPORTED for dim > 256; rows == 0 launches nothing. */
+int hypad_dist_fwd(const float* x, const float* y, float* out, int64_t rows, int dim, hypad_stream_t stream);
+int hypad_dist_bwd(const float* x, const float* y, const float* grad_out, float* grad_x, float* grad_y, int64_t rows, int dim,
+                   hypad_stream_t stream);
+int hypad_dist0_fwd(const float* x, float* out, int64_t rows, int dim, hypad_stream_t stream);
+int hypad_dist0_bwd(const float* x, const float* grad_out, float* grad_x, int64_t rows, int dim, hypad_stream_t stream);
+/* The Moebius GRU hyperspace/hyrnn_nets.py:61-151 (one_rnn_transform :61-65, mobius_gru_cell :68-91, the equal-length branch of
  * mobius_gru_loop :113-127) at k = -1.  x (steps, rows, in_dim) and h0 (rows, hidden) on the ball, w_ih (3 hidden, in_dim),
  * w_hh (3 hidden, hidden), bias (3, hidden) on the ball, chunk order r, h, z; out (steps, rows, hidden) = the hidden state after
  * every step (the last one is h_last); no project anywhere, as in the reference.  steps = 1 is the cell.  nonlin: HYPAD_NONLIN_*
