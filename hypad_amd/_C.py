@@ -148,6 +148,9 @@ _SIGS = {
     "hypad_dist_bwd": (c_int, [P, P, P, P, P, c_int64, c_int, P]),
     "hypad_dist0_fwd": (c_int, [P, P, c_int64, c_int, P]),
     "hypad_dist0_bwd": (c_int, [P, P, P, c_int64, c_int, P]),
+    "hypad_hyp_attention_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int, c_int]),
+    "hypad_hyp_attention_fwd": (c_int, [P, P, P, P, c_int64, c_double, P, P, P, c_int64, c_int64, c_int64, c_int, c_int, P]),
+    "hypad_hyp_attention_bwd": (c_int, [P, P, P, P, c_int64, c_double, P, P, P, P, P, P, c_void_p, c_size_t, c_int64, c_int64, c_int64, c_int, c_int, P]),
     "hypad_mobius_gru_workspace_bytes": (c_size_t, [c_int, c_int64, c_int, c_int]),
     "hypad_mobius_gru_fwd": (c_int, [P] * 7 + [c_void_p, c_size_t, c_int, c_int64, c_int, c_int, c_int, P]),
     "hypad_mobius_gru_bwd": (c_int, [P] * 14 + [c_void_p, c_size_t, c_int, c_int64, c_int, c_int, c_int, P]),

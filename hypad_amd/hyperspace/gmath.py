@@ -11,6 +11,8 @@ tensor, and weights (..., N, M) against xs (..., M, D) for attention and aggrega
 and an op of its own.  HIP kernels forward and backward (docs/history/weighted_midpoint.md).
 dist_matmul (:905-947) is the geodesic distance of every point of x from every point of y -- the score of hyperbolic attention --, dist
 (:861-902) and dist0 (:950-975) its row forms: HIP kernels forward and backward (docs/history/geodesic_distance.md).
+hyperbolic_attention is dist_matmul, a softmax and weighted_midpoint_bmm as one function whose kernels keep no (N, M) tensor
+(docs/history/hyperbolic_attention.md).
 """
 import torch
 
@@ -512,6 +514,107 @@ def dist0(x, *, k, keepdim=False, dim=-1):
     _dist_refusals("dist0", x, k, dim)
     out = _Dist0.apply(x.reshape(_rows_width(x)[0], x.shape[-1]))
     return out.view(*x.shape[:-1], 1) if keepdim else out.view(x.shape[:-1])
+
+
+class _HyperbolicAttention(torch.autograd.Function):
+    """hypad_hyp_attention_*: q (batch, N, D), keys (batch, M, D), values (batch, M, E), bias None, (N, M) or (batch, N, M) ->
+    (batch, N, E); saves the operands, [nom | den] (batch, N, E + 1) and L (batch, N) -- nothing of size N x M."""
+
+    @staticmethod
+    def forward(ctx, q, keys, values, bias, beta):
+        q = _C.require_cuda(q.contiguous(), "q")
+        keys = _C.require_cuda(keys.contiguous(), "keys")
+        values = _C.require_cuda(values.contiguous(), "values")
+        if bias is not None:
+            bias = _C.require_cuda(bias.contiguous(), "bias")
+        batch, n, d = q.shape
+        m, e = values.shape[1], values.shape[2]
+        stride = n * m if bias is not None and bias.dim() == 3 else 0
+        out = torch.empty(batch, n, e, device=q.device, dtype=torch.float32)
+        train = any(ctx.needs_input_grad[:3])
+        saved = torch.empty(batch, n, e + 1, device=q.device, dtype=torch.float32) if train else None
+        lse = torch.empty(batch, n, device=q.device, dtype=torch.float32) if train else None
+        _C.check(_C.lib.hypad_hyp_attention_fwd(_C.ptr(q), _C.ptr(keys), _C.ptr(values), _C.ptr(bias), stride, beta, _C.ptr(out), _C.ptr(saved),
+                                                _C.ptr(lse), batch, n, m, d, e, _C.stream()), "hyp_attention_fwd")
+        if train:
+            ctx.save_for_backward(q, keys, values, saved, lse, *(() if bias is None else (bias,)))
+        ctx.beta, ctx.stride = beta, stride
+        return out
+
+    @staticmethod
+    @_C.first_order_only
+    def backward(ctx, go):
+        q, keys, values, saved, lse, *rest = ctx.saved_tensors
+        bias = rest[0] if rest else None
+        batch, n, d = q.shape
+        m, e = values.shape[1], values.shape[2]
+        go = go.to(torch.float32).contiguous()
+        gq = torch.empty_like(q) if ctx.needs_input_grad[0] else None
+        gk = torch.empty_like(keys) if ctx.needs_input_grad[1] else None
+        gv = torch.empty_like(values) if ctx.needs_input_grad[2] else None
+        nbytes = _C.lib.hypad_hyp_attention_workspace_bytes(batch, n, m, d, e)
+        ws = torch.empty(max(nbytes // 4, 1), device=q.device, dtype=torch.float32)
+        _C.check(_C.lib.hypad_hyp_attention_bwd(_C.ptr(q), _C.ptr(keys), _C.ptr(values), _C.ptr(bias), ctx.stride, ctx.beta, _C.ptr(saved),
+                                                _C.ptr(lse), _C.ptr(go), _C.ptr(gq), _C.ptr(gk), _C.ptr(gv), _C.ptr(ws), nbytes, batch, n, m, d, e,
+                                                _C.stream()), "hyp_attention_bwd")
+        return gq, gk, gv, None, None
+
+
+_ATTN_SUPPORTED = ("supported: k = -1, fp32, q (..., N, D), keys (..., M, D) and values (..., M, E) with the same leading batch dimensions, or "
+                   "none on some of them, 1 <= D, E <= 128, M >= 1, fewer than 2^31 pairs, a finite beta (a float or a one-element tensor) and "
+                   "a bias that is None or fp32 (N, M) or (..., N, M), neither of the two requiring grad; for wider rows compose dist_matmul, "
+                   "torch.softmax and weighted_midpoint_bmm (D, E <= 256)")
+
+
+def hyperbolic_attention(q, keys, values, k, beta=1.0, bias=None):
+    """Hyperbolic attention at k = -1: for every query of q (..., N, D) the gyromidpoint of the points values (..., M, E) under the
+    weights softmax_j(-beta d(q_i, keys_j) + bias_ij), keys (..., M, D) -> (..., N, E).  The contract is the composition of the
+    reference's ``dist_matmul(q, keys.transpose(-1, -2), k)`` (math_.py:905-947), ``torch.softmax(-beta * . + bias, -1)`` and
+    ``weighted_midpoint_bmm(values, ., k, lincomb=False)`` (math_.py:2090-2122), in one HIP launch forward and three backward that keep
+    no (N, M) tensor: the distances and weights are recomputed tile by tile (docs/history/hyperbolic_attention.md).  First-order
+    differentiable in q, keys and values; a gradient that is not needed is not computed.
+
+    The three operands carry the same leading batch dimensions, or some carry none: those are expanded over the batch and materialised
+    on the host, and the sum of their gradient over the batch is left to autograd.  ``bias`` is fp32 (N, M) -- shared by the batch and
+    not expanded -- or (..., N, M); it may hold -inf, the mask, and gets no gradient.  ``beta`` is a finite float or a one-element
+    tensor that does not require grad; it is read on the host and handed to the kernels by value, so a captured graph replays the
+    value it was captured with, whatever the tensor holds later.
+
+    One difference from the composition: a query whose every score is -inf (a fully masked row) gives the origin, an all-zero row, and
+    adds nothing to any gradient; the composition returns NaN there."""
+    if k is not None and abs(float(k) + 1.0) > 1e-12:
+        raise NotImplementedError(f"hyperbolic_attention: curvature k = {float(k)} is not implemented; {_ATTN_SUPPORTED}")
+    if isinstance(beta, torch.Tensor):
+        if beta.numel() != 1 or beta.requires_grad:
+            raise NotImplementedError(f"hyperbolic_attention: beta {tuple(beta.shape)} requires_grad={beta.requires_grad} is not implemented; "
+                                      f"{_ATTN_SUPPORTED}")
+        beta = beta.item()
+    beta = float(beta)
+    if beta != beta or beta in (float("inf"), float("-inf")):
+        raise NotImplementedError(f"hyperbolic_attention: beta = {beta} is not implemented; {_ATTN_SUPPORTED}")
+    ops = (q, keys, values)
+    desc = ", ".join(f"{n} {tuple(t.shape)} {t.dtype}" for n, t in zip(("q", "keys", "values"), ops))
+    if any(t.dim() < 2 or t.dtype != torch.float32 for t in ops):
+        raise NotImplementedError(f"hyperbolic_attention: {desc} is not implemented; {_ATTN_SUPPORTED}")
+    leads = {tuple(t.shape[:-2]) for t in ops} - {()}
+    n, d, m, e = q.shape[-2], q.shape[-1], keys.shape[-2], values.shape[-1]
+    if len(leads) > 1 or keys.shape[-1] != d or values.shape[-2] != m or not 1 <= d <= 128 or not 1 <= e <= 128 or m < 1:
+        raise NotImplementedError(f"hyperbolic_attention: {desc} is not implemented; {_ATTN_SUPPORTED}")
+    lead = leads.pop() if leads else ()
+    nb = 1
+    for s in lead:
+        nb *= s
+    if nb * n * m >= 2 ** 31:
+        raise NotImplementedError(f"hyperbolic_attention: {desc} ({nb * n * m} pairs) is not implemented; {_ATTN_SUPPORTED}")
+    if bias is not None:
+        if (bias.dtype != torch.float32 or bias.requires_grad or tuple(bias.shape[-2:]) != (n, m) or bias.dim() < 2
+                or tuple(bias.shape[:-2]) not in ((), lead)):
+            raise NotImplementedError(f"hyperbolic_attention: bias {tuple(bias.shape)} {bias.dtype} requires_grad={bias.requires_grad} against "
+                                      f"{desc} is not implemented; {_ATTN_SUPPORTED}")
+        bias = bias if bias.dim() == 2 else bias.reshape(nb, n, m)
+    q3, k3, v3 = (t.expand(*lead, *t.shape[-2:]).reshape(nb, *t.shape[-2:]) for t in ops)
+    out = _HyperbolicAttention.apply(q3, k3, v3, bias, beta)
+    return out.view(*lead, n, e)
 
 
 def mobius_fn_apply(fn, x, *args, k=None, dim=-1, **kwargs):

@@ -220,6 +220,29 @@ int hypad_dist_bwd(const float* x, const float* y, const float* grad_out, float*
                    hypad_stream_t stream);
 int hypad_dist0_fwd(const float* x, float* out, int64_t rows, int dim, hypad_stream_t stream);
 int hypad_dist0_bwd(const float* x, const float* grad_out, float* grad_x, int64_t rows, int dim, hypad_stream_t stream);
+/* gmath.hyperbolic_attention: the composition of dist_matmul (math_.py:905-947), a softmax over the keys and weighted_midpoint_bmm
+ * without lincomb (math_.py:2090-2122) at k = -1, with no N x M tensor in memory.  q (batch, N, D), keys (batch, M, D), values
+ * (batch, M, E) on the ball, out and grad_out (batch, N, E); bias NULL or fp32 (N, M) per batch element at bias_batch_stride elements
+ * (N M, or 0: one bias shared by every batch element), -inf masks a pair; beta by value:
+ *   s_ij = -beta d(q_i, keys_j) + bias_ij    p_ij = softmax_j s_ij    out_i = the gyromidpoint of the values under p_i.
+ * A row whose every s_ij is -inf gives out_i = 0 and adds nothing to any gradient (the composition gives NaN).
+ * fwd: one launch, a workgroup per 16 query rows walks keys and values in chunks of 64 (16 a wave) with a running maximum; products on
+ * fp32 MFMA, distances, exponentials and the epilogue in fp64 registers.  saved (batch, N, E + 1) = [nom | den] and lse (batch, N) = L are written
+ * for the backward; both NULL: inference, the same bits in out.
+ * bwd: a row pass into the workspace (hypad_hyp_attention_workspace_bytes = 4 batch N (E + 2) bytes), one launch for grad_q, one for
+ * grad_keys and grad_values; p is recomputed from L.  Each gradient may be NULL and the others keep their bits.  No atomics: two runs give
+ * the same bits.  batch == 0 or N == 0 launches nothing; the backward then writes zeros to grad_keys and grad_values.
+ * Every argument is validated before anything is launched: HYPAD_EINVAL for a NULL operand that has elements, a negative size, D or
+ * E <= 0, M == 0 with N > 0, a bias stride that is neither, saved without lse, or a beta that is not finite; HYPAD_EUNSUPPORTED for D or
+ * E > 128, 2^31 or more pairs, or LDS that does not fit; HYPAD_EWORKSPACE below the workspace size. */
+size_t hypad_hyp_attention_workspace_bytes(int64_t batch, int64_t N, int64_t M, int D, int E);
+int hypad_hyp_attention_fwd(const float* q, const float* keys, const float* values, const float* bias /* NULL: none */,
+                            int64_t bias_batch_stride, double beta, float* out, float* saved /* NULL: inference */, float* lse,
+                            int64_t batch, int64_t N, int64_t M, int D, int E, hypad_stream_t stream);
+int hypad_hyp_attention_bwd(const float* q, const float* keys, const float* values, const float* bias, int64_t bias_batch_stride,
+                            double beta, const float* saved, const float* lse, const float* grad_out, float* grad_q, float* grad_keys,
+                            float* grad_values, void* workspace, size_t workspace_bytes, int64_t batch, int64_t N, int64_t M, int D, int E,
+                            hypad_stream_t stream);
 /* The Moebius GRU hyperspace/hyrnn_nets.py:61-151 (one_rnn_transform :61-65, mobius_gru_cell :68-91, the equal-length branch of
  * mobius_gru_loop :113-127) at k = -1.  x (steps, rows, in_dim) and h0 (rows, hidden) on the ball, w_ih (3 hidden, in_dim),
  * w_hh (3 hidden, hidden), bias (3, hidden) on the ball, chunk order r, h, z; out (steps, rows, hidden) = the hidden state after
