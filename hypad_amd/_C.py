@@ -148,6 +148,20 @@ _SIGS = {
     "hypad_dist_bwd": (c_int, [P, P, P, P, P, c_int64, c_int, P]),
     "hypad_dist0_fwd": (c_int, [P, P, c_int64, c_int, P]),
     "hypad_dist0_bwd": (c_int, [P, P, P, c_int64, c_int, P]),
+    "hypad_expmap_fwd": (c_int, [P, P, P, c_int64, c_int, P]),
+    "hypad_expmap_bwd": (c_int, [P, P, P, P, P, c_int64, c_int, P]),
+    "hypad_logmap_fwd": (c_int, [P, P, P, c_int64, c_int, P]),
+    "hypad_logmap_bwd": (c_int, [P, P, P, P, P, c_int64, c_int, P]),
+    "hypad_geodesic_fwd": (c_int, [P, P, P, P, c_int64, c_int, c_int64, P]),
+    "hypad_geodesic_bwd": (c_int, [P, P, P, P, P, P, P, c_int64, c_int, c_int64, P]),
+    "hypad_gyration_fwd": (c_int, [P, P, P, P, c_int64, c_int, P]),
+    "hypad_gyration_bwd": (c_int, [P, P, P, P, P, P, P, c_int64, c_int, P]),
+    "hypad_parallel_transport_fwd": (c_int, [P, P, P, P, c_int64, c_int, P]),
+    "hypad_parallel_transport_bwd": (c_int, [P, P, P, P, P, P, P, c_int64, c_int, P]),
+    "hypad_parallel_transport0_fwd": (c_int, [P, P, P, c_int64, c_int, P]),
+    "hypad_parallel_transport0_bwd": (c_int, [P, P, P, P, P, c_int64, c_int, P]),
+    "hypad_parallel_transport0back_fwd": (c_int, [P, P, P, c_int64, c_int, P]),
+    "hypad_parallel_transport0back_bwd": (c_int, [P, P, P, P, P, c_int64, c_int, P]),
     "hypad_hyp_attention_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int, c_int]),
     "hypad_hyp_attention_fwd": (c_int, [P, P, P, P, c_int64, c_double, P, P, P, c_int64, c_int64, c_int64, c_int, c_int, P]),
     "hypad_hyp_attention_bwd": (c_int, [P, P, P, P, c_int64, c_double, P, P, P, P, P, P, c_void_p, c_size_t, c_int64, c_int64, c_int64, c_int, c_int, P]),

@@ -511,6 +511,148 @@ __device__ __forceinline__ R dist0_row_bwd_d(const R& x, double g) {
   return dx;
 }
 
+// The tangent maps at a point of the ball (math_.py:1097-1102 expmap, :1226-1230 logmap, :1042-1049 geodesic, :657-675 gyration,
+// :1739-1746 parallel_transport, :1776-1779 and :1810-1813 the two transports of the origin).  c(x) = max(1 - |x|^2, 1e-15) = 2 / lambda_x;
+// nothing flows back through it where the clamp holds.  artanh is the log1p form above, so at coincident points logmap and geodesic
+// follow artanh(n) / n -> 1 (the reference's fp32 difference of two logarithms returns 0 there).
+__device__ __forceinline__ double conformal_d(double x2) { return fmax(1.0 - x2, DIST_EPS); }
+__device__ __forceinline__ double conformal_prime_d(double x2) { return 1.0 - x2 >= DIST_EPS ? -1.0 : 0.0; }
+// expmap: x (+) (tanh(min(n / c(x), 15)) u / n), n = max(|u|, 1e-15)
+template <class R>
+__device__ __forceinline__ R expmap_d(const R& x, const R& u) {
+  const double n = fmax(sqrt(rowd_dot(u, u)), (double)MIN_NORM);
+  const double f = tanh_clamped_d(n / conformal_d(rowd_dot(x, x))) / n;
+  R s;
+#pragma unroll
+  HYPAD_ROW_EACH s.v[e] = f * u.v[e];
+  return mobius_add_d(x, s);
+}
+template <class R>
+__device__ __forceinline__ void expmap_bwd_d(const R& x, const R& u, const R& go, R& dx, R& du) {
+  const double raw = sqrt(rowd_dot(u, u)), x2 = rowd_dot(x, x);
+  const double n = fmax(raw, (double)MIN_NORM), c = conformal_d(x2), arg = n / c;
+  const double t = tanh_clamped_d(arg), tp = tanh_prime_d(arg, t), f = t / n;
+  R s, ds;
+#pragma unroll
+  HYPAD_ROW_EACH s.v[e] = f * u.v[e];
+  mobius_add_bwd_d(x, s, go, dx, ds);
+  const double gf = rowd_dot(ds, u);                             // d L / d f;  f = tanh(n / c) / n
+  const double cu = raw >= (double)MIN_NORM ? gf * (tp * arg - t) / (n * n * n) : 0.0;
+  const double cx = -2.0 * gf * tp / (c * c) * conformal_prime_d(x2);      // 2 dL/d|x|^2
+#pragma unroll
+  HYPAD_ROW_EACH { du.v[e] = f * ds.v[e] + cu * u.v[e]; dx.v[e] += cx * x.v[e]; }
+}
+// logmap: artanh(min(n, 1 - 1e-7)) c(x) w / n, w = (-x) (+) y, n = max(|w|, 1e-15)
+template <class R>
+__device__ __forceinline__ R logmap_d(const R& x, const R& y) {
+  const R w = mobius_add_d(rowd_neg(x), y);
+  const double n = fmax(sqrt(rowd_dot(w, w)), (double)MIN_NORM);
+  const double f = artanh_clamped_d(n) * conformal_d(rowd_dot(x, x)) / n;
+  R o;
+#pragma unroll
+  HYPAD_ROW_EACH o.v[e] = f * w.v[e];
+  return o;
+}
+template <class R>
+__device__ __forceinline__ void logmap_bwd_d(const R& x, const R& y, const R& go, R& dx, R& dy) {
+  const R nx = rowd_neg(x);
+  const R w = mobius_add_d(nx, y);
+  const double raw = sqrt(rowd_dot(w, w)), x2 = rowd_dot(x, x);
+  const double n = fmax(raw, (double)MIN_NORM), c = conformal_d(x2), a = artanh_clamped_d(n);
+  const double f = a * c / n, gf = rowd_dot(go, w);              // d L / d f
+  const double cw = raw >= (double)MIN_NORM ? gf * c * (artanh_prime_d(n) * n - a) / (n * n * n) : 0.0;
+  const double cx = 2.0 * gf * a / n * conformal_prime_d(x2);
+  R dw, dnx;
+#pragma unroll
+  HYPAD_ROW_EACH dw.v[e] = f * go.v[e] + cw * w.v[e];
+  mobius_add_bwd_d(nx, y, dw, dnx, dy);
+#pragma unroll
+  HYPAD_ROW_EACH dx.v[e] = cx * x.v[e] - dnx.v[e];
+}
+// geodesic: x (+) (t (x) ((-x) (+) y)); the backward returns dL/dt
+template <class R>
+__device__ __forceinline__ R geodesic_d(double t, const R& x, const R& y) {
+  return mobius_add_d(x, mobius_scalar_mul_d(t, mobius_add_d(rowd_neg(x), y)));
+}
+template <class R>
+__device__ __forceinline__ double geodesic_bwd_d(double t, const R& x, const R& y, const R& go, R& dx, R& dy) {
+  const R nx = rowd_neg(x);
+  const R v = mobius_add_d(nx, y);
+  R dtv, dv, dnx;
+  mobius_add_bwd_d(x, mobius_scalar_mul_d(t, v), go, dx, dtv);
+  const double gt = mobius_scalar_mul_bwd_d(t, v, dtv, dv);
+  mobius_add_bwd_d(nx, y, dv, dnx, dy);
+#pragma unroll
+  HYPAD_ROW_EACH dx.v[e] -= dnx.v[e];
+  return gt;
+}
+// gyration gyr[a, b] u = u + 2 (A a + B b) / d:  A = -<a,u> |b|^2 + <b,u> + 2 <a,b> <b,u>,  B = -<b,u> |a|^2 - <a,u>,
+// d = max(1 + 2 <a,b> + |a|^2 |b|^2, 1e-15)
+template <class R>
+__device__ __forceinline__ R gyration_d(const R& a, const R& b, const R& u) {
+  const double a2 = rowd_dot(a, a), b2 = rowd_dot(b, b), ab = rowd_dot(a, b), au = rowd_dot(a, u), bu = rowd_dot(b, u);
+  const double q = 2.0 / fmax(1.0 + 2.0 * ab + a2 * b2, DIST_EPS);
+  const double A = q * (-au * b2 + bu + 2.0 * ab * bu), B = q * (-bu * a2 - au);
+  R o;
+#pragma unroll
+  HYPAD_ROW_EACH o.v[e] = u.v[e] + A * a.v[e] + B * b.v[e];
+  return o;
+}
+template <class R>
+__device__ __forceinline__ void gyration_bwd_d(const R& a, const R& b, const R& u, const R& go, R& da, R& db, R& du) {
+  const double a2 = rowd_dot(a, a), b2 = rowd_dot(b, b), ab = rowd_dot(a, b), au = rowd_dot(a, u), bu = rowd_dot(b, u);
+  const double draw = 1.0 + 2.0 * ab + a2 * b2, q = 2.0 / fmax(draw, DIST_EPS);
+  const double A = -au * b2 + bu + 2.0 * ab * bu, B = -bu * a2 - au;
+  const double gA = q * rowd_dot(go, a), gB = q * rowd_dot(go, b);           // d L / d A, d L / d B
+  const double gd = draw >= DIST_EPS ? -0.5 * q * (A * gA + B * gB) : 0.0;
+  const double gau = -b2 * gA - gB, gbu = (1.0 + 2.0 * ab) * gA - a2 * gB, gab = 2.0 * (bu * gA + gd);
+  const double ga2 = -bu * gB + b2 * gd, gb2 = -au * gA + a2 * gd;
+#pragma unroll
+  HYPAD_ROW_EACH {
+    da.v[e] = q * A * go.v[e] + gau * u.v[e] + gab * b.v[e] + 2.0 * ga2 * a.v[e];
+    db.v[e] = q * B * go.v[e] + gbu * u.v[e] + gab * a.v[e] + 2.0 * gb2 * b.v[e];
+    du.v[e] = go.v[e] + gau * a.v[e] + gbu * b.v[e];
+  }
+}
+// parallel_transport: gyr[y, -x] v c(y) / c(x)
+template <class R>
+__device__ __forceinline__ R parallel_transport_d(const R& x, const R& y, const R& v) {
+  const double s = conformal_d(rowd_dot(y, y)) / conformal_d(rowd_dot(x, x));
+  R o = gyration_d(y, rowd_neg(x), v);
+#pragma unroll
+  HYPAD_ROW_EACH o.v[e] *= s;
+  return o;
+}
+template <class R>
+__device__ __forceinline__ void parallel_transport_bwd_d(const R& x, const R& y, const R& v, const R& go, R& dx, R& dy, R& dv) {
+  const R nx = rowd_neg(x);
+  const double x2 = rowd_dot(x, x), y2 = rowd_dot(y, y), cx = conformal_d(x2), cy = conformal_d(y2), s = cy / cx;
+  const double gs = rowd_dot(go, gyration_d(y, nx, v));          // d L / d s
+  R gg, dnx;
+#pragma unroll
+  HYPAD_ROW_EACH gg.v[e] = s * go.v[e];
+  gyration_bwd_d(y, nx, v, gg, dy, dnx, dv);
+  const double ky = 2.0 * gs / cx * conformal_prime_d(y2), kx = -2.0 * gs * s / cx * conformal_prime_d(x2);
+#pragma unroll
+  HYPAD_ROW_EACH { dy.v[e] += ky * y.v[e]; dx.v[e] = kx * x.v[e] - dnx.v[e]; }
+}
+// parallel_transport0: v c(y);  parallel_transport0back (BACK): v / c(x)
+template <bool BACK, class R>
+__device__ __forceinline__ R transport0_d(const R& p, const R& v) {
+  const double c = conformal_d(rowd_dot(p, p)), s = BACK ? 1.0 / c : c;
+  R o;
+#pragma unroll
+  HYPAD_ROW_EACH o.v[e] = s * v.v[e];
+  return o;
+}
+template <bool BACK, class R>
+__device__ __forceinline__ void transport0_bwd_d(const R& p, const R& v, const R& go, R& dp, R& dv) {
+  const double p2 = rowd_dot(p, p), c = conformal_d(p2), s = BACK ? 1.0 / c : c;
+  const double k = 2.0 * rowd_dot(go, v) * (BACK ? -s * s : 1.0) * conformal_prime_d(p2);
+#pragma unroll
+  HYPAD_ROW_EACH { dp.v[e] = k * p.v[e]; dv.v[e] = s * go.v[e]; }
+}
+
 // The GRU gate sigmoid(logmap0(y)) (hyrnn_nets.py:81-82).  (Columns past the row's end come out as 0.5: every use multiplies them
 // with a zero of the other operand before a sum is taken.)
 template <class R>

@@ -13,6 +13,9 @@ dist_matmul (:905-947) is the geodesic distance of every point of x from every p
 (:861-902) and dist0 (:950-975) its row forms: HIP kernels forward and backward (docs/history/geodesic_distance.md).
 hyperbolic_attention is dist_matmul, a softmax and weighted_midpoint_bmm as one function whose kernels keep no (N, M) tensor
 (docs/history/hyperbolic_attention.md).
+expmap (:1052-1102), logmap (:1188-1230), geodesic (:978-1049), gyration (:592-675), parallel_transport (:1669-1746),
+parallel_transport0 (:1749-1779) and parallel_transport0back (:1782-1813) are the tangent maps at an arbitrary point of the ball: one
+HIP launch forward and one backward each, operands broadcast against each other (docs/history/tangent_maps.md).
 """
 import torch
 
@@ -615,6 +618,151 @@ def hyperbolic_attention(q, keys, values, k, beta=1.0, bias=None):
     q3, k3, v3 = (t.expand(*lead, *t.shape[-2:]).reshape(nb, *t.shape[-2:]) for t in ops)
     out = _HyperbolicAttention.apply(q3, k3, v3, bias, beta)
     return out.view(*lead, n, e)
+
+
+class _RowMap(torch.autograd.Function):
+    """hypad_<name>_fwd / _bwd for the tangent maps of two or three operands, all of one shape (..., D); saves the operands alone."""
+
+    @staticmethod
+    def forward(ctx, name, *ops):
+        ops = [_C.require_cuda(t.contiguous(), f"{name}: operand {i}") for i, t in enumerate(ops)]
+        shape = ops[0].shape
+        rows, d = _rows_width(ops[0])
+        out = torch.empty(shape, device=ops[0].device, dtype=torch.float32)
+        _C.check(getattr(_C.lib, f"hypad_{name}_fwd")(*map(_C.ptr, ops), _C.ptr(out), rows, d, _C.stream()), f"{name}_fwd")
+        ctx.save_for_backward(*ops)
+        ctx.name = name
+        return out
+
+    @staticmethod
+    @_C.first_order_only
+    def backward(ctx, go):
+        ops = ctx.saved_tensors
+        rows, d = _rows_width(ops[0])
+        go = go.to(torch.float32).contiguous()
+        grads = [torch.empty_like(t) if need else None for t, need in zip(ops, ctx.needs_input_grad[1:])]
+        _C.check(getattr(_C.lib, f"hypad_{ctx.name}_bwd")(*map(_C.ptr, ops), _C.ptr(go), *map(_C.ptr, grads), rows, d, _C.stream()),
+                 f"{ctx.name}_bwd")
+        return (None, *grads)
+
+
+class _Geodesic(torch.autograd.Function):
+    """hypad_geodesic_*: t of one element, or of one element per row of x and y (..., D)."""
+
+    @staticmethod
+    def forward(ctx, t, x, y):
+        x = _C.require_cuda(x.contiguous(), "x")
+        y = _C.require_cuda(y.contiguous(), "y")
+        t1 = _C.require_cuda(t.contiguous().reshape(-1), "t")
+        rows, d = _rows_width(x)
+        out = torch.empty_like(x)
+        _C.check(_C.lib.hypad_geodesic_fwd(_C.ptr(t1), _C.ptr(x), _C.ptr(y), _C.ptr(out), rows, d, t1.shape[0], _C.stream()), "geodesic_fwd")
+        ctx.save_for_backward(t1, x, y)
+        ctx.ts = t.shape
+        return out
+
+    @staticmethod
+    @_C.first_order_only
+    def backward(ctx, go):
+        t1, x, y = ctx.saved_tensors
+        rows, d = _rows_width(x)
+        go = go.to(torch.float32).contiguous()
+        gt = torch.empty(rows, device=x.device, dtype=torch.float32) if ctx.needs_input_grad[0] else None
+        gx = torch.empty_like(x) if ctx.needs_input_grad[1] else None
+        gy = torch.empty_like(y) if ctx.needs_input_grad[2] else None
+        _C.check(_C.lib.hypad_geodesic_bwd(_C.ptr(t1), _C.ptr(x), _C.ptr(y), _C.ptr(go), _C.ptr(gt), _C.ptr(gx), _C.ptr(gy), rows, d, t1.shape[0],
+                                           _C.stream()), "geodesic_bwd")
+        if gt is not None and t1.shape[0] == 1 and rows != 1:   # one t for every row: the rows' contributions, added in a fixed order
+            red = torch.empty(1, device=x.device, dtype=torch.float32)
+            _C.check(_C.lib.hypad_column_sum(_C.ptr(gt), _C.ptr(red), rows, 1, _C.stream()))
+            gt = red
+        return None if gt is None else gt.view(ctx.ts), gx, gy
+
+
+_TANGENT_SUPPORTED = ("supported: k = -1, dim = -1, fp32, operands of the same last dimension whose leading dimensions broadcast against "
+                      "each other, rows of 1 to 256 elements, fewer than 2^31 elements")
+
+
+def _tangent_operands(what, k, dim, **ops):
+    """The operands of a tangent map, broadcast against each other by torch's rules (expanded views: a broadcast operand's gradient is
+    summed by autograd, the expand's backward); every refusal comes before any device call."""
+    if k is not None and abs(float(k) + 1.0) > 1e-12:
+        raise NotImplementedError(f"{what}: curvature k = {float(k)} is not implemented; {_TANGENT_SUPPORTED}")
+    desc = ", ".join(f"{n} {tuple(t.shape)} {t.dtype}" for n, t in ops.items())
+    ts = list(ops.values())
+    if any(t.dim() < 1 or t.dtype != torch.float32 or t.shape[-1] != ts[0].shape[-1] for t in ts) or not 1 <= ts[0].shape[-1] <= 256:
+        raise NotImplementedError(f"{what}: {desc} is not implemented; {_TANGENT_SUPPORTED}")
+    try:
+        shape = torch.broadcast_shapes(*(tuple(t.shape) for t in ts))
+    except RuntimeError:
+        raise NotImplementedError(f"{what}: {desc} do not broadcast against each other; {_TANGENT_SUPPORTED}") from None
+    if dim != -1 and dim != len(shape) - 1:
+        raise NotImplementedError(f"{what}: dim = {dim} on {desc} is not implemented; {_TANGENT_SUPPORTED}")
+    count = 1
+    for n in shape:
+        count *= n
+    if count >= 2 ** 31:
+        raise NotImplementedError(f"{what}: {desc} ({count} elements) is not implemented; {_TANGENT_SUPPORTED}")
+    return torch.broadcast_tensors(*ts)
+
+
+def expmap(x, u, *, k, dim=-1):
+    """The exponential map at x: the point reached from x along the tangent vector u, x (+) (tanh(lambda_x |u| / 2) u / |u|)
+    (math_.py:1052-1102) at k = -1.  One HIP launch forward and one backward, a wave per row in fp64 registers; first-order
+    differentiable in x and u, which are broadcast against each other."""
+    return _RowMap.apply("expmap", *_tangent_operands("expmap", k, dim, x=x, u=u))
+
+
+def logmap(x, y, *, k, dim=-1):
+    """The logarithmic map at x: the tangent vector at x that points to y, 2 artanh(|w|) w / (lambda_x |w|) with w = (-x) (+) y
+    (math_.py:1188-1230) at k = -1.  One HIP launch forward and one backward; first-order differentiable in x and y, which are broadcast
+    against each other: ``logmap(centroid (B, 1, D), xs (B, N, D))`` maps a batch into the tangent space at its centroid.
+
+    The one deliberate difference from the reference: artanh is 0.5 (log1p(n) - log1p(-n)), so at coincident or near-coincident points
+    the result and its gradient follow the analytic limit artanh(n) / n -> 1, where the reference's fp32 run -- a difference of two
+    logarithms -- returns a gradient of exactly 0.  There is no singularity at x == y and no special case for it."""
+    return _RowMap.apply("logmap", *_tangent_operands("logmap", k, dim, x=x, y=y))
+
+
+def geodesic(t, x, y, *, k, dim=-1):
+    """The point at time t of the geodesic from x (t = 0) to y (t = 1), x (+) (t (x) ((-x) (+) y)) (math_.py:978-1049) at k = -1.  One
+    HIP launch forward and one backward; first-order differentiable in t, x and y.  x and y are broadcast against each other; t is a
+    number, a tensor of one element, or holds one value per row, shape x.shape[:-1] + (1,) after that broadcast.
+
+    As in logmap, artanh is the log1p form: at coincident or near-coincident x and y the result and its gradients follow the analytic
+    limit, where the reference's fp32 run returns a gradient of exactly 0."""
+    x, y = _tangent_operands("geodesic", k, dim, x=x, y=y)
+    if not isinstance(t, torch.Tensor):
+        t = torch.tensor(float(t), dtype=torch.float32, device=x.device)
+    if t.dtype != torch.float32 or (t.numel() != 1 and tuple(t.shape) != tuple(x.shape[:-1]) + (1,)):
+        raise NotImplementedError(f"geodesic: t {tuple(t.shape)} {t.dtype} against x and y broadcast to {tuple(x.shape)} is not implemented; "
+                                  f"{_TANGENT_SUPPORTED}, t a number, of one element or of shape x.shape[:-1] + (1,)")
+    return _Geodesic.apply(t, x, y)
+
+
+def gyration(a, b, u, *, k, dim=-1):
+    """The gyration gyr[a, b] u = -(a (+) b) (+) (a (+) (b (+) u)) in its closed form (math_.py:592-675) at k = -1.  One HIP launch
+    forward and one backward; first-order differentiable in a, b and u, which are broadcast against each other."""
+    return _RowMap.apply("gyration", *_tangent_operands("gyration", k, dim, a=a, b=b, u=u))
+
+
+def parallel_transport(x, y, v, *, k, dim=-1):
+    """The parallel transport of the tangent vector v from x to y along their geodesic, gyr[y, -x] v lambda_x / lambda_y
+    (math_.py:1669-1746) at k = -1.  One HIP launch forward and one backward; first-order differentiable in x, y and v, which are
+    broadcast against each other."""
+    return _RowMap.apply("parallel_transport", *_tangent_operands("parallel_transport", k, dim, x=x, y=y, v=v))
+
+
+def parallel_transport0(y, v, *, k, dim=-1):
+    """The parallel transport of v from the origin to y, v (1 - |y|^2) (math_.py:1749-1779) at k = -1.  One HIP launch forward and one
+    backward; first-order differentiable in y and v, which are broadcast against each other."""
+    return _RowMap.apply("parallel_transport0", *_tangent_operands("parallel_transport0", k, dim, y=y, v=v))
+
+
+def parallel_transport0back(x, v, *, k, dim=-1):
+    """The parallel transport of v from x to the origin, v / (1 - |x|^2) (math_.py:1782-1813) at k = -1.  One HIP launch forward and one
+    backward; first-order differentiable in x and v, which are broadcast against each other."""
+    return _RowMap.apply("parallel_transport0back", *_tangent_operands("parallel_transport0back", k, dim, x=x, v=v))
 
 
 def mobius_fn_apply(fn, x, *args, k=None, dim=-1, **kwargs):

@@ -220,6 +220,46 @@ int hypad_dist_bwd(const float* x, const float* y, const float* grad_out, float*
                    hypad_stream_t stream);
 int hypad_dist0_fwd(const float* x, float* out, int64_t rows, int dim, hypad_stream_t stream);
 int hypad_dist0_bwd(const float* x, const float* grad_out, float* grad_x, int64_t rows, int dim, hypad_stream_t stream);
+/* The tangent maps at a point of the ball, at k = -1, on rows (rows, dim) of fp32; c(x) = max(1 - |x|^2, 1e-15) = 2 / lambda_x:
+ *   gmath.expmap  math_.py:1052-1102 (_expmap :1097-1102):  x (+) (tanh(min(n / c(x), 15)) u / n),  n = max(|u|, 1e-15)
+ *   gmath.logmap  math_.py:1188-1230 (_logmap :1226-1230):  artanh(min(n, 1 - 1e-7)) c(x) w / n,  w = (-x) (+) y,  n = max(|w|, 1e-15)
+ *   gmath.geodesic  math_.py:978-1049 (_geodesic :1042-1049):  x (+) (t (x) ((-x) (+) y)), (x) as hypad_mobius_scalar_mul_fwd;
+ *     t holds t_count values: 1, or one per row
+ *   gmath.gyration  math_.py:592-675 (_gyration :657-675):  u + 2 (A a + B b) / max(1 + 2 <a,b> + |a|^2 |b|^2, 1e-15),
+ *     A = -<a,u> |b|^2 + <b,u> + 2 <a,b> <b,u>,  B = -<b,u> |a|^2 - <a,u>
+ *   gmath.parallel_transport  math_.py:1669-1746 (_parallel_transport :1739-1746):  gyration(y, -x, v) c(y) / c(x)
+ *   gmath.parallel_transport0  math_.py:1749-1779 (_parallel_transport0 :1776-1779):  v c(y)
+ *   gmath.parallel_transport0back  math_.py:1782-1813 (_parallel_transport0back :1810-1813):  v / c(x)
+ * One launch forward and one backward each, a wave per row in fp64 registers; the backward recomputes everything from the operands.
+ * artanh is 0.5 (log1p(n) - log1p(-n)): at coincident points logmap and geodesic follow artanh(n) / n -> 1, where the reference's fp32
+ * difference of two logarithms returns 0.  Nothing flows back through a clamp that holds; the norm's gradient at 0 is 0.
+ * bwd: every gradient may be NULL and the others keep their bits.  grad_t (rows) receives the per-row dL/dt -- with t_count == 1 the
+ * contributions to be summed by the caller (hypad_column_sum at dim = 1), as hypad_mobius_scalar_mul_bwd's grad_r.  No atomics, no
+ * workspace: two runs give the same bits.
+ * Every argument is validated before anything is launched: HYPAD_EINVAL for a NULL operand that has elements, rows < 0, dim <= 0 or a
+ * t_count that is neither 1 nor rows; HYPAD_EUNSUPPORTED for dim > 256 or rows dim >= 2^31; rows == 0 launches nothing. */
+int hypad_expmap_fwd(const float* x, const float* u, float* out, int64_t rows, int dim, hypad_stream_t stream);
+int hypad_expmap_bwd(const float* x, const float* u, const float* grad_out, float* grad_x, float* grad_u, int64_t rows, int dim,
+                     hypad_stream_t stream);
+int hypad_logmap_fwd(const float* x, const float* y, float* out, int64_t rows, int dim, hypad_stream_t stream);
+int hypad_logmap_bwd(const float* x, const float* y, const float* grad_out, float* grad_x, float* grad_y, int64_t rows, int dim,
+                     hypad_stream_t stream);
+int hypad_geodesic_fwd(const float* t, const float* x, const float* y, float* out, int64_t rows, int dim, int64_t t_count,
+                       hypad_stream_t stream);
+int hypad_geodesic_bwd(const float* t, const float* x, const float* y, const float* grad_out, float* grad_t, float* grad_x, float* grad_y,
+                       int64_t rows, int dim, int64_t t_count, hypad_stream_t stream);
+int hypad_gyration_fwd(const float* a, const float* b, const float* u, float* out, int64_t rows, int dim, hypad_stream_t stream);
+int hypad_gyration_bwd(const float* a, const float* b, const float* u, const float* grad_out, float* grad_a, float* grad_b, float* grad_u,
+                       int64_t rows, int dim, hypad_stream_t stream);
+int hypad_parallel_transport_fwd(const float* x, const float* y, const float* v, float* out, int64_t rows, int dim, hypad_stream_t stream);
+int hypad_parallel_transport_bwd(const float* x, const float* y, const float* v, const float* grad_out, float* grad_x, float* grad_y,
+                                 float* grad_v, int64_t rows, int dim, hypad_stream_t stream);
+int hypad_parallel_transport0_fwd(const float* y, const float* v, float* out, int64_t rows, int dim, hypad_stream_t stream);
+int hypad_parallel_transport0_bwd(const float* y, const float* v, const float* grad_out, float* grad_y, float* grad_v, int64_t rows, int dim,
+                                  hypad_stream_t stream);
+int hypad_parallel_transport0back_fwd(const float* x, const float* v, float* out, int64_t rows, int dim, hypad_stream_t stream);
+int hypad_parallel_transport0back_bwd(const float* x, const float* v, const float* grad_out, float* grad_x, float* grad_v, int64_t rows,
+                                      int dim, hypad_stream_t stream);
 /* gmath.hyperbolic_attention: the composition of dist_matmul (math_.py:905-947), a softmax over the keys and weighted_midpoint_bmm
  * without lincomb (math_.py:2090-2122) at k = -1, with no N x M tensor in memory.  q (batch, N, D), keys (batch, M, D), values
  * (batch, M, E) on the ball, out and grad_out (batch, N, E); bias NULL or fp32 (N, M) per batch element at bias_batch_stride elements
