@@ -162,6 +162,26 @@ _SIGS = {
     "hypad_parallel_transport0_bwd": (c_int, [P, P, P, P, P, c_int64, c_int, P]),
     "hypad_parallel_transport0back_fwd": (c_int, [P, P, P, c_int64, c_int, P]),
     "hypad_parallel_transport0back_bwd": (c_int, [P, P, P, P, P, c_int64, c_int, P]),
+    "hypad_mobius_sub_fwd": (c_int, [P, P, P, c_int64, c_int, P]),
+    "hypad_mobius_sub_bwd": (c_int, [P, P, P, P, P, c_int64, c_int, P]),
+    "hypad_mobius_coadd_fwd": (c_int, [P, P, P, c_int64, c_int, P]),
+    "hypad_mobius_coadd_bwd": (c_int, [P, P, P, P, P, c_int64, c_int, P]),
+    "hypad_mobius_cosub_fwd": (c_int, [P, P, P, c_int64, c_int, P]),
+    "hypad_mobius_cosub_bwd": (c_int, [P, P, P, P, P, c_int64, c_int, P]),
+    "hypad_geodesic_unit_fwd": (c_int, [P, P, P, P, c_int64, c_int, c_int64, P]),
+    "hypad_geodesic_unit_bwd": (c_int, [P, P, P, P, P, P, P, c_int64, c_int, c_int64, P]),
+    "hypad_lambda_x_fwd": (c_int, [P, P, c_int64, c_int, P]),
+    "hypad_lambda_x_bwd": (c_int, [P, P, P, c_int64, c_int, P]),
+    "hypad_inner_fwd": (c_int, [P, P, P, P, c_int64, c_int, P]),
+    "hypad_inner_bwd": (c_int, [P, P, P, P, P, P, P, c_int64, c_int, P]),
+    "hypad_norm_fwd": (c_int, [P, P, P, c_int64, c_int, P]),
+    "hypad_norm_bwd": (c_int, [P, P, P, P, P, c_int64, c_int, P]),
+    "hypad_egrad2rgrad_fwd": (c_int, [P, P, P, c_int64, c_int, P]),
+    "hypad_egrad2rgrad_bwd": (c_int, [P, P, P, P, P, c_int64, c_int, P]),
+    "hypad_sproj_fwd": (c_int, [P, P, c_int64, c_int, P]),
+    "hypad_sproj_bwd": (c_int, [P, P, P, c_int64, c_int, P]),
+    "hypad_inv_sproj_fwd": (c_int, [P, P, c_int64, c_int, P]),
+    "hypad_inv_sproj_bwd": (c_int, [P, P, P, c_int64, c_int, P]),
     "hypad_hyp_attention_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int, c_int]),
     "hypad_hyp_attention_fwd": (c_int, [P, P, P, P, c_int64, c_double, P, P, P, c_int64, c_int64, c_int64, c_int, c_int, P]),
     "hypad_hyp_attention_bwd": (c_int, [P, P, P, P, c_int64, c_double, P, P, P, P, P, P, c_void_p, c_size_t, c_int64, c_int64, c_int64, c_int, c_int, P]),

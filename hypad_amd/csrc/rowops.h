@@ -653,6 +653,170 @@ __device__ __forceinline__ void transport0_bwd_d(const R& p, const R& v, const R
   HYPAD_ROW_EACH { dp.v[e] = k * p.v[e]; dv.v[e] = s * go.v[e]; }
 }
 
+// The rest of the gyrogroup and the metric (math_.py:558-589 mobius_sub, :678-744 mobius_coadd, :747-779 mobius_cosub, :1139-1185
+// geodesic_unit, :355-383 lambda_x, :386-430 inner, :433-472 norm, :1816-1845 egrad2rgrad, :1848-1874 sproj, :1877-1905 inv_sproj).
+// mobius_sub: x (+) (-y)
+template <class R>
+__device__ __forceinline__ R mobius_sub_d(const R& x, const R& y) { return mobius_add_d(x, rowd_neg(y)); }
+template <class R>
+__device__ __forceinline__ void mobius_sub_bwd_d(const R& x, const R& y, const R& go, R& dx, R& dy) {
+  R dny;
+  mobius_add_bwd_d(x, rowd_neg(y), go, dx, dny);
+  dy = rowd_neg(dny);
+}
+// mobius_coadd: ((1 - |y|^2) x + (1 - |x|^2) y) / max(1 - |x|^2 |y|^2, 1e-15);  mobius_cosub (SUB): the same of x and -y
+template <bool SUB, class R>
+__device__ __forceinline__ R mobius_coadd_d(const R& x, const R& ys) {
+  const R y = SUB ? rowd_neg(ys) : ys;
+  const double x2 = rowd_dot(x, x), y2 = rowd_dot(y, y);
+  const double A = 1.0 - y2, B = 1.0 - x2, rD = 1.0 / fmax(1.0 - x2 * y2, DIST_EPS);
+  R m;
+#pragma unroll
+  HYPAD_ROW_EACH m.v[e] = (A * x.v[e] + B * y.v[e]) * rD;
+  return m;
+}
+template <bool SUB, class R>
+__device__ __forceinline__ void mobius_coadd_bwd_d(const R& x, const R& ys, const R& go, R& dx, R& dy) {
+  const R y = SUB ? rowd_neg(ys) : ys;
+  const double x2 = rowd_dot(x, x), y2 = rowd_dot(y, y);
+  const double A = 1.0 - y2, B = 1.0 - x2, draw = 1.0 - x2 * y2, rD = 1.0 / fmax(draw, DIST_EPS);
+  R m, dN;
+#pragma unroll
+  HYPAD_ROW_EACH { m.v[e] = (A * x.v[e] + B * y.v[e]) * rD; dN.v[e] = go.v[e] * rD; }
+  const double dD = draw >= DIST_EPS ? -rowd_dot(go, m) * rD : 0.0;
+  const double dA = rowd_dot(dN, x), dB = rowd_dot(dN, y);
+  const double dx2 = -dB - y2 * dD, dy2 = -dA - x2 * dD, sy = SUB ? -1.0 : 1.0;
+#pragma unroll
+  HYPAD_ROW_EACH { dx.v[e] = A * dN.v[e] + 2.0 * dx2 * x.v[e]; dy.v[e] = sy * (B * dN.v[e] + 2.0 * dy2 * y.v[e]); }
+}
+// geodesic_unit: x (+) (tanh(clamp(t / 2, +-15)) u / n), n = max(|u|, 1e-15); the backward returns dL/dt
+template <class R>
+__device__ __forceinline__ R geodesic_unit_d(double t, const R& x, const R& u) {
+  const double f = tanh_clamped2_d(0.5 * t) / fmax(sqrt(rowd_dot(u, u)), (double)MIN_NORM);
+  R s;
+#pragma unroll
+  HYPAD_ROW_EACH s.v[e] = f * u.v[e];
+  return mobius_add_d(x, s);
+}
+template <class R>
+__device__ __forceinline__ double geodesic_unit_bwd_d(double t, const R& x, const R& u, const R& go, R& dx, R& du) {
+  const double raw = sqrt(rowd_dot(u, u)), n = fmax(raw, (double)MIN_NORM);
+  const double th = tanh_clamped2_d(0.5 * t), tp = tanh_prime2_d(0.5 * t, th), f = th / n;
+  R s, ds;
+#pragma unroll
+  HYPAD_ROW_EACH s.v[e] = f * u.v[e];
+  mobius_add_bwd_d(x, s, go, dx, ds);
+  const double gf = rowd_dot(ds, u);                             // d L / d f;  f = tanh(t / 2) / n
+  const double cu = raw >= (double)MIN_NORM ? -gf * th / (n * n * n) : 0.0;
+#pragma unroll
+  HYPAD_ROW_EACH du.v[e] = f * ds.v[e] + cu * u.v[e];
+  return 0.5 * gf * tp / n;
+}
+// lambda_x = 2 / c(x), one value per row
+template <class R>
+__device__ __forceinline__ double lambda_x_d(const R& x) { return 2.0 / conformal_d(rowd_dot(x, x)); }
+template <class R>
+__device__ __forceinline__ void lambda_x_bwd_d(const R& x, double g, R& dx) {
+  const double x2 = rowd_dot(x, x), c = conformal_d(x2);
+  const double k = -4.0 * g / (c * c) * conformal_prime_d(x2);    // 2 dL/d|x|^2
+#pragma unroll
+  HYPAD_ROW_EACH dx.v[e] = k * x.v[e];
+}
+// inner: lambda_x^2 <u, v>
+template <class R>
+__device__ __forceinline__ double inner_d(const R& x, const R& u, const R& v) {
+  const double c = conformal_d(rowd_dot(x, x));
+  return 4.0 / (c * c) * rowd_dot(u, v);
+}
+template <class R>
+__device__ __forceinline__ void inner_bwd_d(const R& x, const R& u, const R& v, double g, R& dx, R& du, R& dv) {
+  const double x2 = rowd_dot(x, x), c = conformal_d(x2), l2 = 4.0 / (c * c);
+  const double k = -16.0 * g * rowd_dot(u, v) / (c * c * c) * conformal_prime_d(x2), s = g * l2;
+#pragma unroll
+  HYPAD_ROW_EACH { dx.v[e] = k * x.v[e]; du.v[e] = s * v.v[e]; dv.v[e] = s * u.v[e]; }
+}
+// norm: lambda_x |u|, the Euclidean norm without a clamp; a zero tangent gets gradient 0
+template <class R>
+__device__ __forceinline__ double tangent_norm_d(const R& x, const R& u) { return 2.0 / conformal_d(rowd_dot(x, x)) * sqrt(rowd_dot(u, u)); }
+template <class R>
+__device__ __forceinline__ void tangent_norm_bwd_d(const R& x, const R& u, double g, R& dx, R& du) {
+  const double x2 = rowd_dot(x, x), c = conformal_d(x2), n = sqrt(rowd_dot(u, u));
+  const double k = -4.0 * g * n / (c * c) * conformal_prime_d(x2), s = n > 0.0 ? 2.0 * g / (c * n) : 0.0;
+#pragma unroll
+  HYPAD_ROW_EACH { dx.v[e] = k * x.v[e]; du.v[e] = s * u.v[e]; }
+}
+// egrad2rgrad: grad / lambda_x^2 = grad c(x)^2 / 4
+template <class R>
+__device__ __forceinline__ R egrad2rgrad_d(const R& x, const R& g) {
+  const double c = conformal_d(rowd_dot(x, x)), s = 0.25 * c * c;
+  R o;
+#pragma unroll
+  HYPAD_ROW_EACH o.v[e] = s * g.v[e];
+  return o;
+}
+template <class R>
+__device__ __forceinline__ void egrad2rgrad_bwd_d(const R& x, const R& g, const R& go, R& dx, R& dg) {
+  const double x2 = rowd_dot(x, x), c = conformal_d(x2), s = 0.25 * c * c;
+  const double k = rowd_dot(go, g) * c * conformal_prime_d(x2);   // 2 dL/d|x|^2
+#pragma unroll
+  HYPAD_ROW_EACH { dx.v[e] = k * x.v[e]; dg.v[e] = s * go.v[e]; }
+}
+// The two projections between the ball (D columns) and the hyperboloid (D + 1, the time-like coordinate last).  The element at one
+// column of a row, for every lane: a masked sum.
+template <class R>
+__device__ __forceinline__ double rowd_at(const R& a, int col, int lane) {
+  double s = 0.0;
+#pragma unroll
+  HYPAD_ROW_EACH s += (lane & (R::G - 1)) + R::G * e == col ? a.v[e] : 0.0;
+  return groupd_sum<R::G>(s);
+}
+template <class R>
+__device__ __forceinline__ void rowd_set(R& a, int col, int lane, double val) {
+#pragma unroll
+  HYPAD_ROW_EACH if ((lane & (R::G - 1)) + R::G * e == col) a.v[e] = val;
+}
+// sproj: h[:D] / (1 + h[D]), no clamp.  The result's column D is left as it comes: the store ends before it.
+template <class R>
+__device__ __forceinline__ R sproj_d(const R& h, int D, int lane) {
+  const double f = 1.0 / (1.0 + rowd_at(h, D, lane));
+  R o;
+#pragma unroll
+  HYPAD_ROW_EACH o.v[e] = f * h.v[e];
+  return o;
+}
+// go holds D columns (column D zero, as rowd_load leaves it)
+template <class R>
+__device__ __forceinline__ R sproj_bwd_d(const R& h, const R& go, int D, int lane) {
+  const double hD = rowd_at(h, D, lane), f = 1.0 / (1.0 + hD);
+  const double gD = -f * f * (rowd_dot(go, h));                   // (go's column D is zero: the sum runs over the D space-like columns)
+  R dh;
+#pragma unroll
+  HYPAD_ROW_EACH dh.v[e] = f * go.v[e];
+  rowd_set(dh, D, lane, gD);
+  return dh;
+}
+// inv_sproj: cat(lambda_x x, lambda_x - 1)
+template <class R>
+__device__ __forceinline__ R inv_sproj_d(const R& x, int D, int lane) {
+  const double lam = 2.0 / conformal_d(rowd_dot(x, x));
+  R o;
+#pragma unroll
+  HYPAD_ROW_EACH o.v[e] = lam * x.v[e];
+  rowd_set(o, D, lane, lam - 1.0);
+  return o;
+}
+// go holds D + 1 columns, x D (column D zero)
+template <class R>
+__device__ __forceinline__ R inv_sproj_bwd_d(const R& x, const R& go, int D, int lane) {
+  const double x2 = rowd_dot(x, x), c = conformal_d(x2), lam = 2.0 / c;
+  const double glam = rowd_dot(go, x) + rowd_at(go, D, lane);     // d L / d lambda
+  const double k = -4.0 * glam / (c * c) * conformal_prime_d(x2);
+  R dx;
+#pragma unroll
+  HYPAD_ROW_EACH dx.v[e] = lam * go.v[e] + k * x.v[e];
+  return dx;
+}
+
 // The GRU gate sigmoid(logmap0(y)) (hyrnn_nets.py:81-82).  (Columns past the row's end come out as 0.5: every use multiplies them
 // with a zero of the other operand before a sum is taken.)
 template <class R>

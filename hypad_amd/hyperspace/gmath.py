@@ -16,6 +16,11 @@ hyperbolic_attention is dist_matmul, a softmax and weighted_midpoint_bmm as one 
 expmap (:1052-1102), logmap (:1188-1230), geodesic (:978-1049), gyration (:592-675), parallel_transport (:1669-1746),
 parallel_transport0 (:1749-1779) and parallel_transport0back (:1782-1813) are the tangent maps at an arbitrary point of the ball: one
 HIP launch forward and one backward each, operands broadcast against each other (docs/history/tangent_maps.md).
+mobius_sub (:558-589), mobius_coadd (:678-744), mobius_cosub (:747-779) and geodesic_unit (:1139-1185) are the rest of the gyrogroup;
+lambda_x (:355-383), inner (:386-430), norm (:433-472) and egrad2rgrad (:1816-1845) the Riemannian metric -- with expmap the pieces of a
+hand-written Riemannian update --; sproj (:1848-1874) and inv_sproj (:1877-1905) move between the ball and the hyperboloid: one HIP launch
+forward and one backward each.  antipode (:1908-1950), mobius_fn_apply_chain (:1374-1428) and mobiusify (:1472-1498) need no kernel of
+their own (docs/history/gyro_ops.md).  With these every public function of math_.py but dist2plane_matmul has its counterpart here.
 """
 import torch
 
@@ -646,19 +651,19 @@ class _RowMap(torch.autograd.Function):
         return (None, *grads)
 
 
-class _Geodesic(torch.autograd.Function):
-    """hypad_geodesic_*: t of one element, or of one element per row of x and y (..., D)."""
+class _TimeRowMap(torch.autograd.Function):
+    """hypad_<name>_fwd / _bwd for geodesic and geodesic_unit: t of one element, or of one element per row of the two operands (..., D)."""
 
     @staticmethod
-    def forward(ctx, t, x, y):
+    def forward(ctx, name, t, x, y):
         x = _C.require_cuda(x.contiguous(), "x")
-        y = _C.require_cuda(y.contiguous(), "y")
+        y = _C.require_cuda(y.contiguous(), f"{name}: the second row operand")
         t1 = _C.require_cuda(t.contiguous().reshape(-1), "t")
         rows, d = _rows_width(x)
         out = torch.empty_like(x)
-        _C.check(_C.lib.hypad_geodesic_fwd(_C.ptr(t1), _C.ptr(x), _C.ptr(y), _C.ptr(out), rows, d, t1.shape[0], _C.stream()), "geodesic_fwd")
+        _C.check(getattr(_C.lib, f"hypad_{name}_fwd")(_C.ptr(t1), _C.ptr(x), _C.ptr(y), _C.ptr(out), rows, d, t1.shape[0], _C.stream()), f"{name}_fwd")
         ctx.save_for_backward(t1, x, y)
-        ctx.ts = t.shape
+        ctx.name, ctx.ts = name, t.shape
         return out
 
     @staticmethod
@@ -667,16 +672,65 @@ class _Geodesic(torch.autograd.Function):
         t1, x, y = ctx.saved_tensors
         rows, d = _rows_width(x)
         go = go.to(torch.float32).contiguous()
-        gt = torch.empty(rows, device=x.device, dtype=torch.float32) if ctx.needs_input_grad[0] else None
-        gx = torch.empty_like(x) if ctx.needs_input_grad[1] else None
-        gy = torch.empty_like(y) if ctx.needs_input_grad[2] else None
-        _C.check(_C.lib.hypad_geodesic_bwd(_C.ptr(t1), _C.ptr(x), _C.ptr(y), _C.ptr(go), _C.ptr(gt), _C.ptr(gx), _C.ptr(gy), rows, d, t1.shape[0],
-                                           _C.stream()), "geodesic_bwd")
+        gt = torch.empty(rows, device=x.device, dtype=torch.float32) if ctx.needs_input_grad[1] else None
+        gx = torch.empty_like(x) if ctx.needs_input_grad[2] else None
+        gy = torch.empty_like(y) if ctx.needs_input_grad[3] else None
+        _C.check(getattr(_C.lib, f"hypad_{ctx.name}_bwd")(_C.ptr(t1), _C.ptr(x), _C.ptr(y), _C.ptr(go), _C.ptr(gt), _C.ptr(gx), _C.ptr(gy), rows, d,
+                                                          t1.shape[0], _C.stream()), f"{ctx.name}_bwd")
         if gt is not None and t1.shape[0] == 1 and rows != 1:   # one t for every row: the rows' contributions, added in a fixed order
             red = torch.empty(1, device=x.device, dtype=torch.float32)
             _C.check(_C.lib.hypad_column_sum(_C.ptr(gt), _C.ptr(red), rows, 1, _C.stream()))
             gt = red
-        return None if gt is None else gt.view(ctx.ts), gx, gy
+        return None, None if gt is None else gt.view(ctx.ts), gx, gy
+
+
+class _RowScalar(torch.autograd.Function):
+    """hypad_<name>_fwd / _bwd for lambda_x, norm and inner: one to three operands of one shape (..., D) -> (...), one value per row."""
+
+    @staticmethod
+    def forward(ctx, name, *ops):
+        ops = [_C.require_cuda(t.contiguous(), f"{name}: operand {i}") for i, t in enumerate(ops)]
+        rows, d = _rows_width(ops[0])
+        out = torch.empty(ops[0].shape[:-1], device=ops[0].device, dtype=torch.float32)
+        _C.check(getattr(_C.lib, f"hypad_{name}_fwd")(*map(_C.ptr, ops), _C.ptr(out), rows, d, _C.stream()), f"{name}_fwd")
+        ctx.save_for_backward(*ops)
+        ctx.name = name
+        return out
+
+    @staticmethod
+    @_C.first_order_only
+    def backward(ctx, go):
+        ops = ctx.saved_tensors
+        rows, d = _rows_width(ops[0])
+        go = go.to(torch.float32).contiguous()
+        grads = [torch.empty_like(t) if need else None for t, need in zip(ops, ctx.needs_input_grad[1:])]
+        _C.check(getattr(_C.lib, f"hypad_{ctx.name}_bwd")(*map(_C.ptr, ops), _C.ptr(go), *map(_C.ptr, grads), rows, d, _C.stream()),
+                 f"{ctx.name}_bwd")
+        return (None, *grads)
+
+
+class _Projection(torch.autograd.Function):
+    """hypad_sproj_* (grow = -1) and hypad_inv_sproj_* (grow = +1): a (..., W) -> (..., W + grow); the entry points take the ball's width."""
+
+    @staticmethod
+    def forward(ctx, name, a, grow):
+        a = _C.require_cuda(a.contiguous(), name)
+        rows, w = _rows_width(a)
+        ball = w if grow > 0 else w - 1
+        out = torch.empty(*a.shape[:-1], w + grow, device=a.device, dtype=torch.float32)
+        _C.check(getattr(_C.lib, f"hypad_{name}_fwd")(_C.ptr(a), _C.ptr(out), rows, ball, _C.stream()), f"{name}_fwd")
+        ctx.save_for_backward(a)
+        ctx.name, ctx.ball = name, ball
+        return out
+
+    @staticmethod
+    @_C.first_order_only
+    def backward(ctx, go):
+        (a,) = ctx.saved_tensors
+        go = go.to(torch.float32).contiguous()
+        ga = torch.empty_like(a)
+        _C.check(getattr(_C.lib, f"hypad_{ctx.name}_bwd")(_C.ptr(a), _C.ptr(go), _C.ptr(ga), _rows_width(a)[0], ctx.ball, _C.stream()), f"{ctx.name}_bwd")
+        return None, ga, None
 
 
 _TANGENT_SUPPORTED = ("supported: k = -1, dim = -1, fp32, operands of the same last dimension whose leading dimensions broadcast against "
@@ -706,6 +760,16 @@ def _tangent_operands(what, k, dim, **ops):
     return torch.broadcast_tensors(*ts)
 
 
+def _time_operand(what, t, x):
+    """(t, x) with t of geodesic and geodesic_unit as a tensor: a number, one element, or one value per row of the broadcast x."""
+    if not isinstance(t, torch.Tensor):
+        t = torch.tensor(float(t), dtype=torch.float32, device=x.device)
+    if t.dtype != torch.float32 or (t.numel() != 1 and tuple(t.shape) != tuple(x.shape[:-1]) + (1,)):
+        raise NotImplementedError(f"{what}: t {tuple(t.shape)} {t.dtype} against row operands broadcast to {tuple(x.shape)} is not implemented; "
+                                  f"{_TANGENT_SUPPORTED}, t a number, of one element or of shape x.shape[:-1] + (1,)")
+    return t, x
+
+
 def expmap(x, u, *, k, dim=-1):
     """The exponential map at x: the point reached from x along the tangent vector u, x (+) (tanh(lambda_x |u| / 2) u / |u|)
     (math_.py:1052-1102) at k = -1.  One HIP launch forward and one backward, a wave per row in fp64 registers; first-order
@@ -732,12 +796,7 @@ def geodesic(t, x, y, *, k, dim=-1):
     As in logmap, artanh is the log1p form: at coincident or near-coincident x and y the result and its gradients follow the analytic
     limit, where the reference's fp32 run returns a gradient of exactly 0."""
     x, y = _tangent_operands("geodesic", k, dim, x=x, y=y)
-    if not isinstance(t, torch.Tensor):
-        t = torch.tensor(float(t), dtype=torch.float32, device=x.device)
-    if t.dtype != torch.float32 or (t.numel() != 1 and tuple(t.shape) != tuple(x.shape[:-1]) + (1,)):
-        raise NotImplementedError(f"geodesic: t {tuple(t.shape)} {t.dtype} against x and y broadcast to {tuple(x.shape)} is not implemented; "
-                                  f"{_TANGENT_SUPPORTED}, t a number, of one element or of shape x.shape[:-1] + (1,)")
-    return _Geodesic.apply(t, x, y)
+    return _TimeRowMap.apply("geodesic", *_time_operand("geodesic", t, x), y)
 
 
 def gyration(a, b, u, *, k, dim=-1):
@@ -763,6 +822,129 @@ def parallel_transport0back(x, v, *, k, dim=-1):
     """The parallel transport of v from x to the origin, v / (1 - |x|^2) (math_.py:1782-1813) at k = -1.  One HIP launch forward and one
     backward; first-order differentiable in x and v, which are broadcast against each other."""
     return _RowMap.apply("parallel_transport0back", *_tangent_operands("parallel_transport0back", k, dim, x=x, v=v))
+
+
+def mobius_sub(x, y, *, k, dim=-1):
+    """The Moebius subtraction x (+) (-y) (math_.py:558-589) at k = -1.  One HIP launch forward and one backward; first-order
+    differentiable in x and y, which are broadcast against each other."""
+    return _RowMap.apply("mobius_sub", *_tangent_operands("mobius_sub", k, dim, x=x, y=y))
+
+
+def mobius_coadd(x, y, *, k, dim=-1):
+    """The Moebius coaddition ((1 - |y|^2) x + (1 - |x|^2) y) / (1 - |x|^2 |y|^2), the commutative sum of the gyrogroup
+    (math_.py:678-744) at k = -1.  One HIP launch forward and one backward; first-order differentiable in x and y, which are broadcast
+    against each other."""
+    return _RowMap.apply("mobius_coadd", *_tangent_operands("mobius_coadd", k, dim, x=x, y=y))
+
+
+def mobius_cosub(x, y, *, k, dim=-1):
+    """The Moebius cosubtraction mobius_coadd(x, -y) (math_.py:747-779) at k = -1: ``mobius_cosub(mobius_add(x, y), y) = x``.  One HIP
+    launch forward and one backward; first-order differentiable in x and y, which are broadcast against each other."""
+    return _RowMap.apply("mobius_cosub", *_tangent_operands("mobius_cosub", k, dim, x=x, y=y))
+
+
+def geodesic_unit(t, x, u, *, k, dim=-1):
+    """The point at geodesic distance t from x in the direction of the tangent vector u, x (+) (tanh(t / 2) u / |u|)
+    (math_.py:1139-1185) at k = -1.  One HIP launch forward and one backward; first-order differentiable in t, x and u.  x and u are
+    broadcast against each other; t is a number, a tensor of one element, or holds one value per row, shape x.shape[:-1] + (1,) after
+    that broadcast."""
+    x, u = _tangent_operands("geodesic_unit", k, dim, x=x, u=u)
+    return _TimeRowMap.apply("geodesic_unit", *_time_operand("geodesic_unit", t, x), u)
+
+
+def _per_row(out, keepdim):
+    return out.unsqueeze(-1) if keepdim else out
+
+
+def lambda_x(x, *, k, keepdim=False, dim=-1):
+    """The conformal factor lambda_x = 2 / (1 - |x|^2) of the rows of x (math_.py:355-383) at k = -1 -> x.shape[:-1], or
+    x.shape[:-1] + (1,) with keepdim.  One HIP launch forward and one backward."""
+    return _per_row(_RowScalar.apply("lambda_x", *_tangent_operands("lambda_x", k, dim, x=x)), keepdim)
+
+
+def inner(x, u, v, *, k, keepdim=False, dim=-1):
+    """The Riemannian inner product lambda_x^2 <u, v> of the tangent vectors u and v at x (math_.py:386-430) at k = -1, one value per
+    row.  One HIP launch forward and one backward; first-order differentiable in x, u and v, which are broadcast against each other.
+
+    One deliberate difference from the reference: with keepdim=False the result has the shape x.shape[:-1] (after the broadcast), as
+    lambda_x, norm and dist have.  The reference multiplies lambda_x^2 of shape (..., 1) with a sum of shape (...), which broadcasts the
+    rows against each other: (33, 5) operands give (33, 33) there.  With keepdim=True the two agree."""
+    return _per_row(_RowScalar.apply("inner", *_tangent_operands("inner", k, dim, x=x, u=u, v=v)), keepdim)
+
+
+def norm(x, u, *, k, keepdim=False, dim=-1):
+    """The Riemannian norm lambda_x |u| of the tangent vector u at x (math_.py:433-472) at k = -1, one value per row.  One HIP launch
+    forward and one backward; first-order differentiable in x and u, which are broadcast against each other; a zero tangent gets
+    gradient 0."""
+    return _per_row(_RowScalar.apply("norm", *_tangent_operands("norm", k, dim, x=x, u=u)), keepdim)
+
+
+def egrad2rgrad(x, grad, *, k, dim=-1):
+    """The Riemannian gradient at x of a function whose Euclidean gradient there is ``grad``: grad / lambda_x^2 (math_.py:1816-1845) at
+    k = -1.  ``p <- expmap(p, -lr * egrad2rgrad(p, p.grad))`` is one step of Riemannian gradient descent.  One HIP launch forward and one
+    backward; first-order differentiable in x and grad, which are broadcast against each other."""
+    return _RowMap.apply("egrad2rgrad", *_tangent_operands("egrad2rgrad", k, dim, x=x, grad=grad))
+
+
+_PROJ_SUPPORTED = ("supported: k = -1, dim = -1, fp32, a ball side of 1 to 255 elements a row (the hyperboloid side, one more, of 2 to 256), fewer "
+                   "than 2^31 elements")
+
+
+def _projection_refusals(what, a, k, dim, grow):
+    if k is not None and abs(float(k) + 1.0) > 1e-12:
+        raise NotImplementedError(f"{what}: curvature k = {float(k)} is not implemented; {_PROJ_SUPPORTED}")
+    if a.dim() < 1 or (dim != -1 and dim != a.dim() - 1):
+        raise NotImplementedError(f"{what}: dim = {dim} on {tuple(a.shape)} is not implemented; {_PROJ_SUPPORTED}")
+    rows, wide = _rows_width(a)[0], a.shape[-1] + max(grow, 0)            # the hyperboloid side
+    if a.dtype != torch.float32 or not 2 <= wide <= 256 or rows * wide >= 2 ** 31:
+        raise NotImplementedError(f"{what}: {tuple(a.shape)} {a.dtype} is not implemented; {_PROJ_SUPPORTED}")
+
+
+def sproj(x, *, k, dim=-1):
+    """The stereographic projection of hyperboloid points x (..., D + 1), the time-like coordinate last, onto the ball:
+    x[..., :D] / (1 + x[..., D]) (math_.py:1848-1874) at k = -1, where the reference's inv_r = sqrt(|k| + 1e-15) is 1.  No clamp, as in the
+    reference.  One HIP launch forward and one backward."""
+    _projection_refusals("sproj", x, k, dim, -1)
+    return _Projection.apply("sproj", x, -1)
+
+
+def inv_sproj(x, *, k, dim=-1):
+    """The inverse stereographic projection of ball points x (..., D) onto the hyperboloid: cat(lambda_x x, lambda_x - 1), shape
+    (..., D + 1) (math_.py:1877-1905) at k = -1.  One HIP launch forward and one backward."""
+    _projection_refusals("inv_sproj", x, k, dim, 1)
+    return _Projection.apply("inv_sproj", x, 1)
+
+
+def antipode(x, *, k, dim=-1):
+    """The antipode of x (math_.py:1908-1950): -x for every k <= 0, as the reference returns.  No kernel."""
+    if k is not None and abs(float(k) + 1.0) > 1e-12:
+        raise NotImplementedError(f"antipode: curvature k = {float(k)} is not implemented; supported: k = -1")
+    return -x
+
+
+def mobius_fn_apply_chain(x, *fns, k=None, dim=-1):
+    """expmap0(fn_n(... fn_1(logmap0(x)))) (math_.py:1374-1428): the two maps are the HIP kernels above, the functions are the caller's
+    own.  Without a function it returns x."""
+    _check_k(k)
+    if dim != -1 and dim != x.dim() - 1:
+        raise NotImplementedError("mobius_fn_apply_chain: only the last dimension (dim = -1) is implemented")
+    if not fns:
+        return x
+    ex = logmap0(x)
+    for fn in fns:
+        ex = fn(ex)
+    return expmap0(ex)
+
+
+def mobiusify(fn):
+    """``fn`` wrapped to work on ball points (math_.py:1472-1498): the new function takes ``k`` and ``dim`` and is
+    mobius_fn_apply(fn, x, *args, k=k, dim=dim, **kwargs)."""
+    import functools
+
+    @functools.wraps(fn)
+    def mobius_fn(x, *args, k=None, dim=-1, **kwargs):
+        return mobius_fn_apply(fn, x, *args, k=k, dim=dim, **kwargs)
+    return mobius_fn
 
 
 def mobius_fn_apply(fn, x, *args, k=None, dim=-1, **kwargs):

@@ -355,6 +355,8 @@ class MobiusDist2Hyperplane(nn.Module):
 
     ``point`` and ``tangent`` are tagged ManifoldParameters (ball / Sphere), as in the reference.  hypad_amd.optim.RiemannianAdam does
     not know how to update them yet and refuses them; the layer trains with Euclidean optimisers (torch.optim.SGD / Adam) meanwhile.
+    A hand-written Riemannian step of ``point`` is ``p <- gmath.expmap(p, -lr * gmath.egrad2rgrad(p, p.grad, k=-1.0), k=-1.0)``
+    (docs/history/gyro_ops.md).
     """
 
     def __init__(self, in_features, out_features, k=-1.0, fp64_hyper=False):

@@ -260,6 +260,56 @@ int hypad_parallel_transport0_bwd(const float* y, const float* v, const float* g
 int hypad_parallel_transport0back_fwd(const float* x, const float* v, float* out, int64_t rows, int dim, hypad_stream_t stream);
 int hypad_parallel_transport0back_bwd(const float* x, const float* v, const float* grad_out, float* grad_x, float* grad_v, int64_t rows,
                                       int dim, hypad_stream_t stream);
+/* The rest of the gyrogroup and the Riemannian metric, at k = -1, on rows (rows, dim) of fp32, in the launch form of the tangent maps;
+ * (+) is hypad_mobius_add_fwd's, c(x) = max(1 - |x|^2, 1e-15), lambda_x = 2 / c(x):
+ *   gmath.mobius_sub  math_.py:558-589 (_mobius_sub :588-589):  x (+) (-y)
+ *   gmath.mobius_coadd  math_.py:678-744 (_mobius_coadd :731-744):  ((1 - |y|^2) x + (1 - |x|^2) y) / max(1 - |x|^2 |y|^2, 1e-15)
+ *   gmath.mobius_cosub  math_.py:747-779 (_mobius_cosub :778-779):  mobius_coadd(x, -y)
+ *   gmath.geodesic_unit  math_.py:1139-1185 (_geodesic_unit :1175-1185):  x (+) (tanh(clamp(t / 2, +-15)) u / max(|u|, 1e-15));
+ *     t holds t_count values: 1, or one per row
+ *   gmath.egrad2rgrad  math_.py:1816-1845 (_egrad2rgrad :1844-1845):  grad / lambda_x^2
+ * with one value per row for out and grad_out, (rows):
+ *   gmath.lambda_x  math_.py:355-383 (_lambda_x :382-383):  lambda_x
+ *   gmath.inner  math_.py:386-430 (_inner :420-430):  lambda_x^2 <u, v>
+ *   gmath.norm  math_.py:433-472 (_norm :463-472):  lambda_x |u|, the Euclidean norm without a clamp
+ * and between the ball, rows of dim elements, and the hyperboloid, rows of dim + 1 with the time-like coordinate last:
+ *   gmath.sproj  math_.py:1848-1874 (_sproj :1870-1874):  h (rows, dim + 1) -> h[:dim] / (1 + h[dim]) (rows, dim), no clamp
+ *   gmath.inv_sproj  math_.py:1877-1905 (_inv_sproj :1899-1905):  x (rows, dim) -> cat(lambda_x x, lambda_x - 1) (rows, dim + 1)
+ * One launch forward and one backward each, a wave per row in fp64 registers; the backward recomputes everything from the operands.
+ * Nothing flows back through a clamp that holds; the gradient of a Euclidean norm at 0 is 0.  bwd: every gradient may be NULL and the
+ * others keep their bits.  grad_t (rows) receives the per-row dL/dt, as hypad_geodesic_bwd's.  No atomics, no workspace: two runs
+ * give the same bits.
+ * Every argument is validated before anything is launched: HYPAD_EINVAL for a NULL operand that has elements, rows < 0, dim <= 0 or a
+ * t_count that is neither 1 nor rows; HYPAD_EUNSUPPORTED for dim > 256 (the projections: dim + 1 > 256) or rows dim >= 2^31 (the
+ * projections: rows (dim + 1)); rows == 0 launches nothing. */
+int hypad_mobius_sub_fwd(const float* x, const float* y, float* out, int64_t rows, int dim, hypad_stream_t stream);
+int hypad_mobius_sub_bwd(const float* x, const float* y, const float* grad_out, float* grad_x, float* grad_y, int64_t rows, int dim,
+                         hypad_stream_t stream);
+int hypad_mobius_coadd_fwd(const float* x, const float* y, float* out, int64_t rows, int dim, hypad_stream_t stream);
+int hypad_mobius_coadd_bwd(const float* x, const float* y, const float* grad_out, float* grad_x, float* grad_y, int64_t rows, int dim,
+                           hypad_stream_t stream);
+int hypad_mobius_cosub_fwd(const float* x, const float* y, float* out, int64_t rows, int dim, hypad_stream_t stream);
+int hypad_mobius_cosub_bwd(const float* x, const float* y, const float* grad_out, float* grad_x, float* grad_y, int64_t rows, int dim,
+                           hypad_stream_t stream);
+int hypad_geodesic_unit_fwd(const float* t, const float* x, const float* u, float* out, int64_t rows, int dim, int64_t t_count,
+                            hypad_stream_t stream);
+int hypad_geodesic_unit_bwd(const float* t, const float* x, const float* u, const float* grad_out, float* grad_t, float* grad_x,
+                            float* grad_u, int64_t rows, int dim, int64_t t_count, hypad_stream_t stream);
+int hypad_lambda_x_fwd(const float* x, float* out, int64_t rows, int dim, hypad_stream_t stream);
+int hypad_lambda_x_bwd(const float* x, const float* grad_out, float* grad_x, int64_t rows, int dim, hypad_stream_t stream);
+int hypad_inner_fwd(const float* x, const float* u, const float* v, float* out, int64_t rows, int dim, hypad_stream_t stream);
+int hypad_inner_bwd(const float* x, const float* u, const float* v, const float* grad_out, float* grad_x, float* grad_u, float* grad_v,
+                    int64_t rows, int dim, hypad_stream_t stream);
+int hypad_norm_fwd(const float* x, const float* u, float* out, int64_t rows, int dim, hypad_stream_t stream);
+int hypad_norm_bwd(const float* x, const float* u, const float* grad_out, float* grad_x, float* grad_u, int64_t rows, int dim,
+                   hypad_stream_t stream);
+int hypad_egrad2rgrad_fwd(const float* x, const float* grad, float* out, int64_t rows, int dim, hypad_stream_t stream);
+int hypad_egrad2rgrad_bwd(const float* x, const float* grad, const float* grad_out, float* grad_x, float* grad_grad, int64_t rows, int dim,
+                          hypad_stream_t stream);
+int hypad_sproj_fwd(const float* h, float* out, int64_t rows, int dim, hypad_stream_t stream);
+int hypad_sproj_bwd(const float* h, const float* grad_out, float* grad_h, int64_t rows, int dim, hypad_stream_t stream);
+int hypad_inv_sproj_fwd(const float* x, float* out, int64_t rows, int dim, hypad_stream_t stream);
+int hypad_inv_sproj_bwd(const float* x, const float* grad_out, float* grad_x, int64_t rows, int dim, hypad_stream_t stream);
 /* gmath.hyperbolic_attention: the composition of dist_matmul (math_.py:905-947), a softmax over the keys and weighted_midpoint_bmm
  * without lincomb (math_.py:2090-2122) at k = -1, with no N x M tensor in memory.  q (batch, N, D), keys (batch, M, D), values
  * (batch, M, E) on the ball, out and grad_out (batch, N, E); bias NULL or fp32 (N, M) per batch element at bias_batch_stride elements
