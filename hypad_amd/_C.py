@@ -144,6 +144,8 @@ _SIGS = {
     "hypad_weighted_midpoint_bmm_bwd": (c_int, [P, P, P, P, P, P, c_void_p, c_size_t, c_int64, c_int64, c_int64, c_int, c_int, P]),
     "hypad_dist_matmul_fwd": (c_int, [P, P, P, c_int64, c_int64, c_int64, c_int, P]),
     "hypad_dist_matmul_bwd": (c_int, [P, P, P, P, P, c_int64, c_int64, c_int64, c_int, P]),
+    "hypad_dist2plane_matmul_fwd": (c_int, [P, P, P, P, c_int64, c_int64, c_int64, c_int, P]),
+    "hypad_dist2plane_matmul_bwd": (c_int, [P, P, P, P, P, P, P, c_int64, c_int64, c_int64, c_int, P]),
     "hypad_dist_fwd": (c_int, [P, P, P, c_int64, c_int, P]),
     "hypad_dist_bwd": (c_int, [P, P, P, P, P, c_int64, c_int, P]),
     "hypad_dist0_fwd": (c_int, [P, P, c_int64, c_int, P]),

@@ -20,7 +20,10 @@ mobius_sub (:558-589), mobius_coadd (:678-744), mobius_cosub (:747-779) and geod
 lambda_x (:355-383), inner (:386-430), norm (:433-472) and egrad2rgrad (:1816-1845) the Riemannian metric -- with expmap the pieces of a
 hand-written Riemannian update --; sproj (:1848-1874) and inv_sproj (:1877-1905) move between the ball and the hyperboloid: one HIP launch
 forward and one backward each.  antipode (:1908-1950), mobius_fn_apply_chain (:1374-1428) and mobiusify (:1472-1498) need no kernel of
-their own (docs/history/gyro_ops.md).  With these every public function of math_.py but dist2plane_matmul has its counterpart here.
+their own (docs/history/gyro_ops.md).
+dist2plane_matmul (:2125-2159) is the batched hyperplane read-out in the operand layout of dist_matmul -- the reference's own formula,
+which is not 2 dist2plane(...) --: one HIP launch forward, two fused launches backward (docs/history/dist2plane_matmul.md).  With it every
+public function of math_.py has its counterpart here.
 """
 import torch
 
@@ -435,15 +438,84 @@ def dist_matmul(x, y, k):
     if x.shape[-1] > 256 or x.shape[-1] < 1 or count >= 2 ** 31:
         raise NotImplementedError(f"dist_matmul: x {tuple(x.shape)} against y {tuple(y.shape)} is not implemented; {_DISTMM_SUPPORTED}")
     yt = y.transpose(-1, -2)                                 # (..., M, D): contiguous already in the usual call
-    if bx != lead:
-        x = x.expand(*lead, *x.shape[-2:])
-    if by != lead:
-        yt = yt.expand(*lead, *yt.shape[-2:])
+    x3, (y3,) = _over_batch(lead, x, (yt,))
+    out = _DistMatmul.apply(x3, y3)
+    return out.view(*lead, x.shape[-2], yt.shape[-2])
+
+
+def _over_batch(lead, x, points):
+    """x (..., N, D) and every tensor of ``points`` (..., M, D) as (batch, rows, D) over the leading dimensions ``lead``: an operand
+    that carries none of them is expanded (materialised by the autograd function's ``contiguous``; the expand's backward sums its
+    gradient over the batch)."""
     nb = 1
     for n in lead:
         nb *= n
-    out = _DistMatmul.apply(x.reshape(nb, *x.shape[-2:]), yt.reshape(nb, *yt.shape[-2:]))
-    return out.view(*lead, x.shape[-2], yt.shape[-2])
+    flat = [(t if tuple(t.shape[:-2]) == lead else t.expand(*lead, *t.shape[-2:])) for t in (x, *points)]
+    flat = [t.reshape(nb, *t.shape[-2:]) for t in flat]
+    return flat[0], flat[1:]
+
+
+class _Dist2PlaneMatmul(torch.autograd.Function):
+    """hypad_dist2plane_matmul_*: x (batch, N, D), p and z (batch, M, D) -> (batch, N, M); saves the operands alone."""
+
+    @staticmethod
+    def forward(ctx, x, p, z):
+        x = _C.require_cuda(x.contiguous(), "x")
+        p = _C.require_cuda(p.contiguous(), "p")
+        z = _C.require_cuda(z.contiguous(), "z")
+        batch, n, d = x.shape
+        m = p.shape[1]
+        out = torch.empty(batch, n, m, device=x.device, dtype=torch.float32)
+        _C.check(_C.lib.hypad_dist2plane_matmul_fwd(_C.ptr(x), _C.ptr(p), _C.ptr(z), _C.ptr(out), batch, n, m, d, _C.stream()),
+                 "dist2plane_matmul_fwd")
+        ctx.save_for_backward(x, p, z)
+        return out
+
+    @staticmethod
+    @_C.first_order_only
+    def backward(ctx, go):
+        x, p, z = ctx.saved_tensors
+        batch, n, d = x.shape
+        go = go.to(torch.float32).contiguous()
+        gx, gp, gz = (torch.empty_like(t) if need else None for t, need in zip((x, p, z), ctx.needs_input_grad))
+        _C.check(_C.lib.hypad_dist2plane_matmul_bwd(_C.ptr(x), _C.ptr(p), _C.ptr(z), _C.ptr(go), _C.ptr(gx), _C.ptr(gp), _C.ptr(gz), batch, n,
+                                                    p.shape[1], d, _C.stream()), "dist2plane_matmul_bwd")
+        return gx, gp, gz
+
+
+_D2PMM_SUPPORTED = ("supported: k = -1, fp32, x (..., N, D) against points p and normals z of one shape (..., D, M), with the same leading batch "
+                    "dimensions on x and on the planes, or none on one side, 1 <= D <= 256, fewer than 2^31 elements in the output")
+
+
+def dist2plane_matmul(x, p, z, *, k):
+    """The reference's batched hyperplane read-out (math_.py:2125-2159) at k = -1: x (..., N, D) on the ball against M planes given by
+    their points p (..., D, M) on the ball and their normals z (..., D, M) -> (..., N, M), in the operand layout of ``dist_matmul``:
+    ``dist2plane_matmul(x, points.transpose(-1, -2), normals.transpose(-1, -2), k=k)``.  With zh = z / max(|z|, 1e-15),
+
+        out = 2 asinh((2 / max(1 - |p|^2, 1e-15)) (<x, zh> - (1 - 2 <x, p> + |x|^2) / max(1 - |x|^2, 1e-15) <p, zh>)) |z|
+
+    This is the reference's formula as it stands.  It is NOT ``2 * dist2plane(x, p, z, signed=True, scaled=True)`` of the transposed
+    operands: the two agree only where x = 0 (docs/history/dist2plane_matmul.md).  One HIP launch forward on fp32 MFMA with an fp64
+    epilogue, one fused launch for grad_x and one for grad_p and grad_z; first-order differentiable in x, p and z.  The planes are handed
+    to the kernels as rows (..., M, D): a p or z that is the transposed view of such a tensor is passed as it is, any other is copied
+    once.  x and the planes carry the same leading batch dimensions, or one side carries none: that side is expanded over the batch and
+    materialised on the host, and the sum of its gradient over the batch is left to autograd (the expand's backward)."""
+    if k is not None and abs(float(k) + 1.0) > 1e-12:
+        raise NotImplementedError(f"dist2plane_matmul: curvature k = {float(k)} is not implemented; {_D2PMM_SUPPORTED}")
+    bx, bp = tuple(x.shape[:-2]), tuple(p.shape[:-2])
+    if (x.dim() < 2 or p.dim() < 2 or p.shape != z.shape or p.shape[-2] != x.shape[-1] or (bx != bp and bx != () and bp != ())
+            or x.dtype != torch.float32 or p.dtype != torch.float32 or z.dtype != torch.float32):
+        raise NotImplementedError(f"dist2plane_matmul: x {tuple(x.shape)} {x.dtype} against p {tuple(p.shape)} {p.dtype} and z {tuple(z.shape)} "
+                                  f"{z.dtype} is not implemented; {_D2PMM_SUPPORTED}")
+    lead = bx or bp
+    count = x.shape[-2] * p.shape[-1]
+    for n in lead:
+        count *= n
+    if x.shape[-1] > 256 or x.shape[-1] < 1 or count >= 2 ** 31:
+        raise NotImplementedError(f"dist2plane_matmul: x {tuple(x.shape)} against planes {tuple(p.shape)} is not implemented; {_D2PMM_SUPPORTED}")
+    x3, (p3, z3) = _over_batch(lead, x, (p.transpose(-1, -2), z.transpose(-1, -2)))
+    out = _Dist2PlaneMatmul.apply(x3, p3, z3)
+    return out.view(*lead, x.shape[-2], p.shape[-1])
 
 
 class _Dist(torch.autograd.Function):

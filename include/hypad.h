@@ -210,6 +210,24 @@ int hypad_weighted_midpoint_bwd(const float* xs, const float* weights, int64_t w
 int hypad_dist_matmul_fwd(const float* x, const float* y, float* out, int64_t batch, int64_t N, int64_t M, int D, hypad_stream_t stream);
 int hypad_dist_matmul_bwd(const float* x, const float* y, const float* grad_out, float* grad_x, float* grad_y,
                           int64_t batch, int64_t N, int64_t M, int D, hypad_stream_t stream);
+/* gmath.dist2plane_matmul  math_.py:2125-2159 (_dist2plane_matmul :2136-2159) at k = -1: the reference's batched hyperplane read-out
+ * in the operand layout of dist_matmul.  x (batch, N, D) on the ball, the planes' points p and normals z (batch, M, D) -- row-major:
+ * the caller transposes the reference's (batch, D, M) --, out and grad_out (batch, N, M).  With zh = z / max(|z|, 1e-15),
+ * bx = max(1 - |x|^2, 1e-15), bp = max(1 - |p|^2, 1e-15), alpha = 1 - 2 <x, p> + |x|^2:
+ *   t = (2 / bp) (<x, zh> - (alpha / bx) <p, zh>)    out = 2 asinh(t) |z|
+ * -- not 2 hypad_dist2plane(signed, scaled) of the same operands: the two agree only at x = 0.
+ * One launch: <x, p> and <x, z> on fp32 MFMA from one staged x tile, the norms and <p, z> as fp64 sums of the staged values (1 - |x|^2
+ * and 1 - |p|^2 come from those sums), the epilogue in fp64 registers.  bwd: one fused launch for grad_x, one for grad_p and grad_z
+ * together (the pair terms are recomputed tile by tile: no N x M intermediate, no workspace); each gradient may be NULL and the others
+ * keep their bits.  Nothing flows through a clamp that holds; a zero normal gives out = 0 and adds nothing to any gradient.  No
+ * atomics: two runs give the same bits.  batch, N or M == 0 launches nothing and writes zeros to the gradients.
+ * Every argument is validated before anything is launched: HYPAD_EINVAL for a NULL operand (x, p, z, out / grad_out) that has
+ * elements, a negative batch, N or M, or D <= 0; HYPAD_EUNSUPPORTED for D > 256, an element count of 2^31 or more, or LDS that does
+ * not fit. */
+int hypad_dist2plane_matmul_fwd(const float* x, const float* p, const float* z, float* out, int64_t batch, int64_t N, int64_t M, int D,
+                                hypad_stream_t stream);
+int hypad_dist2plane_matmul_bwd(const float* x, const float* p, const float* z, const float* grad_out, float* grad_x, float* grad_p,
+                                float* grad_z, int64_t batch, int64_t N, int64_t M, int D, hypad_stream_t stream);
 /* gmath.dist  math_.py:861-902 (_dist :893-902, _mobius_add :536-555) at k = -1: 2 artanh(|(-x) (+) y|) of the rows of x and y
  * (rows, dim), out and grad_out (rows); the norm has no clamp, artanh clamps at 1 - 1e-7.  A wave per row in fp64 registers.  Two
  * rows that are equal element by element give distance 0 and gradient 0.  bwd: grad_x or grad_y may be NULL.
