@@ -120,10 +120,14 @@ class _LstmBidirT1(torch.autograd.Function):
 
 
 def linear_act(x, weight, bias, act=_C.ACT_NONE):
+    """act(x W^T + b) for x (rows, in): nn.Linear followed by nothing, nn.Tanh or nn.LeakyReLU(0.2).  Floating operands of any dtype are
+    cast to fp32 and the result is fp32."""
     return _LinearAct.apply(x, weight, bias, act)
 
 
 def lstm_layer(x, group, layer):
+    """One bidirectional LSTM layer of the parameter holder ``group`` at sequence length 1 on x (rows, in) -> (rows, 2H).  Floating operands
+    of any dtype are cast to fp32 and the result is fp32."""
     g = lambda n: getattr(group, n)
     sfx = f"_l{layer}"
     return _LstmBidirT1.apply(x, g("weight_ih" + sfx), g("weight_hh" + sfx), g("bias_ih" + sfx), g("bias_hh" + sfx),
@@ -215,7 +219,8 @@ class _LstmBidirSeq(torch.autograd.Function):
 
 def lstm_seq(x, lstm, layer=0, hx=None):
     """The differentiable form of lstm_seq_forward: ``(out, (h_n, c_n))`` of one bidirectional layer of a ``torch.nn.LSTM``-shaped parameter holder
-    over (T, rows, in), with gradients for the input, the initial states and all eight parameters (back-propagation through time on the device)."""
+    over (T, rows, in), with gradients for the input, the initial states and all eight parameters (back-propagation through time on the device).
+    Floating operands of any dtype are cast to fp32 and the results are fp32."""
     names = ("weight_ih", "weight_hh", "bias_ih", "bias_hh")
     ps = [getattr(lstm, n + f"_l{layer}") for n in names] + [getattr(lstm, n + f"_l{layer}_reverse") for n in names]
     h0, c0 = (None, None) if hx is None else hx
@@ -227,7 +232,8 @@ def lstm_seq_forward(x, lstm, layer=0, hx=None):
     """One bidirectional layer of a ``torch.nn.LSTM``-shaped parameter holder over a whole sequence (inference): ``x`` (T, rows, in)
     -> ``(out (T, rows, 2H), (h_n, c_n) each (2, rows, H))`` as ``nn.LSTM(in, H, bidirectional=True)(x, hx)`` returns them.  The
     reference's modules (models/tadgan.py:15-20, :35-38) are such layers driven with T = 1; this is the general-T
-    form: one MFMA GEMM for the input projections of all steps + a persistent recurrence kernel (csrc/lstm_seq.hip)."""
+    form: one MFMA GEMM for the input projections of all steps + a persistent recurrence kernel (csrc/lstm_seq.hip).  Floating operands of any
+    dtype are cast to fp32 and the results are fp32."""
     if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in lstm.parameters())):
         raise _C.HypadError("lstm_seq_forward is the inference form: wrap the call in torch.no_grad(), or use lstm_seq (back-propagation through time)")
     names = ("weight_ih", "weight_hh", "bias_ih", "bias_hh")

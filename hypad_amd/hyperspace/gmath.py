@@ -30,6 +30,7 @@ import torch
 from .. import _C
 
 _K_MSG = "only curvature k = -1 is implemented (the only value HypAD uses: hyperspace/hyrnn_nets.py:20,166)"
+_ROW_SUPPORTED = "supported: k = -1, dim = -1 (the last dimension), floating operands, which are cast to fp32 (the result is fp32)"
 
 
 def _check_k(k):
@@ -37,10 +38,33 @@ def _check_k(k):
         raise NotImplementedError(_K_MSG)
 
 
+def _check_last_dim(what, x, dim):
+    """The row kernels work along the last dimension alone: any other ``dim`` is refused, not ignored."""
+    if dim != -1 and dim != x.dim() - 1:
+        raise NotImplementedError(f"{what}: dim = {dim} on an operand {tuple(x.shape)} is not implemented; {_ROW_SUPPORTED}")
+
+
 def _rows(t):
     t = t.to(torch.float32).contiguous()
     _C.require_cuda(t)
     return t, t.reshape(-1, t.shape[-1])
+
+
+def _launch(rows, entry, *args):
+    """The entry point ``entry`` over ``rows`` rows.  Without rows nothing is called: there is nothing to launch, and the data pointer
+    of an empty tensor is null, which the entry points refuse."""
+    if rows:
+        _C.check(getattr(_C.lib, entry)(*args), entry)
+
+
+def _column_sum(g):
+    """(rows, n) -> (1, n): the rows' contributions to the gradient of a one-row operand, added in a fixed order; zeros over no rows."""
+    rows, n = g.shape
+    if rows == 0:
+        return torch.zeros(1, n, device=g.device, dtype=torch.float32)
+    red = torch.empty(1, n, device=g.device, dtype=torch.float32)
+    _C.check(_C.lib.hypad_column_sum(_C.ptr(g), _C.ptr(red), rows, n, _C.stream()), "hypad_column_sum")
+    return red
 
 
 def _rows_width(t):
@@ -63,7 +87,7 @@ class _Unary(torch.autograd.Function):
     def forward(ctx, x, fwd, bwd):
         x, x2 = _rows(x)
         out = torch.empty_like(x2)
-        _C.check(getattr(_C.lib, fwd)(_C.ptr(x2), _C.ptr(out), x2.shape[0], x2.shape[1], _C.stream()), fwd)
+        _launch(x2.shape[0], fwd, _C.ptr(x2), _C.ptr(out), x2.shape[0], x2.shape[1], _C.stream())
         ctx.save_for_backward(x2)
         ctx.bwd, ctx.shape = bwd, x.shape
         return out.view(x.shape)
@@ -74,22 +98,31 @@ class _Unary(torch.autograd.Function):
         (x2,) = ctx.saved_tensors
         go2 = go.to(torch.float32).contiguous().reshape(x2.shape)
         gx = torch.empty_like(x2)
-        _C.check(getattr(_C.lib, ctx.bwd)(_C.ptr(x2), _C.ptr(go2), _C.ptr(gx), x2.shape[0], x2.shape[1], _C.stream()), ctx.bwd)
+        _launch(x2.shape[0], ctx.bwd, _C.ptr(x2), _C.ptr(go2), _C.ptr(gx), x2.shape[0], x2.shape[1], _C.stream())
         return gx.view(ctx.shape), None, None
 
 
 def expmap0(u, *, k=None, dim=-1):
+    """tanh(|u|) u / |u| along the last dimension (math_.py:1132-1136) at k = -1.  A floating operand of any dtype is cast to fp32 and the
+    result is fp32; any other ``dim`` is refused."""
     _check_k(k)
+    _check_last_dim("expmap0", u, dim)
     return _Unary.apply(u, "hypad_expmap0_fwd", "hypad_expmap0_bwd")
 
 
 def logmap0(y, *, k=None, dim=-1):
+    """artanh(|y|) y / |y| along the last dimension (math_.py:1267-1270) at k = -1.  A floating operand of any dtype is cast to fp32 and
+    the result is fp32; any other ``dim`` is refused."""
     _check_k(k)
+    _check_last_dim("logmap0", y, dim)
     return _Unary.apply(y, "hypad_logmap0_fwd", "hypad_logmap0_bwd")
 
 
 def project(x, *, k=None, dim=-1, eps=-1.0):
+    """Rows beyond the norm 1 - 4e-3 scaled back onto it (math_.py:340-352) at k = -1.  A floating operand of any dtype is cast to fp32
+    and the result is fp32 (with the fp32 eps); any other ``dim`` is refused."""
     _check_k(k)
+    _check_last_dim("project", x, dim)
     if eps >= 0:
         raise NotImplementedError("custom eps: the fused kernel uses the fp32 default 4e-3 (math_.py:343-347)")
     return _Unary.apply(x, "hypad_project_fwd", "hypad_project_bwd")
@@ -104,7 +137,7 @@ class _MobiusAdd(torch.autograd.Function):
         y, y2 = _rows(y)
         yr = y2.shape[0]
         out = torch.empty_like(x2)
-        _C.check(_C.lib.hypad_mobius_add_fwd(_C.ptr(x2), _C.ptr(y2), _C.ptr(out), x2.shape[0], x2.shape[1], yr, _C.stream()))
+        _launch(x2.shape[0], "hypad_mobius_add_fwd", _C.ptr(x2), _C.ptr(y2), _C.ptr(out), x2.shape[0], x2.shape[1], yr, _C.stream())
         ctx.save_for_backward(x2, y2)
         ctx.xs, ctx.ys = x.shape, y.shape
         return out.view(x.shape)
@@ -115,23 +148,31 @@ class _MobiusAdd(torch.autograd.Function):
         x2, y2 = ctx.saved_tensors
         go2 = go.to(torch.float32).contiguous().reshape(x2.shape)
         gx, gy = torch.empty_like(x2), torch.empty_like(x2)
-        _C.check(_C.lib.hypad_mobius_add_bwd(_C.ptr(x2), _C.ptr(y2), _C.ptr(go2), _C.ptr(gx), _C.ptr(gy), x2.shape[0],
-                                             x2.shape[1], y2.shape[0], _C.stream()))
+        _launch(x2.shape[0], "hypad_mobius_add_bwd", _C.ptr(x2), _C.ptr(y2), _C.ptr(go2), _C.ptr(gx), _C.ptr(gy), x2.shape[0], x2.shape[1],
+                y2.shape[0], _C.stream())
         if y2.shape[0] == 1 and x2.shape[0] != 1:
-            red = torch.empty(1, x2.shape[1], device=x2.device, dtype=torch.float32)
-            _C.check(_C.lib.hypad_column_sum(_C.ptr(gy), _C.ptr(red), x2.shape[0], x2.shape[1], _C.stream()))
-            gy = red
+            gy = _column_sum(gy)
         return gx.view(ctx.xs), gy.view(ctx.ys)
 
 
 def mobius_add(x, y, *, k=None, dim=-1):
+    """x (+) y along the last dimension (math_.py:536-555) at k = -1: one HIP launch forward and one backward.  The leading dimensions
+    of x and y broadcast against each other by torch's rules.  A y of a single row and fewer dimensions than x -- the bias of a layer --
+    is broadcast inside the kernel and its gradient summed there; every other broadcast operand is expanded and materialised, which
+    leaves the sum of its gradient to autograd (the expand's backward).  Floating operands of any dtype are cast to fp32 and the result
+    is fp32; any other ``dim`` is refused."""
     _check_k(k)
     if x.dim() < 1 or y.dim() < 1 or y.shape[-1] != x.shape[-1]:
         raise _C.HypadError(f"mobius_add: x {tuple(x.shape)} and y {tuple(y.shape)} differ in their last dimension")
-    if y.dim() == x.dim() and y.shape != x.shape:
-        y = y.expand_as(x)
-    if y.dim() < x.dim():
-        y = y.reshape(1, -1)
+    _check_last_dim("mobius_add", x if x.dim() >= y.dim() else y, dim)
+    if y.dim() < x.dim() and y.numel() == y.shape[-1]:
+        return _MobiusAdd.apply(x, y.reshape(1, -1))
+    if y.shape != x.shape:
+        try:
+            shape = torch.broadcast_shapes(tuple(x.shape), tuple(y.shape))
+        except RuntimeError:
+            raise _C.HypadError(f"mobius_add: x {tuple(x.shape)} and y {tuple(y.shape)} do not broadcast against each other") from None
+        x, y = x.expand(shape), y.expand(shape)
     return _MobiusAdd.apply(x, y)
 
 
@@ -141,8 +182,8 @@ class _MobiusPointwiseMul(torch.autograd.Function):
         x, x2 = _rows(x)
         w, w2 = _rows(w)
         out = torch.empty_like(x2)
-        _C.check(_C.lib.hypad_mobius_pointwise_mul_fwd(_C.ptr(w2), _C.ptr(x2), _C.ptr(out), x2.shape[0], x2.shape[1], w2.shape[0], _C.stream()),
-                 "mobius_pointwise_mul_fwd")
+        _launch(x2.shape[0], "hypad_mobius_pointwise_mul_fwd", _C.ptr(w2), _C.ptr(x2), _C.ptr(out), x2.shape[0], x2.shape[1], w2.shape[0],
+                _C.stream())
         ctx.save_for_backward(w2, x2)
         ctx.ws, ctx.xs = w.shape, x.shape
         return out.view(x.shape)
@@ -153,12 +194,10 @@ class _MobiusPointwiseMul(torch.autograd.Function):
         w2, x2 = ctx.saved_tensors
         go2 = go.to(torch.float32).contiguous().reshape(x2.shape)
         gw, gx = torch.empty_like(x2), torch.empty_like(x2)
-        _C.check(_C.lib.hypad_mobius_pointwise_mul_bwd(_C.ptr(w2), _C.ptr(x2), _C.ptr(go2), _C.ptr(gw), _C.ptr(gx), x2.shape[0], x2.shape[1],
-                                                       w2.shape[0], _C.stream()), "mobius_pointwise_mul_bwd")
+        _launch(x2.shape[0], "hypad_mobius_pointwise_mul_bwd", _C.ptr(w2), _C.ptr(x2), _C.ptr(go2), _C.ptr(gw), _C.ptr(gx), x2.shape[0],
+                x2.shape[1], w2.shape[0], _C.stream())
         if w2.shape[0] == 1 and x2.shape[0] != 1:
-            red = torch.empty(1, x2.shape[1], device=x2.device, dtype=torch.float32)
-            _C.check(_C.lib.hypad_column_sum(_C.ptr(gw), _C.ptr(red), x2.shape[0], x2.shape[1], _C.stream()))
-            gw = red
+            gw = _column_sum(gw)
         return gw.view(ctx.ws), gx.view(ctx.xs)
 
 
@@ -167,7 +206,8 @@ _PMUL_SUPPORTED = "supported: k = -1, dim = -1, fp32, w of the shape of x or one
 
 def mobius_pointwise_mul(w, x, *, k=None, dim=-1):
     """diag(w) (x) x for ball-valued rows of x (math_.py:1328-1371) at k = -1: one HIP launch forward and one backward, first-order
-    differentiable in w and x.  w has the shape of x, or is a single row broadcast over the rows of x."""
+    differentiable in w and x.  w has the shape of x, or is a single row broadcast over the rows of x.  Floating operands of any dtype
+    are cast to fp32 and the result is fp32."""
     if k is not None and abs(float(k) + 1.0) > 1e-12:
         raise NotImplementedError(f"mobius_pointwise_mul: curvature k = {float(k)} is not implemented; {_PMUL_SUPPORTED}")
     if dim != -1 and dim != x.dim() - 1:
@@ -188,8 +228,8 @@ class _MobiusScalarMul(torch.autograd.Function):
         x, x2 = _rows(x)
         r1 = _C.require_cuda(r.to(torch.float32).contiguous().reshape(-1), "r")
         out = torch.empty_like(x2)
-        _C.check(_C.lib.hypad_mobius_scalar_mul_fwd(_C.ptr(r1), _C.ptr(x2), _C.ptr(out), x2.shape[0], x2.shape[1], r1.shape[0], _C.stream()),
-                 "mobius_scalar_mul_fwd")
+        _launch(x2.shape[0], "hypad_mobius_scalar_mul_fwd", _C.ptr(r1), _C.ptr(x2), _C.ptr(out), x2.shape[0], x2.shape[1], r1.shape[0],
+                _C.stream())
         ctx.save_for_backward(r1, x2)
         ctx.rs, ctx.xs = r.shape, x.shape
         return out.view(x.shape)
@@ -202,12 +242,10 @@ class _MobiusScalarMul(torch.autograd.Function):
         go2 = go.to(torch.float32).contiguous().reshape(x2.shape)
         gr = torch.empty(rows, device=x2.device, dtype=torch.float32) if ctx.needs_input_grad[0] else None
         gx = torch.empty_like(x2) if ctx.needs_input_grad[1] else None
-        _C.check(_C.lib.hypad_mobius_scalar_mul_bwd(_C.ptr(r1), _C.ptr(x2), _C.ptr(go2), _C.ptr(gr), _C.ptr(gx), rows, x2.shape[1], r1.shape[0],
-                                                    _C.stream()), "mobius_scalar_mul_bwd")
+        _launch(rows, "hypad_mobius_scalar_mul_bwd", _C.ptr(r1), _C.ptr(x2), _C.ptr(go2), _C.ptr(gr), _C.ptr(gx), rows, x2.shape[1], r1.shape[0],
+                _C.stream())
         if gr is not None and r1.shape[0] == 1 and rows != 1:      # one r for every row: the rows' contributions, added in a fixed order
-            red = torch.empty(1, device=x2.device, dtype=torch.float32)
-            _C.check(_C.lib.hypad_column_sum(_C.ptr(gr), _C.ptr(red), rows, 1, _C.stream()))
-            gr = red
+            gr = _column_sum(gr.view(rows, 1)).view(1)
         return None if gr is None else gr.view(ctx.rs), None if gx is None else gx.view(ctx.xs)
 
 
@@ -217,7 +255,7 @@ _SMUL_SUPPORTED = "supported: k = -1, dim = -1, fp32, r of one element or of sha
 def mobius_scalar_mul(r, x, *, k=None, dim=-1):
     """r (x) x = tanh(r artanh |x|) x / |x| for ball-valued rows of x (math_.py:788-858) at k = -1: one HIP launch forward and one
     backward, first-order differentiable in r and x.  r is a tensor of one element (or a number) or holds one value per row of x,
-    shape x.shape[:-1] + (1,)."""
+    shape x.shape[:-1] + (1,).  Floating operands of any dtype are cast to fp32 and the result is fp32."""
     if k is not None and abs(float(k) + 1.0) > 1e-12:
         raise NotImplementedError(f"mobius_scalar_mul: curvature k = {float(k)} is not implemented; {_SMUL_SUPPORTED}")
     if dim != -1 and dim != x.dim() - 1:
@@ -1022,15 +1060,16 @@ def mobiusify(fn):
 def mobius_fn_apply(fn, x, *args, k=None, dim=-1, **kwargs):
     """expmap0(fn(logmap0(x)))  (math_.py:1431-1469): the two maps are the HIP kernels above (first-order gradients, as theirs);
     ``fn`` is the caller's own function of the tangent vector.  Inside mobius_linear, tanh and relu run fused in the layer's
-    kernels instead (hyrnn_nets.mobius_linear)."""
+    kernels instead (hyrnn_nets.mobius_linear).  A floating x of any dtype is cast to fp32 by logmap0: ``fn`` sees fp32, and the result
+    is fp32."""
     _check_k(k)
-    if dim != -1 and dim != x.dim() - 1:
-        raise NotImplementedError("mobius_fn_apply: only the last dimension (dim = -1) is implemented")
+    _check_last_dim("mobius_fn_apply", x, dim)
     return expmap0(fn(logmap0(x), *args, **kwargs))
 
 
 def mobius_matvec(m, x, *, k=None, dim=-1):
-    """math_.py:1308-1323: see hyrnn_nets.mobius_matvec (one HIP launch, differentiable in m and x)."""
+    """math_.py:1308-1323: see hyrnn_nets.mobius_matvec (one HIP launch, differentiable in m and x; a floating x of any dtype is cast to
+    fp32, m is fp32, the result is fp32)."""
     from .hyrnn_nets import mobius_matvec as _matvec
     return _matvec(m, x, k=-1.0 if k is None else k, dim=dim)
 
@@ -1084,7 +1123,7 @@ _D2P_SUPPORTED = ("supported: k = -1, dim = -1, fp32, x of shape (..., 1, K) aga
 def dist2plane(x, p, a, *, k=None, keepdim=False, signed=False, scaled=False, dim=-1):
     """Geodesic distance of x to the hyperplanes through p with normals a (math_.py:1599-1666) at k = -1, for the layer's calling
     pattern: x (..., 1, K) against p, a (N, K) -> (..., N), or (..., N, 1) with keepdim.  One HIP launch forward; first-order
-    differentiable in x, p and a."""
+    differentiable in x, p and a.  A floating x of any dtype is cast to fp32; p and a are fp32, and so is the result."""
     if k is not None and abs(float(k) + 1.0) > 1e-12:
         raise NotImplementedError(f"dist2plane: curvature k = {float(k)} is not implemented; {_D2P_SUPPORTED}")
     if dim != -1 and dim != x.dim() - 1:
@@ -1106,7 +1145,7 @@ class _RowDist(torch.autograd.Function):
         u, u2 = _rows(u)
         v, v2 = _rows(v)
         out = torch.empty(u2.shape[0], device=u2.device, dtype=torch.float32)
-        _C.check(_C.lib.hypad_poincare_rowdist_fwd(_C.ptr(u2), _C.ptr(v2), _C.ptr(out), u2.shape[0], u2.shape[1], _C.stream()))
+        _launch(u2.shape[0], "hypad_poincare_rowdist_fwd", _C.ptr(u2), _C.ptr(v2), _C.ptr(out), u2.shape[0], u2.shape[1], _C.stream())
         ctx.save_for_backward(u2, v2)
         ctx.us, ctx.vs = u.shape, v.shape
         return out.view(u.shape[:-1])
@@ -1117,13 +1156,14 @@ class _RowDist(torch.autograd.Function):
         u2, v2 = ctx.saved_tensors
         gd = gd.to(torch.float32).contiguous().reshape(-1)
         gu, gv = torch.empty_like(u2), torch.empty_like(v2)
-        _C.check(_C.lib.hypad_poincare_rowdist_bwd(_C.ptr(u2), _C.ptr(v2), _C.ptr(gd), _C.ptr(gu), _C.ptr(gv), u2.shape[0],
-                                                   u2.shape[1], _C.stream()))
+        _launch(u2.shape[0], "hypad_poincare_rowdist_bwd", _C.ptr(u2), _C.ptr(v2), _C.ptr(gd), _C.ptr(gu), _C.ptr(gv), u2.shape[0], u2.shape[1],
+                _C.stream())
         return gu.view(ctx.us), gv.view(ctx.vs)
 
 
 def poincare_rowdist(u, v):
-    """acosh(1 + 2|u-v|^2 / ((1-|u|^2)(1-|v|^2)) + 1e-7) per row (train.py:226-230)."""
+    """acosh(1 + 2|u-v|^2 / ((1-|u|^2)(1-|v|^2)) + 1e-7) per row (train.py:226-230).  u and v have one shape (..., D); floating operands
+    of any dtype are cast to fp32 (the fp64 window path of utils/anomaly_detection_utils.py relies on it) and the result is fp32."""
     return _RowDist.apply(u, v)
 
 
@@ -1133,8 +1173,8 @@ class _HyperLoss(torch.autograd.Function):
         _same_shape("hyperbolic_loss", u, v)
         u, u2 = _rows(u)
         v, v2 = _rows(v)
-        out = torch.empty(1, device=u2.device, dtype=torch.float32)
-        _C.check(_C.lib.hypad_hyper_loss_fwd(_C.ptr(u2), _C.ptr(v2), _C.ptr(out), u2.shape[0], u2.shape[1], int(batch), _C.stream()))
+        out = torch.empty(1, device=u2.device, dtype=torch.float32) if u2.shape[0] else torch.zeros(1, device=u2.device, dtype=torch.float32)
+        _launch(u2.shape[0], "hypad_hyper_loss_fwd", _C.ptr(u2), _C.ptr(v2), _C.ptr(out), u2.shape[0], u2.shape[1], int(batch), _C.stream())
         ctx.save_for_backward(u2, v2)
         ctx.us, ctx.vs, ctx.batch = u.shape, v.shape, int(batch)
         return out.view(())
@@ -1157,5 +1197,6 @@ class _HyperLoss(torch.autograd.Function):
 
 
 def hyperbolic_loss(u, v, batch_size):
-    """torch.div(torch.sum(dist), batch_size)  (train.py:232)."""
+    """torch.div(torch.sum(dist), batch_size)  (train.py:232); 0 over no rows.  Floating operands of any dtype are cast to fp32 and the
+    result is fp32."""
     return _HyperLoss.apply(u, v, batch_size)

@@ -169,7 +169,7 @@ def _check_k(k, what):
 
 def mobius_matvec(m, x, *, k, dim=-1):
     """M (x) x for ball-valued rows of x (reference: hyperspace/hyrnn_nets.py:38-58): one HIP launch forward, differentiable in
-    m and x (first order)."""
+    m and x (first order).  A floating x of any dtype is cast to fp32; m is fp32, and so is the result."""
     _check_k(k, "mobius_matvec")
     if dim != -1 and dim != x.dim() - 1:
         raise NotImplementedError(f"mobius_matvec: dim = {dim} is not implemented; {_SUPPORTED}")
@@ -189,6 +189,9 @@ def _nonlin_code(nonlin):
 
 
 def mobius_linear(input, weight, bias=None, hyperbolic_input=True, hyperbolic_bias=True, nonlin=None, k=-1.0):
+    """The Moebius linear layer (reference: hyperspace/hyrnn_nets.py:13-35) on input (..., in_features): one fused HIP launch forward and
+    a HIP backward in every configuration.  A floating input of any dtype is cast to fp32; weight and bias are fp32, and so is the
+    result."""
     _check_k(k, "mobius_linear")
     code = _nonlin_code(nonlin)
     if weight.dim() != 2:
@@ -200,7 +203,8 @@ def mobius_linear(input, weight, bias=None, hyperbolic_input=True, hyperbolic_bi
 
 
 def one_rnn_transform(W, h, U, x, b, k):
-    """((W (x) h) (+) (U (x) x)) (+) b (reference: hyperspace/hyrnn_nets.py:61-65), composed from the differentiable HIP ops."""
+    """((W (x) h) (+) (U (x) x)) (+) b (reference: hyperspace/hyrnn_nets.py:61-65), composed from the differentiable HIP ops.  Floating
+    h, x and b of any dtype are cast to fp32; W and U are fp32, and so is the result."""
     from . import gmath
     _check_k(k, "one_rnn_transform")
     return gmath.mobius_add(gmath.mobius_add(mobius_matvec(W, h, k=k), mobius_matvec(U, x, k=k), k=k), b, k=k)
@@ -270,7 +274,8 @@ def _gru_check(x, hx, weight_ih, weight_hh, bias, k, what):
 
 def mobius_gru_cell(input, hx, weight_ih, weight_hh, bias, k, nonlin=None):
     """One step of the Moebius GRU (reference: hyperspace/hyrnn_nets.py:68-91): input (rows, in) and hx (rows, hidden) on the ball ->
-    the next hidden state.  The sequence kernels at steps = 1: one GEMM and one launch forward, first-order differentiable."""
+    the next hidden state.  The sequence kernels at steps = 1: one GEMM and one launch forward, first-order differentiable.  Floating
+    operands of any dtype are cast to fp32 and the result is fp32."""
     code = _gru_code(nonlin)
     _gru_check(input, hx, weight_ih, weight_hh, bias, k, "mobius_gru_cell")
     if input.dim() != 2 or input.shape[0] != hx.shape[0]:
@@ -283,7 +288,7 @@ def mobius_gru_loop(input, h0, weight_ih, weight_hh, bias, k, batch_sizes=None, 
     """The Moebius GRU over a sequence (reference: hyperspace/hyrnn_nets.py:94-151): returns (outs, h_last).  input (steps, rows, in),
     or with ``batch_sizes`` the packed (sum(batch_sizes), in); a Euclidean input or h0 goes through expmap0 first.  Equal-length rows
     run as one autograd function on the sequence kernels (one launch for all steps, forward and backward); packed sequences run the
-    reference's own slicing loop over ``mobius_gru_cell``."""
+    reference's own slicing loop over ``mobius_gru_cell``.  Floating operands of any dtype are cast to fp32 and the results are fp32."""
     from . import gmath
     code = _gru_code(nonlin)
     _gru_check(input, h0, weight_ih, weight_hh, bias, k, "mobius_gru_loop")
@@ -323,6 +328,9 @@ def _expmap0_host(u):
 
 
 class MobiusLinear(nn.Linear):
+    """The reference's module around ``mobius_linear`` (hyperspace/hyrnn_nets.py:154-200).  As there, the input goes through ``.float()``:
+    a floating input of any dtype is cast to fp32 and the result is fp32."""
+
     def __init__(self, *args, hyperbolic_input=True, hyperbolic_bias=True, nonlin=None, k=-1.0, fp64_hyper=True, **kwargs):
         super().__init__(*args, **kwargs)
         if fp64_hyper:
@@ -347,7 +355,8 @@ class MobiusLinear(nn.Linear):
 class MobiusDist2Hyperplane(nn.Module):
     """The hyperbolic read-out layer (reference: hyperspace/hyrnn_nets.py:210-245): the signed geodesic distance of every ball-valued
     input row to ``out_features`` hyperplanes of the ball -- through ``point`` with normal ``tangent`` -- times ``exp(scale)``; the
-    counterpart of the logits of an nn.Linear.  One fused HIP launch forward and a HIP backward, ``scale`` inside the kernel.
+    counterpart of the logits of an nn.Linear.  One fused HIP launch forward and a HIP backward, ``scale`` inside the kernel.  As in the
+    reference, the input goes through ``.float()``: a floating input of any dtype is cast to fp32 and the result is fp32.
 
     Curvature: k = -1, the Poincare ball.  The reference's module passes ``k=self.ball.c`` = +1 to dist2plane, a call written for an
     older geoopt whose argument was ``c``; with the vendored math_.py that selects the spherical formulas, which is not what a layer

@@ -52,7 +52,8 @@ def _entries():
          [lambda: gmath.hyperbolic_loss(Z(4, 8), Z(3, 8), 4), lambda: gmath.hyperbolic_loss(Z(4, 8), Z(1, 8), 4),
           lambda: gmath.hyperbolic_loss(Z(4, 8), Z(4, 9), 4)]),
         ("mobius_add", E, lambda: gmath.mobius_add(Z(4, 8), Z(4, 8)),
-         [lambda: gmath.mobius_add(Z(4, 8), Z(4, 7)), lambda: gmath.mobius_add(Z(4, 8), Z(9)), lambda: gmath.mobius_add(Z(2, 4, 8), Z(4, 8))]),
+         # (y (4, 8) against x (2, 4, 8) broadcasts, as in the reference: tests/test_layer_call_forms_host.py; (3, 8) does not)
+         [lambda: gmath.mobius_add(Z(4, 8), Z(4, 7)), lambda: gmath.mobius_add(Z(4, 8), Z(9)), lambda: gmath.mobius_add(Z(2, 4, 8), Z(3, 8))]),
         ("mobius_add, one row", E, lambda: gmath.mobius_add(Z(4, 8), Z(8)), [lambda: gmath.mobius_add(Z(4, 8), Z(7))]),
         ("mobius_pointwise_mul", N, lambda: gmath.mobius_pointwise_mul(Z(4, 8), Z(4, 8)),
          [lambda: gmath.mobius_pointwise_mul(Z(4, 7), Z(4, 8)), lambda: gmath.mobius_pointwise_mul(Z(9), Z(4, 8)),
