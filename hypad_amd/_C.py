@@ -49,6 +49,7 @@ ML_HYPER_INPUT, ML_HYPER_BIAS = 1, 2                # HYPAD_ML_*
 NONLIN_NONE, NONLIN_TANH, NONLIN_RELU = 0, 1, 2    # HYPAD_NONLIN_*
 D2P_SIGNED, D2P_SCALED = 1, 2                       # HYPAD_D2P_*
 MID_LINCOMB, MID_POSWEIGHT, MID_COADD = 1, 2, 4     # HYPAD_MID_*
+MANIFOLD_EUCLIDEAN, MANIFOLD_BALL, MANIFOLD_SPHERE = 0, 1, 2    # HYPAD_MANIFOLD_*
 COMB = {"sum": 0, "mult": 1, "uncertainty": 2, "critic": 3, "critic_uncertainty": 4, "sum_uncertainty": 5, "rec": 6,
         "rec_uncertainty": 7, "eucl_mult": 8, "eucl_sum": 9}
 
@@ -236,6 +237,8 @@ _SIGS = {
     "hypad_profile_iteration": (c_int, [c_int, POINTER(Dims), POINTER(TrainState), POINTER(IterIO), POINTER(c_float), c_int, P]),
     "hypad_adam_step": (c_int, [P, P, P, P, c_int64, c_int, c_float, c_float, c_float, c_float, c_float, P]),
     "hypad_radam_step": (c_int, [P, P, P, P, c_int64, c_int64, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_int, P]),
+    "hypad_radam_rows_step": (c_int, [P, P, P, P, c_int64, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_int, P]),
+    "hypad_rsgd_rows_step": (c_int, [P, P, P, c_int64, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_int, c_int, P]),
     "hypad_unroll_median": (c_int, [P, P, P, c_int64, c_int, P]),
     "hypad_unroll_true": (c_int, [P, P, c_int64, c_int, P]),
     "hypad_unroll_true_f32": (c_int, [P, c_int64, P, c_int64, c_int, P]),

@@ -761,6 +761,26 @@ __device__ __forceinline__ void egrad2rgrad_bwd_d(const R& x, const R& g, const 
 #pragma unroll
   HYPAD_ROW_EACH { dx.v[e] = k * x.v[e]; dg.v[e] = s * go.v[e]; }
 }
+// The unit sphere's maps for the row-wise optimiser steps (riemann_opt.hip; geoopt.manifolds.Sphere, restated): the projection of u on the
+// tangent space at x, u - <x, u> x, which is also its egrad2rgrad and, taken at the end point, its vector transport; and the projection
+// of a row on the sphere, which after x + u is its retraction.  The floor under the norm is this library's (DIST_EPS; geoopt divides
+// unguarded): a row shorter than that stays as short instead of turning into NaN.
+template <class R>
+__device__ __forceinline__ R sphere_proju_d(const R& x, const R& u) {
+  const double xu = rowd_dot(x, u);
+  R o;
+#pragma unroll
+  HYPAD_ROW_EACH o.v[e] = u.v[e] - xu * x.v[e];
+  return o;
+}
+template <class R>
+__device__ __forceinline__ R sphere_projx_d(const R& x) {
+  const double n = fmax(sqrt(rowd_dot(x, x)), DIST_EPS);
+  R o;
+#pragma unroll
+  HYPAD_ROW_EACH o.v[e] = x.v[e] / n;
+  return o;
+}
 // The two projections between the ball (D columns) and the hyperboloid (D + 1, the time-like coordinate last).  The element at one
 // column of a row, for every lane: a masked sum.
 template <class R>

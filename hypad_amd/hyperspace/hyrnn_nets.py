@@ -362,10 +362,11 @@ class MobiusDist2Hyperplane(nn.Module):
     older geoopt whose argument was ``c``; with the vendored math_.py that selects the spherical formulas, which is not what a layer
     of the ball means.  This layer computes k = -1 and accepts no other k.
 
-    ``point`` and ``tangent`` are tagged ManifoldParameters (ball / Sphere), as in the reference.  hypad_amd.optim.RiemannianAdam does
-    not know how to update them yet and refuses them; the layer trains with Euclidean optimisers (torch.optim.SGD / Adam) meanwhile.
-    A hand-written Riemannian step of ``point`` is ``p <- gmath.expmap(p, -lr * gmath.egrad2rgrad(p, p.grad, k=-1.0), k=-1.0)``
-    (docs/history/gyro_ops.md).
+    ``point`` and ``tangent`` are tagged ManifoldParameters (ball / Sphere), as in the reference, so that a Riemannian optimiser moves
+    them on their manifolds: ``hypad_amd.optim.RiemannianAdam(layer.parameters(), manifold_rows=True)`` and
+    ``hypad_amd.optim.RiemannianSGD`` update every row of ``point`` as a point of the ball and every row of ``tangent`` as a unit
+    vector, one launch per parameter and step (docs/history/riemannian_rows.md).  Without ``manifold_rows`` RiemannianAdam refuses
+    the two, as it always did; Euclidean optimisers (torch.optim.SGD / Adam) train the layer as well, off the manifolds.
     """
 
     def __init__(self, in_features, out_features, k=-1.0, fp64_hyper=False):

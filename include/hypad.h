@@ -757,6 +757,34 @@ int hypad_adam_step(float* params, const float* grads, float* exp_avg, float* ex
 int hypad_radam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n,
                      int64_t ball_offset, int ball_dim, int step_index, float lr, float beta1, float beta2,
                      float eps, float weight_decay, int stabilize, hypad_stream_t stream);
+/* Row-wise Riemannian steps: a parameter (rows, dim) of fp32 whose every row is one point of its manifold -- the Poincare ball at
+ * k = -1 (geoopt.PoincareBall) or the unit sphere (geoopt.manifolds.Sphere) -- with its gradient and state tensors of the same shape,
+ * updated in place by ONE launch: a wave per row in fp64 registers, no atomics, no workspace, a row's bits independent of the rows around
+ * it.  Per row x with gradient g, after g <- g + weight_decay x (the maps are listed in docs/history/riemannian_rows.md):
+ *   ball:    r = g / lambda_x^2,  second-moment number lambda_x^2 <r, r>,  retr(x, u) = project(x + u) (hypad_project_fwd),
+ *            transp = hypad_parallel_transport_fwd,  stabilise: x <- project(x)
+ *   sphere:  r = g - <x, g> x,  second-moment number <r, r>,  retr(x, u) = (x + u) / max(|x + u|, 1e-15),  transp(x, y, w) = w - <y, w> y,
+ *            stabilise: x <- x / max(|x|, 1e-15), then w <- w - <x, w> x for the first moment / momentum buffer
+ * hypad_radam_rows_step -- geoopt.optim.RiemannianAdam.step for such a parameter (train.py:282-288 hands the reference's tagged
+ * parameters, hyrnn_nets.py:216-225, to it; geoopt==0.5.0 restated, oracle/radam.py); replaces the ~10 launches of the rule composed from
+ * egrad2rgrad, inner, project, parallel_transport and elementwise ops, and extends hypad_radam_step's single ball vector to rows:
+ *   m <- b1 m + (1 - b1) r;  v <- b2 v + (1 - b2) number, on every element of the row (a row of exp_avg_sq that holds one value
+ *   repeated keeps doing so, bit for bit);  y = retr(x, -lr (m / (1 - b1^t)) / (sqrt(v / (1 - b2^t)) + eps));  m <- transp(x, y, m);  x <- y.
+ * hypad_rsgd_rows_step -- geoopt.optim.RiemannianSGD.step, also for HYPAD_MANIFOLD_EUCLIDEAN rows (r = g, retr(x, u) = x + u, no
+ * transport): without momentum x <- retr(x, -lr r) and momentum_buf is NULL; with momentum b <- momentum b + (1 - dampening) r,
+ * d = r + momentum b (nesterov) or b, y = retr(x, -lr d), b <- transp(x, y, b), x <- y.  The caller creates the buffer (geoopt: a
+ * clone of the first gradient).
+ * Both stabilise when stabilize > 0 and step_index % stabilize == 0.  step_index is the 1-based step number, by value: not for graph
+ * capture.  Every argument is validated before anything is launched: HYPAD_EINVAL for rows < 0, dim <= 0, step_index < 1, an unknown
+ * manifold (hypad_radam_rows_step: also HYPAD_MANIFOLD_EUCLIDEAN), a NULL operand with rows > 0, or a momentum_buf that is not NULL
+ * exactly where momentum == 0; HYPAD_EUNSUPPORTED for dim > 256 or rows dim >= 2^31; rows == 0 launches nothing. */
+enum { HYPAD_MANIFOLD_EUCLIDEAN = 0, HYPAD_MANIFOLD_BALL = 1, HYPAD_MANIFOLD_SPHERE = 2 };
+int hypad_radam_rows_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t rows, int dim, int manifold,
+                          int step_index, float lr, float beta1, float beta2, float eps, float weight_decay, int stabilize,
+                          hypad_stream_t stream);
+int hypad_rsgd_rows_step(float* params, const float* grads, float* momentum_buf, int64_t rows, int dim, int manifold, int step_index,
+                         float lr, float momentum, float dampening, float weight_decay, int nesterov, int stabilize,
+                         hypad_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Window scoring (utils/anomaly_detection_utils.py).  fp64 where NumPy computes in fp64.
