@@ -104,6 +104,13 @@ class RecordInfo(Structure):
                 ("mask_row_stride", c_int), ("n_layers", c_int), ("in_dim", c_int)]
 
 
+class OptimTensor(Structure):                           # hypad_optim_tensor
+    _fields_ = [("param", c_void_p), ("grad", c_void_p), ("state0", c_void_p), ("state1", c_void_p), ("rows", c_int64), ("numel", c_int64),
+                ("dim", c_int), ("manifold", c_int)]
+
+
+OPTIM_GROUP_MAX = 32               # HYPAD_OPTIM_GROUP_MAX
+
 P = c_void_p
 _SIGS = {
     "hypad_abi_version": (c_int, []),
@@ -239,6 +246,9 @@ _SIGS = {
     "hypad_radam_step": (c_int, [P, P, P, P, c_int64, c_int64, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_int, P]),
     "hypad_radam_rows_step": (c_int, [P, P, P, P, c_int64, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_int, P]),
     "hypad_rsgd_rows_step": (c_int, [P, P, P, c_int64, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_int, c_int, P]),
+    "hypad_optim_step_advance": (c_int, [P, P]),
+    "hypad_optim_group_adam": (c_int, [P, c_int, P, c_int, P, c_float, c_float, c_float, c_float, c_float, c_int, P]),
+    "hypad_optim_group_sgd": (c_int, [P, c_int, P, c_int, P, c_float, c_float, c_float, c_float, c_int, c_int, P]),
     "hypad_unroll_median": (c_int, [P, P, P, c_int64, c_int, P]),
     "hypad_unroll_true": (c_int, [P, P, c_int64, c_int, P]),
     "hypad_unroll_true_f32": (c_int, [P, c_int64, P, c_int64, c_int, P]),

@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIB_DIR, "libhypad_hip.so")
 DEV_LIB = os.path.join(LIB_DIR, "libhypad_hip_dev.so")
-SOURCES = ["api_misc.hip", "ops_hyper.hip", "dist2plane.hip", "mobius_gru.hip", "midpoint.hip", "dist.hip", "attention.hip", "ops_dense.hip", "lstm_t1_lds.hip", "lstm_seq.hip", "train_iters.hip", "dw_adam.hip", "score_forward.hip", "critic_fused.hip", "scoring.hip", "intervals.hip", "host_rng.cpp", "riemann_opt.hip", "tangent.hip", "dist2plane_matmul.hip"]
+SOURCES = ["api_misc.hip", "ops_hyper.hip", "dist2plane.hip", "mobius_gru.hip", "midpoint.hip", "dist.hip", "attention.hip", "ops_dense.hip", "lstm_t1_lds.hip", "lstm_seq.hip", "train_iters.hip", "dw_adam.hip", "score_forward.hip", "critic_fused.hip", "scoring.hip", "intervals.hip", "host_rng.cpp", "riemann_opt.hip", "optim_group.hip", "tangent.hip", "dist2plane_matmul.hip"]
 DEV_SOURCES = SOURCES + ["diag.hip"]
 LLVM_BIN = os.environ.get("HYPAD_LLVM_BIN", "/opt/rocm/lib/llvm/bin")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-fvisibility=hidden", "-std=c++17", "-Wno-pass-failed", "-Wno-unused-result"]

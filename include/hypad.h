@@ -786,6 +786,41 @@ int hypad_rsgd_rows_step(float* params, const float* grads, float* momentum_buf,
                          float lr, float momentum, float dampening, float weight_decay, int nesterov, int stabilize,
                          hypad_stream_t stream);
 
+/* Grouped, capturable steps (csrc/optim_group.hip, docs/history/capturable_optim.md): ONE launch updates up to HYPAD_OPTIM_GROUP_MAX
+ * tensors of one rule, each described by a hypad_optim_tensor, and may take its step number and learning rate from device memory, so
+ * that a step captured into a graph advances with every replay.  The descriptors travel by value in the kernel's argument: the array
+ * may be freed when the call returns, and a captured kernel node owns its copy.
+ *   rows, dim   a wave per row of `dim` <= 256 elements, as above
+ *   manifold    HYPAD_MANIFOLD_BALL / _SPHERE: rows dim == numel, the rules and maps of the row-wise steps above.
+ *               HYPAD_MANIFOLD_EUCLIDEAN: a flat tensor of numel elements cut into rows of `dim` with a short last row
+ *               ((rows - 1) dim < numel <= rows dim); SGD's rule with the identity maps, and under Adam the ELEMENT-WISE rule of
+ *               torch.optim.Adam: g += wd p, m = b1 m + (1 - b1) g, v = b2 v + (1 - b2) g^2, p -= lr (m / bc1) / (sqrt(v / bc2) + eps),
+ *               in fp64 registers, rounded once.
+ *   state0/1    Adam: exp_avg, exp_avg_sq.  SGD: the momentum buffer (NULL exactly where momentum == 0), and NULL.
+ * step_dev: the 1-based step number in device memory, read by the kernel (NULL: `step_index`, by value); lr_dev likewise (NULL: `lr`).
+ * hypad_optim_step_advance adds one to a device step counter: a step is "advance, then the grouped launches" in stream order, and no
+ * kernel both reads and writes the counter.  Every argument is validated before anything is launched: HYPAD_EINVAL for n < 1,
+ * n > HYPAD_OPTIM_GROUP_MAX, a NULL list, step_index < 1 where step_dev is NULL, rows < 0, dim <= 0, an unknown manifold, a numel that
+ * disagrees with rows and dim, a NULL operand on a tensor with rows, or a momentum buffer that is not NULL exactly where
+ * momentum == 0; HYPAD_EUNSUPPORTED for dim > 256 or rows dim >= 2^31.  A tensor with rows == 0 is skipped; a call whose tensors are all
+ * empty launches nothing. */
+#define HYPAD_OPTIM_GROUP_MAX 32
+typedef struct hypad_optim_tensor {
+  float* param;
+  const float* grad;
+  float* state0;
+  float* state1;
+  int64_t rows;
+  int64_t numel;
+  int dim;
+  int manifold;
+} hypad_optim_tensor;
+int hypad_optim_step_advance(int32_t* step, hypad_stream_t stream);
+int hypad_optim_group_adam(const hypad_optim_tensor* tensors, int n, const int32_t* step_dev, int step_index, const float* lr_dev, float lr,
+                           float beta1, float beta2, float eps, float weight_decay, int stabilize, hypad_stream_t stream);
+int hypad_optim_group_sgd(const hypad_optim_tensor* tensors, int n, const int32_t* step_dev, int step_index, const float* lr_dev, float lr,
+                          float momentum, float dampening, float weight_decay, int nesterov, int stabilize, hypad_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Window scoring (utils/anomaly_detection_utils.py).  fp64 where NumPy computes in fp64.
  * ---------------------------------------------------------------------------------------------- */
