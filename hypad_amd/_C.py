@@ -192,6 +192,57 @@ _SIGS = {
     "hypad_sproj_bwd": (c_int, [P, P, P, c_int64, c_int, P]),
     "hypad_inv_sproj_fwd": (c_int, [P, P, c_int64, c_int, P]),
     "hypad_inv_sproj_bwd": (c_int, [P, P, P, c_int64, c_int, P]),
+    # the same at k = -c, plus the first-generation row functions: `double c` before the stream (hyperspace/ball.py)
+    "hypad_ball_expmap_fwd": (c_int, [P, P, P, c_int64, c_int, c_double, P]),
+    "hypad_ball_expmap_bwd": (c_int, [P, P, P, P, P, c_int64, c_int, c_double, P]),
+    "hypad_ball_logmap_fwd": (c_int, [P, P, P, c_int64, c_int, c_double, P]),
+    "hypad_ball_logmap_bwd": (c_int, [P, P, P, P, P, c_int64, c_int, c_double, P]),
+    "hypad_ball_geodesic_fwd": (c_int, [P, P, P, P, c_int64, c_int, c_int64, c_double, P]),
+    "hypad_ball_geodesic_bwd": (c_int, [P, P, P, P, P, P, P, c_int64, c_int, c_int64, c_double, P]),
+    "hypad_ball_gyration_fwd": (c_int, [P, P, P, P, c_int64, c_int, c_double, P]),
+    "hypad_ball_gyration_bwd": (c_int, [P, P, P, P, P, P, P, c_int64, c_int, c_double, P]),
+    "hypad_ball_parallel_transport_fwd": (c_int, [P, P, P, P, c_int64, c_int, c_double, P]),
+    "hypad_ball_parallel_transport_bwd": (c_int, [P, P, P, P, P, P, P, c_int64, c_int, c_double, P]),
+    "hypad_ball_parallel_transport0_fwd": (c_int, [P, P, P, c_int64, c_int, c_double, P]),
+    "hypad_ball_parallel_transport0_bwd": (c_int, [P, P, P, P, P, c_int64, c_int, c_double, P]),
+    "hypad_ball_parallel_transport0back_fwd": (c_int, [P, P, P, c_int64, c_int, c_double, P]),
+    "hypad_ball_parallel_transport0back_bwd": (c_int, [P, P, P, P, P, c_int64, c_int, c_double, P]),
+    "hypad_ball_mobius_sub_fwd": (c_int, [P, P, P, c_int64, c_int, c_double, P]),
+    "hypad_ball_mobius_sub_bwd": (c_int, [P, P, P, P, P, c_int64, c_int, c_double, P]),
+    "hypad_ball_mobius_coadd_fwd": (c_int, [P, P, P, c_int64, c_int, c_double, P]),
+    "hypad_ball_mobius_coadd_bwd": (c_int, [P, P, P, P, P, c_int64, c_int, c_double, P]),
+    "hypad_ball_mobius_cosub_fwd": (c_int, [P, P, P, c_int64, c_int, c_double, P]),
+    "hypad_ball_mobius_cosub_bwd": (c_int, [P, P, P, P, P, c_int64, c_int, c_double, P]),
+    "hypad_ball_geodesic_unit_fwd": (c_int, [P, P, P, P, c_int64, c_int, c_int64, c_double, P]),
+    "hypad_ball_geodesic_unit_bwd": (c_int, [P, P, P, P, P, P, P, c_int64, c_int, c_int64, c_double, P]),
+    "hypad_ball_lambda_x_fwd": (c_int, [P, P, c_int64, c_int, c_double, P]),
+    "hypad_ball_lambda_x_bwd": (c_int, [P, P, P, c_int64, c_int, c_double, P]),
+    "hypad_ball_inner_fwd": (c_int, [P, P, P, P, c_int64, c_int, c_double, P]),
+    "hypad_ball_inner_bwd": (c_int, [P, P, P, P, P, P, P, c_int64, c_int, c_double, P]),
+    "hypad_ball_norm_fwd": (c_int, [P, P, P, c_int64, c_int, c_double, P]),
+    "hypad_ball_norm_bwd": (c_int, [P, P, P, P, P, c_int64, c_int, c_double, P]),
+    "hypad_ball_egrad2rgrad_fwd": (c_int, [P, P, P, c_int64, c_int, c_double, P]),
+    "hypad_ball_egrad2rgrad_bwd": (c_int, [P, P, P, P, P, c_int64, c_int, c_double, P]),
+    "hypad_ball_sproj_fwd": (c_int, [P, P, c_int64, c_int, c_double, P]),
+    "hypad_ball_sproj_bwd": (c_int, [P, P, P, c_int64, c_int, c_double, P]),
+    "hypad_ball_inv_sproj_fwd": (c_int, [P, P, c_int64, c_int, c_double, P]),
+    "hypad_ball_inv_sproj_bwd": (c_int, [P, P, P, c_int64, c_int, c_double, P]),
+    "hypad_ball_project_fwd": (c_int, [P, P, c_int64, c_int, c_double, P]),
+    "hypad_ball_project_bwd": (c_int, [P, P, P, c_int64, c_int, c_double, P]),
+    "hypad_ball_expmap0_fwd": (c_int, [P, P, c_int64, c_int, c_double, P]),
+    "hypad_ball_expmap0_bwd": (c_int, [P, P, P, c_int64, c_int, c_double, P]),
+    "hypad_ball_logmap0_fwd": (c_int, [P, P, c_int64, c_int, c_double, P]),
+    "hypad_ball_logmap0_bwd": (c_int, [P, P, P, c_int64, c_int, c_double, P]),
+    "hypad_ball_mobius_add_fwd": (c_int, [P, P, P, c_int64, c_int, c_double, P]),
+    "hypad_ball_mobius_add_bwd": (c_int, [P, P, P, P, P, c_int64, c_int, c_double, P]),
+    "hypad_ball_mobius_pointwise_mul_fwd": (c_int, [P, P, P, c_int64, c_int, c_double, P]),
+    "hypad_ball_mobius_pointwise_mul_bwd": (c_int, [P, P, P, P, P, c_int64, c_int, c_double, P]),
+    "hypad_ball_mobius_scalar_mul_fwd": (c_int, [P, P, P, c_int64, c_int, c_int64, c_double, P]),
+    "hypad_ball_mobius_scalar_mul_bwd": (c_int, [P, P, P, P, P, c_int64, c_int, c_int64, c_double, P]),
+    "hypad_ball_dist_fwd": (c_int, [P, P, P, c_int64, c_int, c_double, P]),
+    "hypad_ball_dist_bwd": (c_int, [P, P, P, P, P, c_int64, c_int, c_double, P]),
+    "hypad_ball_dist0_fwd": (c_int, [P, P, c_int64, c_int, c_double, P]),
+    "hypad_ball_dist0_bwd": (c_int, [P, P, P, c_int64, c_int, c_double, P]),
     "hypad_hyp_attention_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int, c_int]),
     "hypad_hyp_attention_fwd": (c_int, [P, P, P, P, c_int64, c_double, P, P, P, c_int64, c_int64, c_int64, c_int, c_int, P]),
     "hypad_hyp_attention_bwd": (c_int, [P, P, P, P, c_int64, c_double, P, P, P, P, P, P, c_void_p, c_size_t, c_int64, c_int64, c_int64, c_int, c_int, P]),

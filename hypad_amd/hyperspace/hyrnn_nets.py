@@ -19,11 +19,203 @@ from .. import _C
 
 
 class PoincareBall:
-    """Marker for ball-valued parameters (the reference's geoopt.PoincareBall(c=1))."""
+    """The Poincare ball of curvature k = -c (the reference's geoopt.PoincareBall(c)): the tag of ball-valued parameters, and the
+    object through which the 25 row-wise functions of math_.py and ``antipode`` are reached with k = -c bound -- ``ball.expmap(x, u)``,
+    ``ball.dist(x, y)``, ``ball.transp(x, y, v)`` -- under the names of math_.py and geoopt's aliases ``projx``, ``transp``, ``transp0``
+    and ``transp0back``.
+
+    Each method takes the operands of the ``gmath`` function of its name without ``k`` and applies that function's operand rules and
+    refusals before any device call.  At c == 1 it calls that function, so its bits are ``gmath``'s; at any other finite c > 0 it runs
+    the ``hypad_ball_*`` kernels, one HIP launch forward and one backward, a wave per row in fp64 registers (hyperspace/ball.py,
+    docs/history/curvature.md).  c <= 0, a c that is not finite and a c that requires grad raise NotImplementedError.  c is read on
+    the host from the tensor stored here: nothing waits for the device, the launches go to the current stream and can be captured
+    under ``torch.cuda.graph`` (a replay uses the c it was captured with).
+
+    The methods are the functions of math_.py and nothing more: unlike geoopt's manifold class none of them projects its result back
+    into the ball implicitly (geoopt's ``expmap(..., project=True)``, ``mobius_add(..., project=True)``); call ``project`` where it is
+    wanted.  The layers, the matmul forms (dist_matmul, dist2plane, weighted_midpoint, hyperbolic_attention) and the optimisers stay
+    at c = 1."""
 
     def __init__(self, c=1.0):
         self.c = torch.tensor(float(c))
         self.k = -self.c
+
+    def _c(self, what):
+        from . import ball
+        return ball.curvature(self, what)
+
+    # ---- one operand
+    def project(self, x, *, dim=-1, eps=-1.0):
+        """Rows beyond the norm (1 - 4e-3) / sqrt(c) scaled back onto it (math_.py:340-352)."""
+        from . import ball, gmath
+        c = self._c("project")
+        if eps >= 0:
+            raise NotImplementedError("custom eps: the fused kernel uses the fp32 default 4e-3 (math_.py:343-347)")
+        ball.cast_rows("project", dim, x=x)
+        return gmath.project(x, k=-1.0, dim=dim) if c == 1.0 else ball.unary("project", c, x, dim)
+
+    def expmap0(self, u, *, dim=-1):
+        """tanh(sqrt(c) |u|) u / (sqrt(c) |u|) (math_.py:1105-1136)."""
+        from . import ball, gmath
+        c = self._c("expmap0")
+        ball.cast_rows("expmap0", dim, u=u)
+        return gmath.expmap0(u, k=-1.0, dim=dim) if c == 1.0 else ball.unary("expmap0", c, u, dim)
+
+    def logmap0(self, y, *, dim=-1):
+        """artanh(sqrt(c) |y|) y / (sqrt(c) |y|) (math_.py:1233-1270)."""
+        from . import ball, gmath
+        c = self._c("logmap0")
+        ball.cast_rows("logmap0", dim, y=y)
+        return gmath.logmap0(y, k=-1.0, dim=dim) if c == 1.0 else ball.unary("logmap0", c, y, dim)
+
+    def dist0(self, x, *, keepdim=False, dim=-1):
+        """The geodesic distance from the origin, 2 artanh(sqrt(c) |x|) / sqrt(c) (math_.py:950-975)."""
+        from . import ball, gmath
+        c = self._c("dist0")
+        return gmath.dist0(x, k=-1.0, keepdim=keepdim, dim=dim) if c == 1.0 else ball.dist0(c, x, keepdim, dim)
+
+    def lambda_x(self, x, *, keepdim=False, dim=-1):
+        """The conformal factor 2 / (1 - c |x|^2) (math_.py:355-383)."""
+        from . import ball, gmath
+        c = self._c("lambda_x")
+        return gmath.lambda_x(x, k=-1.0, keepdim=keepdim, dim=dim) if c == 1.0 else ball.per_row("lambda_x", c, keepdim, dim, x=x)
+
+    def sproj(self, x, *, dim=-1):
+        """Hyperboloid points (..., D + 1) onto the ball: x[..., :D] / (1 + sqrt(c) x[..., D]) (math_.py:1848-1874)."""
+        from . import ball, gmath
+        c = self._c("sproj")
+        return gmath.sproj(x, k=-1.0, dim=dim) if c == 1.0 else ball.projection("sproj", c, x, dim, -1)
+
+    def inv_sproj(self, x, *, dim=-1):
+        """Ball points (..., D) onto the hyperboloid: cat(lambda_x x, (lambda_x - 1) / sqrt(c)) (math_.py:1877-1905)."""
+        from . import ball, gmath
+        c = self._c("inv_sproj")
+        return gmath.inv_sproj(x, k=-1.0, dim=dim) if c == 1.0 else ball.projection("inv_sproj", c, x, dim, 1)
+
+    def antipode(self, x, *, dim=-1):
+        """-x, the antipode at every k < 0 (math_.py:1908-1950).  No kernel."""
+        self._c("antipode")
+        return -x
+
+    # ---- two ball points, or a point and a tangent vector
+    def mobius_add(self, x, y, *, dim=-1):
+        """x (+) y at curvature -c (math_.py:536-555); x and y broadcast against each other."""
+        from . import ball, gmath
+        c = self._c("mobius_add")
+        ball.cast_rows("mobius_add", dim, x=x, y=y)
+        return gmath.mobius_add(x, y, k=-1.0, dim=dim) if c == 1.0 else ball.mobius_add(c, x, y, dim)
+
+    def mobius_sub(self, x, y, *, dim=-1):
+        """x (+) (-y) (math_.py:558-589)."""
+        from . import ball, gmath
+        c = self._c("mobius_sub")
+        return gmath.mobius_sub(x, y, k=-1.0, dim=dim) if c == 1.0 else ball.rows("mobius_sub", c, dim, x=x, y=y)
+
+    def mobius_coadd(self, x, y, *, dim=-1):
+        """The Moebius coaddition (math_.py:678-744)."""
+        from . import ball, gmath
+        c = self._c("mobius_coadd")
+        return gmath.mobius_coadd(x, y, k=-1.0, dim=dim) if c == 1.0 else ball.rows("mobius_coadd", c, dim, x=x, y=y)
+
+    def mobius_cosub(self, x, y, *, dim=-1):
+        """mobius_coadd(x, -y) (math_.py:747-779)."""
+        from . import ball, gmath
+        c = self._c("mobius_cosub")
+        return gmath.mobius_cosub(x, y, k=-1.0, dim=dim) if c == 1.0 else ball.rows("mobius_cosub", c, dim, x=x, y=y)
+
+    def dist(self, x, y, *, keepdim=False, dim=-1):
+        """The geodesic distance 2 artanh(sqrt(c) |(-x) (+) y|) / sqrt(c) (math_.py:861-902); rows that are equal element by element are
+        at distance 0 with gradient 0."""
+        from . import ball, gmath
+        c = self._c("dist")
+        return gmath.dist(x, y, k=-1.0, keepdim=keepdim, dim=dim) if c == 1.0 else ball.dist(c, x, y, keepdim, dim)
+
+    def expmap(self, x, u, *, dim=-1):
+        """The exponential map at x (math_.py:1052-1102)."""
+        from . import ball, gmath
+        c = self._c("expmap")
+        return gmath.expmap(x, u, k=-1.0, dim=dim) if c == 1.0 else ball.rows("expmap", c, dim, x=x, u=u)
+
+    def logmap(self, x, y, *, dim=-1):
+        """The logarithmic map at x (math_.py:1188-1230), with the library's log1p artanh: at coincident points it follows the analytic
+        limit, as ``gmath.logmap``."""
+        from . import ball, gmath
+        c = self._c("logmap")
+        return gmath.logmap(x, y, k=-1.0, dim=dim) if c == 1.0 else ball.rows("logmap", c, dim, x=x, y=y)
+
+    def parallel_transport0(self, y, v, *, dim=-1):
+        """The parallel transport of v from the origin to y, v (1 - c |y|^2) (math_.py:1749-1779)."""
+        from . import ball, gmath
+        c = self._c("parallel_transport0")
+        return gmath.parallel_transport0(y, v, k=-1.0, dim=dim) if c == 1.0 else ball.rows("parallel_transport0", c, dim, y=y, v=v)
+
+    def parallel_transport0back(self, x, v, *, dim=-1):
+        """The parallel transport of v from x to the origin, v / (1 - c |x|^2) (math_.py:1782-1813)."""
+        from . import ball, gmath
+        c = self._c("parallel_transport0back")
+        return gmath.parallel_transport0back(x, v, k=-1.0, dim=dim) if c == 1.0 else ball.rows("parallel_transport0back", c, dim, x=x, v=v)
+
+    def norm(self, x, u, *, keepdim=False, dim=-1):
+        """The Riemannian norm lambda_x |u| (math_.py:433-472)."""
+        from . import ball, gmath
+        c = self._c("norm")
+        return gmath.norm(x, u, k=-1.0, keepdim=keepdim, dim=dim) if c == 1.0 else ball.per_row("norm", c, keepdim, dim, x=x, u=u)
+
+    def egrad2rgrad(self, x, grad, *, dim=-1):
+        """The Riemannian gradient grad / lambda_x^2 (math_.py:1816-1845)."""
+        from . import ball, gmath
+        c = self._c("egrad2rgrad")
+        return gmath.egrad2rgrad(x, grad, k=-1.0, dim=dim) if c == 1.0 else ball.rows("egrad2rgrad", c, dim, x=x, grad=grad)
+
+    # ---- a scalar or a weight row with a point
+    def mobius_scalar_mul(self, r, x, *, dim=-1):
+        """r (x) x = tanh(r artanh(sqrt(c) |x|)) x / (sqrt(c) |x|) (math_.py:788-858); r a number, one element, or one value per row."""
+        from . import ball, gmath
+        c = self._c("mobius_scalar_mul")
+        return gmath.mobius_scalar_mul(r, x, k=-1.0, dim=dim) if c == 1.0 else ball.mobius_scalar_mul(c, r, x, dim)
+
+    def mobius_pointwise_mul(self, w, x, *, dim=-1):
+        """diag(w) (x) x (math_.py:1328-1371); w of the shape of x or one row of it."""
+        from . import ball, gmath
+        c = self._c("mobius_pointwise_mul")
+        return gmath.mobius_pointwise_mul(w, x, k=-1.0, dim=dim) if c == 1.0 else ball.mobius_pointwise_mul(c, w, x, dim)
+
+    # ---- three operands
+    def geodesic(self, t, x, y, *, dim=-1):
+        """The point at time t of the geodesic from x to y (math_.py:978-1049); t a number, one element, or one value per row."""
+        from . import ball, gmath
+        c = self._c("geodesic")
+        return gmath.geodesic(t, x, y, k=-1.0, dim=dim) if c == 1.0 else ball.timed("geodesic", c, t, dim, x=x, y=y)
+
+    def geodesic_unit(self, t, x, u, *, dim=-1):
+        """The point at geodesic distance t from x in the direction u (math_.py:1139-1185)."""
+        from . import ball, gmath
+        c = self._c("geodesic_unit")
+        return gmath.geodesic_unit(t, x, u, k=-1.0, dim=dim) if c == 1.0 else ball.timed("geodesic_unit", c, t, dim, x=x, u=u)
+
+    def gyration(self, a, b, u, *, dim=-1):
+        """gyr[a, b] u (math_.py:592-675)."""
+        from . import ball, gmath
+        c = self._c("gyration")
+        return gmath.gyration(a, b, u, k=-1.0, dim=dim) if c == 1.0 else ball.rows("gyration", c, dim, a=a, b=b, u=u)
+
+    def parallel_transport(self, x, y, v, *, dim=-1):
+        """The parallel transport of v from x to y along their geodesic (math_.py:1669-1746)."""
+        from . import ball, gmath
+        c = self._c("parallel_transport")
+        return gmath.parallel_transport(x, y, v, k=-1.0, dim=dim) if c == 1.0 else ball.rows("parallel_transport", c, dim, x=x, y=y, v=v)
+
+    def inner(self, x, u, v, *, keepdim=False, dim=-1):
+        """The Riemannian inner product lambda_x^2 <u, v>, one value per row as ``gmath.inner`` (math_.py:386-430)."""
+        from . import ball, gmath
+        c = self._c("inner")
+        return gmath.inner(x, u, v, k=-1.0, keepdim=keepdim, dim=dim) if c == 1.0 else ball.per_row("inner", c, keepdim, dim, x=x, u=u, v=v)
+
+    # geoopt's names
+    projx = project
+    transp = parallel_transport
+    transp0 = parallel_transport0
+    transp0back = parallel_transport0back
 
 
 class Sphere:

@@ -328,6 +328,107 @@ int hypad_sproj_fwd(const float* h, float* out, int64_t rows, int dim, hypad_str
 int hypad_sproj_bwd(const float* h, const float* grad_out, float* grad_h, int64_t rows, int dim, hypad_stream_t stream);
 int hypad_inv_sproj_fwd(const float* x, float* out, int64_t rows, int dim, hypad_stream_t stream);
 int hypad_inv_sproj_bwd(const float* x, const float* grad_out, float* grad_x, int64_t rows, int dim, hypad_stream_t stream);
+/* The 25 row-wise functions at any negative curvature k = -c, c finite and positive, on rows (rows, dim) of fp32 -- what
+ * hyrnn_nets.PoincareBall(c) calls for c != 1 (docs/history/curvature.md).  Each hypad_ball_<name>_fwd / _bwd has the argument list of
+ * hypad_<name>_fwd / _bwd plus `double c` before the stream, and computes math_.py's function of that name with k = -c:
+ *   project :340-352, lambda_x :355-383, inner :386-430, norm :433-472, mobius_add :536-555, mobius_sub :558-589, gyration :592-675,
+ *   mobius_coadd :678-744, mobius_cosub :747-779, mobius_scalar_mul :788-858, dist :861-902, dist0 :950-975, geodesic :978-1049,
+ *   expmap :1052-1102, expmap0 :1105-1136, geodesic_unit :1139-1185, logmap :1188-1230, logmap0 :1233-1270, mobius_pointwise_mul
+ *   :1328-1371, parallel_transport :1669-1746, parallel_transport0 :1749-1779, parallel_transport0back :1782-1813, egrad2rgrad
+ *   :1816-1845, sproj :1848-1874, inv_sproj :1877-1905.
+ * With s = sqrt(c), x -> s x takes the ball of radius 1 / s onto the unit ball and every one of these functions at -c onto itself at
+ * -1, clamps included (artanh at 1 - 1e-7, tanh at 15, max(1 + k |x|^2, 1e-15), project's radius (1 - 4e-3) / s):
+ *   f_c(a_0, a_1, ...) = s^eo f_1(s^e0 a_0, s^e1 a_1, ...)
+ * with exponents (e0, e1, ... -> eo):
+ *   project, expmap0, logmap0, dist0, sproj, inv_sproj                                  1 -> -1
+ *   mobius_add, mobius_sub, mobius_coadd, mobius_cosub, dist, logmap, expmap            1, 1 -> -1
+ *   mobius_scalar_mul (r, x), mobius_pointwise_mul (w, x)                               0, 1 -> -1
+ *   geodesic (t, x, y)                                                                  0, 1, 1 -> -1
+ *   geodesic_unit (t, x, u)                                                             1, 1, 0 -> -1
+ *   gyration (a, b, u), parallel_transport (x, y, v)                                    1, 1, 0 -> 0
+ *   parallel_transport0 (y, v), parallel_transport0back (x, v), norm (x, u), egrad2rgrad (x, grad)   1, 0 -> 0
+ *   lambda_x (x)  1 -> 0;   inner (x, u, v)  1, 0, 0 -> 0
+ * and f_1 the k = -1 function documented above (sproj and inv_sproj with inv_r = sqrt(c) for the reference's sqrt(|k| + 1e-15)).  The
+ * backward is the chain rule through the factors: grad_out times s^eo going in, each operand's gradient times its s^e coming out.
+ * The kernels are those of the k = -1 entry points -- a wave per row in fp64 registers, operands scaled after the load and the result
+ * before the store, the backward recomputed from the operands, no atomics, no workspace --, so c = 1.0 returns the bits of
+ * hypad_<name>_*.  project, expmap0, logmap0, mobius_add, mobius_pointwise_mul, mobius_scalar_mul, dist and dist0, whose k = -1 entry
+ * points are older kernels, run in this launch form too: within rounding of those at c = 1.0, and without their one-row broadcast
+ * (every row operand is (rows, dim); r of mobius_scalar_mul holds r_rows values, 1 or one per row, as t_count).
+ * Validation and return codes as hypad_<name>_*'s, after HYPAD_EINVAL for a c that is not finite and positive.  bwd: every gradient may
+ * be NULL and the others keep their bits. */
+int hypad_ball_expmap_fwd(const float* x, const float* u, float* out, int64_t rows, int dim, double c, hypad_stream_t stream);
+int hypad_ball_expmap_bwd(const float* x, const float* u, const float* grad_out, float* grad_x, float* grad_u, int64_t rows, int dim, double c,
+                          hypad_stream_t stream);
+int hypad_ball_logmap_fwd(const float* x, const float* y, float* out, int64_t rows, int dim, double c, hypad_stream_t stream);
+int hypad_ball_logmap_bwd(const float* x, const float* y, const float* grad_out, float* grad_x, float* grad_y, int64_t rows, int dim, double c,
+                          hypad_stream_t stream);
+int hypad_ball_geodesic_fwd(const float* t, const float* x, const float* y, float* out, int64_t rows, int dim, int64_t t_count, double c,
+                            hypad_stream_t stream);
+int hypad_ball_geodesic_bwd(const float* t, const float* x, const float* y, const float* grad_out, float* grad_t, float* grad_x, float* grad_y,
+                            int64_t rows, int dim, int64_t t_count, double c, hypad_stream_t stream);
+int hypad_ball_gyration_fwd(const float* a, const float* b, const float* u, float* out, int64_t rows, int dim, double c, hypad_stream_t stream);
+int hypad_ball_gyration_bwd(const float* a, const float* b, const float* u, const float* grad_out, float* grad_a, float* grad_b, float* grad_u,
+                            int64_t rows, int dim, double c, hypad_stream_t stream);
+int hypad_ball_parallel_transport_fwd(const float* x, const float* y, const float* v, float* out, int64_t rows, int dim, double c,
+                                      hypad_stream_t stream);
+int hypad_ball_parallel_transport_bwd(const float* x, const float* y, const float* v, const float* grad_out, float* grad_x, float* grad_y,
+                                      float* grad_v, int64_t rows, int dim, double c, hypad_stream_t stream);
+int hypad_ball_parallel_transport0_fwd(const float* y, const float* v, float* out, int64_t rows, int dim, double c, hypad_stream_t stream);
+int hypad_ball_parallel_transport0_bwd(const float* y, const float* v, const float* grad_out, float* grad_y, float* grad_v, int64_t rows, int dim,
+                                       double c, hypad_stream_t stream);
+int hypad_ball_parallel_transport0back_fwd(const float* x, const float* v, float* out, int64_t rows, int dim, double c, hypad_stream_t stream);
+int hypad_ball_parallel_transport0back_bwd(const float* x, const float* v, const float* grad_out, float* grad_x, float* grad_v, int64_t rows,
+                                           int dim, double c, hypad_stream_t stream);
+int hypad_ball_mobius_sub_fwd(const float* x, const float* y, float* out, int64_t rows, int dim, double c, hypad_stream_t stream);
+int hypad_ball_mobius_sub_bwd(const float* x, const float* y, const float* grad_out, float* grad_x, float* grad_y, int64_t rows, int dim, double c,
+                              hypad_stream_t stream);
+int hypad_ball_mobius_coadd_fwd(const float* x, const float* y, float* out, int64_t rows, int dim, double c, hypad_stream_t stream);
+int hypad_ball_mobius_coadd_bwd(const float* x, const float* y, const float* grad_out, float* grad_x, float* grad_y, int64_t rows, int dim, double c,
+                                hypad_stream_t stream);
+int hypad_ball_mobius_cosub_fwd(const float* x, const float* y, float* out, int64_t rows, int dim, double c, hypad_stream_t stream);
+int hypad_ball_mobius_cosub_bwd(const float* x, const float* y, const float* grad_out, float* grad_x, float* grad_y, int64_t rows, int dim, double c,
+                                hypad_stream_t stream);
+int hypad_ball_geodesic_unit_fwd(const float* t, const float* x, const float* u, float* out, int64_t rows, int dim, int64_t t_count, double c,
+                                 hypad_stream_t stream);
+int hypad_ball_geodesic_unit_bwd(const float* t, const float* x, const float* u, const float* grad_out, float* grad_t, float* grad_x, float* grad_u,
+                                 int64_t rows, int dim, int64_t t_count, double c, hypad_stream_t stream);
+int hypad_ball_lambda_x_fwd(const float* x, float* out, int64_t rows, int dim, double c, hypad_stream_t stream);
+int hypad_ball_lambda_x_bwd(const float* x, const float* grad_out, float* grad_x, int64_t rows, int dim, double c, hypad_stream_t stream);
+int hypad_ball_inner_fwd(const float* x, const float* u, const float* v, float* out, int64_t rows, int dim, double c, hypad_stream_t stream);
+int hypad_ball_inner_bwd(const float* x, const float* u, const float* v, const float* grad_out, float* grad_x, float* grad_u, float* grad_v,
+                         int64_t rows, int dim, double c, hypad_stream_t stream);
+int hypad_ball_norm_fwd(const float* x, const float* u, float* out, int64_t rows, int dim, double c, hypad_stream_t stream);
+int hypad_ball_norm_bwd(const float* x, const float* u, const float* grad_out, float* grad_x, float* grad_u, int64_t rows, int dim, double c,
+                        hypad_stream_t stream);
+int hypad_ball_egrad2rgrad_fwd(const float* x, const float* grad, float* out, int64_t rows, int dim, double c, hypad_stream_t stream);
+int hypad_ball_egrad2rgrad_bwd(const float* x, const float* grad, const float* grad_out, float* grad_x, float* grad_grad, int64_t rows, int dim,
+                               double c, hypad_stream_t stream);
+int hypad_ball_sproj_fwd(const float* h, float* out, int64_t rows, int dim, double c, hypad_stream_t stream);
+int hypad_ball_sproj_bwd(const float* h, const float* grad_out, float* grad_h, int64_t rows, int dim, double c, hypad_stream_t stream);
+int hypad_ball_inv_sproj_fwd(const float* x, float* out, int64_t rows, int dim, double c, hypad_stream_t stream);
+int hypad_ball_inv_sproj_bwd(const float* x, const float* grad_out, float* grad_x, int64_t rows, int dim, double c, hypad_stream_t stream);
+int hypad_ball_project_fwd(const float* x, float* out, int64_t rows, int dim, double c, hypad_stream_t stream);
+int hypad_ball_project_bwd(const float* x, const float* grad_out, float* grad_x, int64_t rows, int dim, double c, hypad_stream_t stream);
+int hypad_ball_expmap0_fwd(const float* u, float* out, int64_t rows, int dim, double c, hypad_stream_t stream);
+int hypad_ball_expmap0_bwd(const float* u, const float* grad_out, float* grad_u, int64_t rows, int dim, double c, hypad_stream_t stream);
+int hypad_ball_logmap0_fwd(const float* y, float* out, int64_t rows, int dim, double c, hypad_stream_t stream);
+int hypad_ball_logmap0_bwd(const float* y, const float* grad_out, float* grad_y, int64_t rows, int dim, double c, hypad_stream_t stream);
+int hypad_ball_mobius_add_fwd(const float* x, const float* y, float* out, int64_t rows, int dim, double c, hypad_stream_t stream);
+int hypad_ball_mobius_add_bwd(const float* x, const float* y, const float* grad_out, float* grad_x, float* grad_y, int64_t rows, int dim, double c,
+                              hypad_stream_t stream);
+int hypad_ball_mobius_pointwise_mul_fwd(const float* w, const float* x, float* out, int64_t rows, int dim, double c, hypad_stream_t stream);
+int hypad_ball_mobius_pointwise_mul_bwd(const float* w, const float* x, const float* grad_out, float* grad_w, float* grad_x, int64_t rows, int dim,
+                                        double c, hypad_stream_t stream);
+int hypad_ball_mobius_scalar_mul_fwd(const float* r, const float* x, float* out, int64_t rows, int dim, int64_t r_rows, double c,
+                                     hypad_stream_t stream);
+int hypad_ball_mobius_scalar_mul_bwd(const float* r, const float* x, const float* grad_out, float* grad_r, float* grad_x, int64_t rows, int dim,
+                                     int64_t r_rows, double c, hypad_stream_t stream);
+int hypad_ball_dist_fwd(const float* x, const float* y, float* out, int64_t rows, int dim, double c, hypad_stream_t stream);
+int hypad_ball_dist_bwd(const float* x, const float* y, const float* grad_out, float* grad_x, float* grad_y, int64_t rows, int dim, double c,
+                        hypad_stream_t stream);
+int hypad_ball_dist0_fwd(const float* x, float* out, int64_t rows, int dim, double c, hypad_stream_t stream);
+int hypad_ball_dist0_bwd(const float* x, const float* grad_out, float* grad_x, int64_t rows, int dim, double c, hypad_stream_t stream);
 /* gmath.hyperbolic_attention: the composition of dist_matmul (math_.py:905-947), a softmax over the keys and weighted_midpoint_bmm
  * without lincomb (math_.py:2090-2122) at k = -1, with no N x M tensor in memory.  q (batch, N, D), keys (batch, M, D), values
  * (batch, M, E) on the ball, out and grad_out (batch, N, E); bias NULL or fp32 (N, M) per batch element at bias_batch_stride elements
