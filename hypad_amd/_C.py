@@ -246,6 +246,15 @@ _SIGS = {
     "hypad_hyp_attention_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int, c_int]),
     "hypad_hyp_attention_fwd": (c_int, [P, P, P, P, c_int64, c_double, P, P, P, c_int64, c_int64, c_int64, c_int, c_int, P]),
     "hypad_hyp_attention_bwd": (c_int, [P, P, P, P, c_int64, c_double, P, P, P, P, P, P, c_void_p, c_size_t, c_int64, c_int64, c_int64, c_int, c_int, P]),
+    "hypad_ball_dist_matmul_fwd": (c_int, [P, P, P, c_int64, c_int64, c_int64, c_int, c_double, P]),
+    "hypad_ball_dist_matmul_bwd": (c_int, [P, P, P, P, P, c_int64, c_int64, c_int64, c_int, c_double, P]),
+    "hypad_ball_weighted_midpoint_bmm_fwd": (c_int, [P, P, P, P, c_int64, c_int64, c_int64, c_int, c_int, c_double, P]),
+    "hypad_ball_weighted_midpoint_bmm_bwd": (c_int, [P, P, P, P, P, P, c_void_p, c_size_t, c_int64, c_int64, c_int64, c_int, c_int, c_double, P]),
+    "hypad_ball_weighted_midpoint_fwd": (c_int, [P, P, c_int64, P, P, c_void_p, c_size_t, c_int64, c_int64, c_int, c_int, c_double, P]),
+    "hypad_ball_weighted_midpoint_bwd": (c_int, [P, P, c_int64, P, P, P, P, c_void_p, c_size_t, c_int64, c_int64, c_int, c_int, c_double, P]),
+    "hypad_ball_hyp_attention_fwd": (c_int, [P, P, P, P, c_int64, c_double, P, P, P, c_int64, c_int64, c_int64, c_int, c_int, c_double, P]),
+    "hypad_ball_hyp_attention_bwd": (c_int, [P, P, P, P, c_int64, c_double, P, P, P, P, P, P, c_void_p, c_size_t, c_int64, c_int64, c_int64, c_int, c_int,
+                                             c_double, P]),
     "hypad_mobius_gru_workspace_bytes": (c_size_t, [c_int, c_int64, c_int, c_int]),
     "hypad_mobius_gru_fwd": (c_int, [P] * 7 + [c_void_p, c_size_t, c_int, c_int64, c_int, c_int, c_int, P]),
     "hypad_mobius_gru_bwd": (c_int, [P] * 14 + [c_void_p, c_size_t, c_int, c_int64, c_int, c_int, c_int, P]),

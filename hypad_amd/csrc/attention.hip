@@ -121,10 +121,13 @@ __device__ __forceinline__ void stage_bias(float* __restrict__ ps, const float* 
   }
 }
 
-template <int NT>
+// CV... here and below: the launch's curvature -- nothing at k = -1, one Curv at k = -c (rowops.h): d_c in the scores, gamma_j = 2 / max(1 -
+// c |v_j|^2, 1e-15) with d gamma / d v = c gamma^2 v, the tail of the midpoint at c, dL/dxy = -2 (a + b) and dL/d|q|^2 = a + b (c |k|^2).
+template <int NT, class... CV>
 __global__ __launch_bounds__(THREADS) void attn_fwd_kernel(const float* __restrict__ Q, const float* __restrict__ K, const float* __restrict__ V,
                                                             const float* __restrict__ bias, int64_t bias_bs, double beta, float* __restrict__ out,
-                                                            float* __restrict__ saved, float* __restrict__ lse, int N, int M, int D, int E, int tiles) {
+                                                            float* __restrict__ saved, float* __restrict__ lse, int N, int M, int D, int E, int tiles,
+                                                            CV... cv) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int LDB = NT * 16 + 4, NA = NT / WAVES;
   float* qt = smem;                                     // [MT][LDB] the query rows, resident
@@ -170,7 +173,7 @@ __global__ __launch_bounds__(THREADS) void attn_fwd_kernel(const float* __restri
     {                                                   // four threads a point
       const double s = tile_row_sq(ks, LDB, D, tid);
       float* p = vs + (tid >> 2) * LDB;
-      const double g = 2.0 / fmax(1.0 - tile_row_sq(vs, LDB, E, tid), GAMMA_EPS);
+      const double g = 2.0 / fmax(1.0 - curv_mul(tile_row_sq(vs, LDB, E, tid), cv...), GAMMA_EPS);
       for (int c = tid & 3; c < E; c += 4) p[c] = (float)(g * (double)p[c]);
       if ((tid & 3) == 0) { k2s[tid >> 2] = s; cjs[tid >> 2] = g - 1.0; }
     }
@@ -181,7 +184,7 @@ __global__ __launch_bounds__(THREADS) void attn_fwd_kernel(const float* __restri
     for (int r = 0; r < 4; ++r) {
       const int lr = 4 * q + r;
       sv[r] = HYPAD_NEG_INF;
-      if (lc < kw) sv[r] = -beta * dist_pair_d(q2s[lr], k2s[lc], (double)xy[r]) + (bias ? (double)ps[lr * LDP + lc] : 0.0);
+      if (lc < kw) sv[r] = -beta * dist_pair_d(q2s[lr], k2s[lc], (double)xy[r], cv...) + (bias ? (double)ps[lr * LDP + lc] : 0.0);
       const double top = group16_max(sv[r]);
       if (j == 0) wmx[wave * MT + lr] = top;
     }
@@ -240,7 +243,7 @@ __global__ __launch_bounds__(THREADS) void attn_fwd_kernel(const float* __restri
         if (t * 16 + j < E) sp[t * 16 + j] = (float)v.v[t];
       if (j == 0) { sp[E] = denf; lse[(size_t)b * N + gi] = Lrow[lr]; }
     }
-    const R o = midpoint_tail_d(v, (double)denf, 0.0, MidpointCfg{true, false, true, false});
+    const R o = midpoint_tail_d(v, (double)denf, 0.0, MidpointCfg{true, false, true, false}, cv...);
 #pragma unroll
     for (int t = 0; t < NT; ++t)
       if (rv && t * 16 + j < E) out[((size_t)b * N + gi) * E + t * 16 + j] = (float)o.v[t];
@@ -249,8 +252,9 @@ __global__ __launch_bounds__(THREADS) void attn_fwd_kernel(const float* __restri
 
 // The row pass of the backward, a wave per query row: from saved = [nom | den], L and grad_out to [g_s | g_d | delta] (rows, E + 2).
 // A row without a finite score (L = -inf) gets zeros.
+template <class... CV>
 __global__ __launch_bounds__(THREADS) void attn_rows_bwd(const float* __restrict__ saved, const float* __restrict__ lse, const float* __restrict__ go,
-                                                          float* __restrict__ ws, int64_t rows, int E) {
+                                                          float* __restrict__ ws, int64_t rows, int E, CV... cv) {
   const int lane = threadIdx.x & 63;
   for (int64_t r = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6); r < rows; r += (int64_t)gridDim.x * WAVES) {
     const float* sp = saved + r * (E + 1);
@@ -258,7 +262,7 @@ __global__ __launch_bounds__(THREADS) void attn_rows_bwd(const float* __restrict
     const double den = (double)sp[E];
     RW gnom;
     double gden, gr;
-    midpoint_tail_bwd_d(nom, den, 0.0, MidpointCfg{true, false, true, false}, rowd_load<RW>(go + r * E, E, lane), gnom, gden, gr);
+    midpoint_tail_bwd_d(nom, den, 0.0, MidpointCfg{true, false, true, false}, rowd_load<RW>(go + r * E, E, lane), gnom, gden, gr, cv...);
     double delta = rowd_dot(gnom, nom) + gden * den;
     if (lse[r] == (float)HYPAD_NEG_INF) {
 #pragma unroll
@@ -273,18 +277,19 @@ __global__ __launch_bounds__(THREADS) void attn_rows_bwd(const float* __restrict
 }
 
 // One pair of the backward: the weight p, and under g = -beta p (gw - delta) the pair terms a, b of dist_pair_bwd_d.  x2 is the query's.
+template <class... CV>
 __device__ __forceinline__ float pair_bwd(double x2, double y2, double xy, double bias, double beta, double L, double gw, double delta, double& a,
-                                          double& b) {
-  const float pf = (float)exp(-beta * dist_pair_d(x2, y2, xy) + bias - L);
-  dist_pair_bwd_d(x2, y2, xy, -beta * (double)pf * (gw - delta), a, b);
+                                          double& b, CV... cv) {
+  const float pf = (float)exp(-beta * dist_pair_d(x2, y2, xy, cv...) + bias - L);
+  dist_pair_bwd_d(x2, y2, xy, -beta * (double)pf * (gw - delta), a, b, cv...);
   return pf;
 }
 
-template <int NT>
+template <int NT, class... CV>
 __global__ __launch_bounds__(THREADS) void attn_gradq_kernel(const float* __restrict__ Q, const float* __restrict__ K, const float* __restrict__ V,
                                                               const float* __restrict__ bias, int64_t bias_bs, double beta,
                                                               const float* __restrict__ lse, const float* __restrict__ ws, float* __restrict__ grad,
-                                                              int N, int M, int D, int E, int tiles) {
+                                                              int N, int M, int D, int E, int tiles, CV... cv) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int LDB = NT * 16 + 4, NA = NT / WAVES;
   float* qt = smem;                                     // [MT][LDB] the query rows, resident
@@ -336,7 +341,7 @@ __global__ __launch_bounds__(THREADS) void attn_gradq_kernel(const float* __rest
     __syncthreads();
     {                                                   // four threads a point
       const double s = tile_row_sq(ks, LDB, D, tid);
-      const double g = 2.0 / fmax(1.0 - tile_row_sq(vs, LDB, E, tid), GAMMA_EPS);
+      const double g = 2.0 / fmax(1.0 - curv_mul(tile_row_sq(vs, LDB, E, tid), cv...), GAMMA_EPS);
       if ((tid & 3) == 0) { k2s[tid >> 2] = s; gms[tid >> 2] = g; cjs[tid >> 2] = g - 1.0; }
     }
     const f32x4 xy = tile_dots<LDB>(qt, ks, d4, wave * 16, j, q), gv = tile_dots<LDB>(gt, vs, e4, wave * 16, j, q);
@@ -349,9 +354,9 @@ __global__ __launch_bounds__(THREADS) void attn_gradq_kernel(const float* __rest
       float P = 0.f;
       if (Lr[r] != HYPAD_NEG_INF && lc < kw && bv != HYPAD_NEG_INF) {
         double da, db;
-        pair_bwd(q2s[lr], kk2, (double)xy[r], bv, beta, Lr[r], gm * (double)gv[r] + gdr[r] * cj, dlr[r], da, db);
+        pair_bwd(q2s[lr], kk2, (double)xy[r], bv, beta, Lr[r], gm * (double)gv[r] + gdr[r] * cj, dlr[r], da, db, cv...);
         P = (float)(-2.0 * (da + db));
-        rs[r] += da + db * kk2;
+        rs[r] += da + db * curv_mul(kk2, cv...);
       }
       ps[lr * LDP + lc] = P;
     }
@@ -377,11 +382,11 @@ __global__ __launch_bounds__(THREADS) void attn_gradq_kernel(const float* __rest
 }
 
 // grad_keys and grad_values of 16 keys and values against the N queries of their batch element; either may be NULL.
-template <int NT>
+template <int NT, class... CV>
 __global__ __launch_bounds__(THREADS) void attn_gradkv_kernel(const float* __restrict__ Q, const float* __restrict__ K, const float* __restrict__ V,
                                                                const float* __restrict__ bias, int64_t bias_bs, double beta,
                                                                const float* __restrict__ lse, const float* __restrict__ ws, float* __restrict__ gk,
-                                                               float* __restrict__ gvl, int N, int M, int D, int E, int tiles) {
+                                                               float* __restrict__ gvl, int N, int M, int D, int E, int tiles, CV... cv) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int LDB = NT * 16 + 4, NA = NT / WAVES;
   float* kt = smem;                                     // [MT][LDB] the keys, resident
@@ -413,7 +418,7 @@ __global__ __launch_bounds__(THREADS) void attn_gradkv_kernel(const float* __res
   __syncthreads();
   if (wave == 0) {
     const double s = tile_row_sq(kt, LDB, D, tid);
-    const double g = 2.0 / fmax(1.0 - tile_row_sq(vt, LDB, E, tid), GAMMA_EPS);
+    const double g = 2.0 / fmax(1.0 - curv_mul(tile_row_sq(vt, LDB, E, tid), cv...), GAMMA_EPS);
     if ((tid & 3) == 0) { k2s[tid >> 2] = s; gms[tid >> 2] = g; cjs[tid >> 2] = g - 1.0; }
   }
   f32x4 ack[NA], acv[NA];
@@ -454,9 +459,9 @@ __global__ __launch_bounds__(THREADS) void attn_gradkv_kernel(const float* __res
       if (L != HYPAD_NEG_INF && bv != HYPAD_NEG_INF) {
         const double kk2 = k2s[lr];
         double da, db;
-        pf = pair_bwd(qq, kk2, (double)xy[r], bv, beta, L, gms[lr] * (double)gv[r] + gd * cjs[lr], dl, da, db);
+        pf = pair_bwd(qq, kk2, (double)xy[r], bv, beta, L, gms[lr] * (double)gv[r] + gd * cjs[lr], dl, da, db, cv...);
         P = (float)(-2.0 * (da + db));
-        rs[r] += da + db * qq;
+        rs[r] += da + db * curv_mul(qq, cv...);
         hs[r] += (double)pf * gd;
       }
       ps[lr * LDP + lc] = pf;
@@ -500,9 +505,9 @@ __global__ __launch_bounds__(THREADS) void attn_gradkv_kernel(const float* __res
     R G, x;
 #pragma unroll
     for (int t = 0; t < NT; ++t) { G.v[t] = (double)qs[lr * LDB + t * 16 + j]; x.v[t] = (double)vt[lr * LDB + t * 16 + j]; }
-    const double om = 1.0 - rowd_dot(x, x);
+    const double om = 1.0 - curv_mul(rowd_dot(x, x), cv...);
     const double g = 2.0 / fmax(om, GAMMA_EPS);
-    const double s2 = om >= GAMMA_EPS ? g * g * (rowd_dot(G, x) + h) : 0.0;
+    const double s2 = om >= GAMMA_EPS ? curv_mul(g * g * (rowd_dot(G, x) + h), cv...) : 0.0;
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
       const int c = t * 16 + j;
@@ -537,28 +542,21 @@ inline size_t attn_workspace_floats(int64_t batch, int64_t N, int E) { return (s
 #define HYPAD_ATTN_LAUNCH(kernel, lds, grid, st, ...)                                        \
   do {                                                                                       \
     if (nt == 4) {                                                                           \
-      const hipError_t e = allow_lds((const void*)kernel<4>, lds);                           \
+      const hipError_t e = allow_lds((const void*)kernel<4, CV...>, lds);                    \
       if (e != hipSuccess) return (int)e;                                                    \
-      hipLaunchKernelGGL((kernel<4>), grid, dim3(THREADS), lds, st, __VA_ARGS__);            \
+      hipLaunchKernelGGL((kernel<4, CV...>), grid, dim3(THREADS), lds, st, __VA_ARGS__);     \
     } else {                                                                                 \
-      const hipError_t e = allow_lds((const void*)kernel<8>, lds);                           \
+      const hipError_t e = allow_lds((const void*)kernel<8, CV...>, lds);                    \
       if (e != hipSuccess) return (int)e;                                                    \
-      hipLaunchKernelGGL((kernel<8>), grid, dim3(THREADS), lds, st, __VA_ARGS__);            \
+      hipLaunchKernelGGL((kernel<8, CV...>), grid, dim3(THREADS), lds, st, __VA_ARGS__);     \
     }                                                                                        \
     HYPAD_CHECK_LAUNCH();                                                                    \
   } while (0)
 
-}  // namespace
-
-extern "C" {
-
-size_t hypad_hyp_attention_workspace_bytes(int64_t batch, int64_t N, int64_t M, int D, int E) {
-  if (batch <= 0 || N <= 0 || M <= 0 || D <= 0 || E <= 0) return 0;
-  return attn_workspace_floats(batch, N, E) * sizeof(float);
-}
-
-int hypad_hyp_attention_fwd(const float* q, const float* keys, const float* values, const float* bias, int64_t bias_batch_stride, double beta,
-                            float* out, float* saved, float* lse, int64_t batch, int64_t N, int64_t M, int D, int E, hypad_stream_t s) {
+// the bodies of the entry points, at k = -1 (no cv) and at k = -c
+template <class... CV>
+int attn_fwd(const float* q, const float* keys, const float* values, const float* bias, int64_t bias_batch_stride, double beta, float* out,
+             float* saved, float* lse, int64_t batch, int64_t N, int64_t M, int D, int E, hypad_stream_t s, CV... cv) {
   const int rc = attn_check(batch, N, M, D, E, beta);
   if (rc) return rc;
   if (bias && bias_batch_stride != 0 && bias_batch_stride != N * M) return HYPAD_EINVAL;
@@ -570,13 +568,14 @@ int hypad_hyp_attention_fwd(const float* q, const float* keys, const float* valu
   const size_t lds = fwd_lds(nt);
   const dim3 grid((unsigned)(batch * tiles));
   HYPAD_ATTN_LAUNCH(attn_fwd_kernel, lds, grid, (hipStream_t)s, q, keys, values, bias, bias_batch_stride, beta, out, saved, lse, (int)N, (int)M, D, E,
-                    (int)tiles);
+                    (int)tiles, cv...);
   return HYPAD_OK;
 }
 
-int hypad_hyp_attention_bwd(const float* q, const float* keys, const float* values, const float* bias, int64_t bias_batch_stride, double beta,
-                            const float* saved, const float* lse, const float* grad_out, float* grad_q, float* grad_keys, float* grad_values,
-                            void* workspace, size_t workspace_bytes, int64_t batch, int64_t N, int64_t M, int D, int E, hypad_stream_t s) {
+template <class... CV>
+int attn_bwd(const float* q, const float* keys, const float* values, const float* bias, int64_t bias_batch_stride, double beta, const float* saved,
+             const float* lse, const float* grad_out, float* grad_q, float* grad_keys, float* grad_values, void* workspace, size_t workspace_bytes,
+             int64_t batch, int64_t N, int64_t M, int D, int E, hypad_stream_t s, CV... cv) {
   const int rc = attn_check(batch, N, M, D, E, beta);
   if (rc) return rc;
   if (bias && bias_batch_stride != 0 && bias_batch_stride != N * M) return HYPAD_EINVAL;
@@ -592,21 +591,56 @@ int hypad_hyp_attention_bwd(const float* q, const float* keys, const float* valu
   if (tq > INT_LIMIT / batch || tk > INT_LIMIT / batch) return HYPAD_EUNSUPPORTED;
   const int nt = nt_of(D, E);
   float* ws = (float*)workspace;
-  hipLaunchKernelGGL(attn_rows_bwd, dim3(wave_grid(batch * N)), dim3(THREADS), 0, st, saved, lse, grad_out, ws, batch * N, E);
+  hipLaunchKernelGGL(attn_rows_bwd<CV...>, dim3(wave_grid(batch * N)), dim3(THREADS), 0, st, saved, lse, grad_out, ws, batch * N, E, cv...);
   HYPAD_CHECK_LAUNCH();
   if (grad_q) {
     const size_t lds = gq_lds(nt);
     const dim3 grid((unsigned)(batch * tq));
     HYPAD_ATTN_LAUNCH(attn_gradq_kernel, lds, grid, st, q, keys, values, bias, bias_batch_stride, beta, lse, (const float*)ws, grad_q, (int)N, (int)M,
-                      D, E, (int)tq);
+                      D, E, (int)tq, cv...);
   }
   if (grad_keys || grad_values) {
     const size_t lds = gkv_lds(nt);
     const dim3 grid((unsigned)(batch * tk));
     HYPAD_ATTN_LAUNCH(attn_gradkv_kernel, lds, grid, st, q, keys, values, bias, bias_batch_stride, beta, lse, (const float*)ws, grad_keys,
-                      grad_values, (int)N, (int)M, D, E, (int)tk);
+                      grad_values, (int)N, (int)M, D, E, (int)tk, cv...);
   }
   return HYPAD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t hypad_hyp_attention_workspace_bytes(int64_t batch, int64_t N, int64_t M, int D, int E) {
+  if (batch <= 0 || N <= 0 || M <= 0 || D <= 0 || E <= 0) return 0;
+  return attn_workspace_floats(batch, N, E) * sizeof(float);
+}
+
+int hypad_hyp_attention_fwd(const float* q, const float* keys, const float* values, const float* bias, int64_t bias_batch_stride, double beta,
+                            float* out, float* saved, float* lse, int64_t batch, int64_t N, int64_t M, int D, int E, hypad_stream_t s) {
+  return attn_fwd(q, keys, values, bias, bias_batch_stride, beta, out, saved, lse, batch, N, M, D, E, s);
+}
+int hypad_hyp_attention_bwd(const float* q, const float* keys, const float* values, const float* bias, int64_t bias_batch_stride, double beta,
+                            const float* saved, const float* lse, const float* grad_out, float* grad_q, float* grad_keys, float* grad_values,
+                            void* workspace, size_t workspace_bytes, int64_t batch, int64_t N, int64_t M, int D, int E, hypad_stream_t s) {
+  return attn_bwd(q, keys, values, bias, bias_batch_stride, beta, saved, lse, grad_out, grad_q, grad_keys, grad_values, workspace, workspace_bytes,
+                  batch, N, M, D, E, s);
+}
+// the same at k = -c: c is checked first, then everything as above; hypad_hyp_attention_workspace_bytes serves both
+int hypad_ball_hyp_attention_fwd(const float* q, const float* keys, const float* values, const float* bias, int64_t bias_batch_stride, double beta,
+                                 float* out, float* saved, float* lse, int64_t batch, int64_t N, int64_t M, int D, int E, double c,
+                                 hypad_stream_t s) {
+  return curv_invalid(c) ? HYPAD_EINVAL
+                  : attn_fwd(q, keys, values, bias, bias_batch_stride, beta, out, saved, lse, batch, N, M, D, E, s, curv_of(c));
+}
+int hypad_ball_hyp_attention_bwd(const float* q, const float* keys, const float* values, const float* bias, int64_t bias_batch_stride, double beta,
+                                 const float* saved, const float* lse, const float* grad_out, float* grad_q, float* grad_keys, float* grad_values,
+                                 void* workspace, size_t workspace_bytes, int64_t batch, int64_t N, int64_t M, int D, int E, double c,
+                                 hypad_stream_t s) {
+  return curv_invalid(c) ? HYPAD_EINVAL
+                  : attn_bwd(q, keys, values, bias, bias_batch_stride, beta, saved, lse, grad_out, grad_q, grad_keys, grad_values, workspace,
+                             workspace_bytes, batch, N, M, D, E, s, curv_of(c));
 }
 
 }  // extern "C"

@@ -61,8 +61,10 @@ __device__ __forceinline__ double quad_sum(double s) {
   return s + __shfl_xor(s, 2, WAVE);
 }
 
+// CV... here and below: the launch's curvature -- nothing at k = -1, one Curv at k = -c (rowops.h)
+template <class... CV>
 __global__ __launch_bounds__(THREADS) void dist_pair_fwd_kernel(const float* __restrict__ X, const float* __restrict__ Y, float* __restrict__ out,
-                                                                 int N, int M, int D, int tn, int tm) {
+                                                                 int N, int M, int D, int tn, int tm, CV... cv) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int ld = fw_ld(D);
   float* xt = smem;                                     // [64][ld] rows of x
@@ -109,16 +111,16 @@ __global__ __launch_bounds__(THREADS) void dist_pair_fwd_kernel(const float* __r
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       const int lc = t * 16 + j, gj = j0 + lc;
-      if (gj < M) out[(size_t)gi * M + gj] = (float)dist_pair_d(xx, y2s[lc], (double)acc[t][r]);
+      if (gj < M) out[(size_t)gi * M + gj] = (float)dist_pair_d(xx, y2s[lc], (double)acc[t][r], cv...);
     }
   }
 }
 
 // The gradient of the `rows` rows of A (rows, D) against the K rows of B (K, D) of one batch element.  GRADY = false: A = x, B = y,
 // g(i, k) = G[i][k]; GRADY = true: A = y, B = x, g(j, k) = G[k][j].  G is (N, M) row-major: gld = M.
-template <int NT, bool GRADY>
+template <int NT, bool GRADY, class... CV>
 __global__ __launch_bounds__(THREADS) void dist_pair_bwd_kernel(const float* __restrict__ A, const float* __restrict__ B, const float* __restrict__ G,
-                                                                 float* __restrict__ grad, int rows, int K, int gld, int D, int tiles) {
+                                                                 float* __restrict__ grad, int rows, int K, int gld, int D, int tiles, CV... cv) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int LDB = NT * 16 + 4;
   float* at = smem;                                     // [MT][LDB] the own rows, resident
@@ -183,9 +185,9 @@ __global__ __launch_bounds__(THREADS) void dist_pair_bwd_kernel(const float* __r
         const int lc = t * 16 + j;
         const double bb = b2s[lc];
         double da, db;
-        dist_pair_bwd_d(aa, bb, (double)xy[t][r], (double)ps[lr * LDP + lc], da, db);      // (g = 0 past either edge: nothing)
+        dist_pair_bwd_d(aa, bb, (double)xy[t][r], (double)ps[lr * LDP + lc], da, db, cv...);      // (g = 0 past either edge: nothing)
         ps[lr * LDP + lc] = (float)(-2.0 * (da + db));
-        rs[r] += da + db * bb;
+        rs[r] += da + db * curv_mul(bb, cv...);
       }
     }
     __syncthreads();                                    // P is in LDS
@@ -268,16 +270,17 @@ inline int rows_check(int64_t rows, int dim) {
   return dim > MAX_D ? HYPAD_EUNSUPPORTED : HYPAD_OK;
 }
 
-template <bool GRADY>
-int launch_pair_bwd(const float* A, const float* B, const float* G, float* grad, int64_t batch, int rows, int K, int gld, int D, hipStream_t st) {
+template <bool GRADY, class... CV>
+int launch_pair_bwd(const float* A, const float* B, const float* G, float* grad, int64_t batch, int rows, int K, int gld, int D, hipStream_t st,
+                    CV... cv) {
   const size_t lds = bwd_lds(D);
   const int tiles = (rows + MT - 1) / MT;
   const dim3 grid((unsigned)(batch * tiles));
 #define HYPAD_DIST_LAUNCH(NT)                                                                                                      \
   do {                                                                                                                              \
-    const hipError_t e = allow_lds((const void*)dist_pair_bwd_kernel<NT, GRADY>, lds);                                              \
+    const hipError_t e = allow_lds((const void*)dist_pair_bwd_kernel<NT, GRADY, CV...>, lds);                                       \
     if (e != hipSuccess) return (int)e;                                                                                             \
-    hipLaunchKernelGGL((dist_pair_bwd_kernel<NT, GRADY>), grid, dim3(THREADS), lds, st, A, B, G, grad, rows, K, gld, D, tiles);      \
+    hipLaunchKernelGGL((dist_pair_bwd_kernel<NT, GRADY, CV...>), grid, dim3(THREADS), lds, st, A, B, G, grad, rows, K, gld, D, tiles, cv...); \
   } while (0)
   if (D <= 64) HYPAD_DIST_LAUNCH(4);
   else if (D <= 128) HYPAD_DIST_LAUNCH(8);
@@ -287,11 +290,8 @@ int launch_pair_bwd(const float* A, const float* B, const float* G, float* grad,
   return HYPAD_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int hypad_dist_matmul_fwd(const float* x, const float* y, float* out, int64_t batch, int64_t N, int64_t M, int D, hypad_stream_t s) {
+template <class... CV>
+int pair_fwd(const float* x, const float* y, float* out, int64_t batch, int64_t N, int64_t M, int D, hypad_stream_t s, CV... cv) {
   const int rc = pair_check(batch, N, M, D);
   if (rc) return rc;
   if (pair_missing(x, y, out, batch, N, M)) return HYPAD_EINVAL;
@@ -299,15 +299,17 @@ int hypad_dist_matmul_fwd(const float* x, const float* y, float* out, int64_t ba
   const int tn = (int)((N + MT - 1) / MT), tm = (int)((M + MT - 1) / MT);
   if ((int64_t)tn * tm > INT_LIMIT / batch) return HYPAD_EUNSUPPORTED;
   const size_t lds = fwd_lds(D);
-  const hipError_t e = allow_lds((const void*)dist_pair_fwd_kernel, lds);
+  const hipError_t e = allow_lds((const void*)dist_pair_fwd_kernel<CV...>, lds);
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(dist_pair_fwd_kernel, dim3((unsigned)(batch * tn * tm)), dim3(THREADS), lds, (hipStream_t)s, x, y, out, (int)N, (int)M, D, tn, tm);
+  hipLaunchKernelGGL(dist_pair_fwd_kernel<CV...>, dim3((unsigned)(batch * tn * tm)), dim3(THREADS), lds, (hipStream_t)s, x, y, out, (int)N, (int)M, D, tn,
+                     tm, cv...);
   HYPAD_CHECK_LAUNCH();
   return HYPAD_OK;
 }
 
-int hypad_dist_matmul_bwd(const float* x, const float* y, const float* grad_out, float* grad_x, float* grad_y, int64_t batch, int64_t N, int64_t M,
-                          int D, hypad_stream_t s) {
+template <class... CV>
+int pair_bwd(const float* x, const float* y, const float* grad_out, float* grad_x, float* grad_y, int64_t batch, int64_t N, int64_t M, int D,
+             hypad_stream_t s, CV... cv) {
   const int rc = pair_check(batch, N, M, D);
   if (rc) return rc;
   if (pair_missing(x, y, grad_out, batch, N, M)) return HYPAD_EINVAL;
@@ -317,11 +319,31 @@ int hypad_dist_matmul_bwd(const float* x, const float* y, const float* grad_out,
     return rx ? rx : zero_floats(grad_y, (size_t)batch * M * D, st);
   }
   if (grad_x) {
-    const int r = launch_pair_bwd<false>(x, y, grad_out, grad_x, batch, (int)N, (int)M, (int)M, D, st);
+    const int r = launch_pair_bwd<false>(x, y, grad_out, grad_x, batch, (int)N, (int)M, (int)M, D, st, cv...);
     if (r) return r;
   }
-  if (grad_y) return launch_pair_bwd<true>(y, x, grad_out, grad_y, batch, (int)M, (int)N, (int)M, D, st);
+  if (grad_y) return launch_pair_bwd<true>(y, x, grad_out, grad_y, batch, (int)M, (int)N, (int)M, D, st, cv...);
   return HYPAD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hypad_dist_matmul_fwd(const float* x, const float* y, float* out, int64_t batch, int64_t N, int64_t M, int D, hypad_stream_t s) {
+  return pair_fwd(x, y, out, batch, N, M, D, s);
+}
+int hypad_dist_matmul_bwd(const float* x, const float* y, const float* grad_out, float* grad_x, float* grad_y, int64_t batch, int64_t N, int64_t M,
+                          int D, hypad_stream_t s) {
+  return pair_bwd(x, y, grad_out, grad_x, grad_y, batch, N, M, D, s);
+}
+// the same at k = -c: c is checked first, then everything as above
+int hypad_ball_dist_matmul_fwd(const float* x, const float* y, float* out, int64_t batch, int64_t N, int64_t M, int D, double c, hypad_stream_t s) {
+  return curv_invalid(c) ? HYPAD_EINVAL : pair_fwd(x, y, out, batch, N, M, D, s, curv_of(c));
+}
+int hypad_ball_dist_matmul_bwd(const float* x, const float* y, const float* grad_out, float* grad_x, float* grad_y, int64_t batch, int64_t N,
+                               int64_t M, int D, double c, hypad_stream_t s) {
+  return curv_invalid(c) ? HYPAD_EINVAL : pair_bwd(x, y, grad_out, grad_x, grad_y, batch, N, M, D, s, curv_of(c));
 }
 
 int hypad_dist_fwd(const float* x, const float* y, float* out, int64_t rows, int dim, hypad_stream_t s) {

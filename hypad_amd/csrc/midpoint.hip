@@ -69,10 +69,12 @@ inline size_t gw_lds(int D) { return (size_t)(2 * MT * gw_ld(D) + 2 * MT) * size
 // out rows x contraction positions of one batch element.  GRADX = false, the forward: a(i, j) = W[i][j], the chunk rows are
 // gamma_j x_j formed from X (M, D), the side vector is c_j.  GRADX = true: a(j, i) = W[i][j], the chunk rows are g_s_i (N, D), the
 // side vector is g_d_i, and the epilogue closes grad_x.  `rows` = output rows, `K` = contraction length, wld = M.
-template <int NT, bool GRADX>
+// CV... here and below: the launch's curvature -- nothing at k = -1, one Curv at k = -c (rowops.h), where gamma_j = 2 / max(1 - c |x_j|^2,
+// 1e-15), d gamma / d x = c gamma^2 x, and the tail halves by 1 + sqrt(1 - c |t|^2) and projects onto (1 - 4e-3) / sqrt(c).
+template <int NT, bool GRADX, class... CV>
 __global__ __launch_bounds__(THREADS) void mid_product_kernel(const float* __restrict__ W, const float* __restrict__ B, const float* __restrict__ side,
                                                                const float* __restrict__ X, float* __restrict__ out, float* __restrict__ saved,
-                                                               int rows, int K, int wld, int D, int tiles, int lincomb) {
+                                                               int rows, int K, int wld, int D, int tiles, int lincomb, CV... cv) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int LDB = NT * 16 + 4;
   float* bs = smem;                                     // [KC][LDB]
@@ -111,7 +113,7 @@ __global__ __launch_bounds__(THREADS) void mid_product_kernel(const float* __res
       for (int c = tid & 3; c < D; c += 4) { const double v = p[c]; s += v * v; }
       s += __shfl_xor(s, 1, WAVE);
       s += __shfl_xor(s, 2, WAVE);
-      const double g = 2.0 / fmax(1.0 - s, GAMMA_EPS);
+      const double g = 2.0 / fmax(1.0 - curv_mul(s, cv...), GAMMA_EPS);
       for (int c = tid & 3; c < D; c += 4) p[c] = (float)(g * (double)p[c]);
       if ((tid & 3) == 0) sv[tid >> 2] = (float)(g - 1.0);
       __syncthreads();
@@ -148,9 +150,9 @@ __global__ __launch_bounds__(THREADS) void mid_product_kernel(const float* __res
       R x;
 #pragma unroll
       for (int t = 0; t < NT; ++t) x.v[t] = (rv && t * 16 + j < D) ? (double)xr[t * 16 + j] : 0.0;
-      const double om = 1.0 - rowd_dot(x, x);
+      const double om = 1.0 - curv_mul(rowd_dot(x, x), cv...);
       const double g = 2.0 / fmax(om, GAMMA_EPS);
-      const double s = om >= GAMMA_EPS ? g * g * (rowd_dot(v, x) + dn[lr]) : 0.0;
+      const double s = om >= GAMMA_EPS ? curv_mul(g * g * (rowd_dot(v, x) + dn[lr]), cv...) : 0.0;
 #pragma unroll
       for (int t = 0; t < NT; ++t)
         if (rv && t * 16 + j < D) out[((size_t)b * rows + gr) * D + t * 16 + j] = (float)(g * v.v[t] + s * x.v[t]);
@@ -163,7 +165,7 @@ __global__ __launch_bounds__(THREADS) void mid_product_kernel(const float* __res
           if (t * 16 + j < D) sp[t * 16 + j] = acc[t][r];
         if (j == 0) { sp[D] = denf; sp[D + 1] = alf; }
       }
-      const R o = midpoint_tail_d(v, (double)denf, (double)alf, MidpointCfg{true, lincomb != 0, true, false});
+      const R o = midpoint_tail_d(v, (double)denf, (double)alf, MidpointCfg{true, lincomb != 0, true, false}, cv...);
 #pragma unroll
       for (int t = 0; t < NT; ++t)
         if (rv && t * 16 + j < D) out[((size_t)b * rows + gr) * D + t * 16 + j] = (float)o.v[t];
@@ -175,25 +177,27 @@ __global__ __launch_bounds__(THREADS) void mid_product_kernel(const float* __res
 // g_alpha.  The scalar of lincomb is r = rscale alpha (1 in the bmm form, 1/2 in the reduce form).  T: fp32 in the bmm form, whose
 // sums are fp32 MFMA products; fp64 in the reduce form, whose sums are fp64 and where grad_w = gamma <g_nom, x> + (gamma - 1) g_d is
 // the difference of two terms 1 / sqrt(1 - |t|^2) times its size when one point carries the row (a single point: exactly zero).
-template <class T>
+template <class T, class... CV>
 __global__ __launch_bounds__(THREADS) void mid_rows_bwd(const T* __restrict__ saved, const float* __restrict__ go, T* __restrict__ gs,
                                                          T* __restrict__ gd, T* __restrict__ ga, int64_t rows, int D, MidpointCfg cfg,
-                                                         float rscale) {
+                                                         float rscale, CV... cv) {
   const int lane = threadIdx.x & 63;
   for (int64_t r = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6); r < rows; r += (int64_t)gridDim.x * WAVES) {
     const T* sp = saved + r * (D + 2);
     RW gnom;
     double gden, gr;
-    midpoint_tail_bwd_d(load_row(sp, D, lane), (double)sp[D], (double)rscale * (double)sp[D + 1], cfg, load_row(go + r * D, D, lane), gnom, gden, gr);
+    midpoint_tail_bwd_d(load_row(sp, D, lane), (double)sp[D], (double)rscale * (double)sp[D + 1], cfg, load_row(go + r * D, D, lane), gnom, gden, gr,
+                        cv...);
     store_row(gs + r * D, gnom, D, lane);
     if (lane == 0) { gd[r] = (T)gden; ga[r] = (T)((double)rscale * gr); }
   }
 }
 
 // grad_w (N, M) of one batch element, a 64 x 64 tile per workgroup: gamma_j <g_s_i, x_j> + sign(w_ij) (g_d_i c_j + g_alpha_i).
+template <class... CV>
 __global__ __launch_bounds__(THREADS) void mid_gradw_kernel(const float* __restrict__ W, const float* __restrict__ X, const float* __restrict__ gs,
                                                              const float* __restrict__ gd, const float* __restrict__ ga, float* __restrict__ gw,
-                                                             int N, int M, int D, int tn, int tm, int lincomb) {
+                                                             int N, int M, int D, int tn, int tm, int lincomb, CV... cv) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int ld = gw_ld(D);
   float* gt = smem;                                     // [64][ld] g_s rows
@@ -236,7 +240,7 @@ __global__ __launch_bounds__(THREADS) void mid_gradw_kernel(const float* __restr
   x2 += __shfl_xor(x2, 1, WAVE);
   x2 += __shfl_xor(x2, 2, WAVE);
   if ((tid & 3) == 0) {
-    const double g = 2.0 / fmax(1.0 - x2, GAMMA_EPS);
+    const double g = 2.0 / fmax(1.0 - curv_mul(x2, cv...), GAMMA_EPS);
     gam[tid >> 2] = (float)g;
     cj[tid >> 2] = (float)(g - 1.0);
   }
@@ -287,20 +291,22 @@ __device__ __forceinline__ MidpointCfg red_cfg(int flags) {
   return MidpointCfg{!(flags & (HYPAD_MID_LINCOMB | HYPAD_MID_COADD)), (flags & HYPAD_MID_LINCOMB) != 0, false, true};
 }
 // the fp64 sums of a kept row to `saved` and to the row of out
+template <class... CV>
 __device__ __forceinline__ void red_finish(const RW& nom, double den, double alpha, float* __restrict__ out, double* __restrict__ saved, int64_t rho,
-                                           int D, int flags, int lane) {
+                                           int D, int flags, int lane, CV... cv) {
   if (saved) {
     double* sp = saved + rho * (D + 2);
     store_row(sp, nom, D, lane);
     if (lane == 0) { sp[D] = den; sp[D + 1] = alpha; }
   }
-  store_row(out + rho * D, midpoint_tail_d(nom, den, 0.5 * alpha, red_cfg(flags)), D, lane);
+  store_row(out + rho * D, midpoint_tail_d(nom, den, 0.5 * alpha, red_cfg(flags), cv...), D, lane);
 }
 // A wave per (kept row, slice of the positions): the three sums in fp64 registers.  One slice: the row is finished here; more: the
 // partial sums go to part (slices, R, D + 2) and mid_reduce_finish adds them in slice order.
+template <class... CV>
 __global__ __launch_bounds__(THREADS) void mid_reduce_kernel(const float* __restrict__ xs, const float* __restrict__ w, int wkind,
                                                               double* __restrict__ part, float* __restrict__ out, double* __restrict__ saved, int64_t M,
-                                                              int64_t R, int D, int slices, int64_t slice_len, int flags) {
+                                                              int64_t R, int D, int slices, int64_t slice_len, int flags, CV... cv) {
   const int lane = threadIdx.x & 63;
   const bool pos = (flags & HYPAD_MID_POSWEIGHT) != 0;
   for (int64_t task = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6); task < R * slices; task += (int64_t)gridDim.x * WAVES) {
@@ -314,14 +320,14 @@ __global__ __launch_bounds__(THREADS) void mid_reduce_kernel(const float* __rest
       const int64_t idx = m * R + rho;
       const RW x = rowd_load<RW>(xs + idx * D, D, lane);
       const double wv = red_weight(w, wkind, idx);
-      const double g = 2.0 / fmax(1.0 - rowd_dot(x, x), GAMMA_EPS);
+      const double g = 2.0 / fmax(1.0 - curv_mul(rowd_dot(x, x), cv...), GAMMA_EPS);
 #pragma unroll
       for (int e = 0; e < RW::EPL; ++e) nom.v[e] += g * wv * x.v[e];
       den += (g - 1.0) * fabs(wv);
       alpha += pos ? fabs(wv) : wv;
     }
     if (slices == 1) {
-      red_finish(nom, den, alpha, out, saved, rho, D, flags, lane);
+      red_finish(nom, den, alpha, out, saved, rho, D, flags, lane, cv...);
     } else {
       double* p = part + (sl * R + rho) * (D + 2);
 #pragma unroll
@@ -330,8 +336,9 @@ __global__ __launch_bounds__(THREADS) void mid_reduce_kernel(const float* __rest
     }
   }
 }
+template <class... CV>
 __global__ __launch_bounds__(THREADS) void mid_reduce_finish(const double* __restrict__ part, float* __restrict__ out, double* __restrict__ saved,
-                                                              int64_t R, int D, int slices, int flags) {
+                                                              int64_t R, int D, int slices, int flags, CV... cv) {
   const int lane = threadIdx.x & 63;
   for (int64_t rho = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6); rho < R; rho += (int64_t)gridDim.x * WAVES) {
     RW nom;
@@ -345,26 +352,27 @@ __global__ __launch_bounds__(THREADS) void mid_reduce_finish(const double* __res
       den += p[D];
       alpha += p[D + 1];
     }
-    red_finish(nom, den, alpha, out, saved, rho, D, flags, lane);
+    red_finish(nom, den, alpha, out, saved, rho, D, flags, lane, cv...);
   }
 }
 // The element-wise pass of the backward, a wave per (position, kept row):
 //   grad_x = gamma w g_nom + gamma^2 (w <g_nom, x> + |w| g_d) x        (the second term 0 where gamma is clamped)
 //   grad_w = gamma <g_nom, x> + sign(w) (gamma - 1) g_d + g_alpha      (g_alpha times -1 for a negative weight with posweight)
 // gw (M, R): the weights' gradient, or the summands of a single weight's.
+template <class... CV>
 __global__ __launch_bounds__(THREADS) void mid_reduce_elem_bwd(const float* __restrict__ xs, const float* __restrict__ w, int wkind,
                                                                 const double* __restrict__ gnom, const double* __restrict__ gd,
                                                                 const double* __restrict__ ga, float* __restrict__ gx, float* __restrict__ gw,
-                                                                int64_t MR, int64_t R, int D, int flags) {
+                                                                int64_t MR, int64_t R, int D, int flags, CV... cv) {
   const int lane = threadIdx.x & 63;
   const bool pos = (flags & HYPAD_MID_POSWEIGHT) != 0;
   for (int64_t idx = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6); idx < MR; idx += (int64_t)gridDim.x * WAVES) {
     const int64_t rho = idx % R;
     const RW x = load_row(xs + idx * D, D, lane), gn = load_row(gnom + rho * D, D, lane);
     const double wv = red_weight(w, wkind, idx), gdv = gd[rho], gav = ga[rho];
-    const double om = 1.0 - rowd_dot(x, x), g = 2.0 / fmax(om, GAMMA_EPS), gnx = rowd_dot(gn, x);
+    const double om = 1.0 - curv_mul(rowd_dot(x, x), cv...), g = 2.0 / fmax(om, GAMMA_EPS), gnx = rowd_dot(gn, x);
     if (gx) {
-      const double s = om >= GAMMA_EPS ? g * g * (wv * gnx + fabs(wv) * gdv) : 0.0;
+      const double s = om >= GAMMA_EPS ? curv_mul(g * g * (wv * gnx + fabs(wv) * gdv), cv...) : 0.0;
       RW o;
 #pragma unroll
       for (int e = 0; e < RW::EPL; ++e) o.v[e] = g * wv * gn.v[e] + s * x.v[e];
@@ -458,23 +466,114 @@ inline int red_check(const float* xs, const float* w, int64_t w_count, int64_t M
 }
 inline int red_wkind(const float* w, int64_t w_count, int64_t MR) { return !w ? W_NONE : (w_count == 1 && MR != 1) ? W_SCALAR : W_ELEMENTS; }
 
-template <bool GRADX>
+template <bool GRADX, class... CV>
 int launch_product(const float* W, const float* B, const float* side, const float* X, float* out, float* saved, int64_t batch, int rows, int K, int wld,
-                   int D, int lincomb, hipStream_t st) {
+                   int D, int lincomb, hipStream_t st, CV... cv) {
   const size_t lds = prod_lds(D);
   const int tiles = (rows + MT - 1) / MT;
   const dim3 grid((unsigned)(batch * tiles));
 #define HYPAD_MID_LAUNCH(NT)                                                                                                              \
   do {                                                                                                                                     \
-    const hipError_t e = allow_lds((const void*)mid_product_kernel<NT, GRADX>, lds);                                                       \
+    const hipError_t e = allow_lds((const void*)mid_product_kernel<NT, GRADX, CV...>, lds);                                                \
     if (e != hipSuccess) return (int)e;                                                                                                    \
-    hipLaunchKernelGGL((mid_product_kernel<NT, GRADX>), grid, dim3(THREADS), lds, st, W, B, side, X, out, saved, rows, K, wld, D, tiles, lincomb); \
+    hipLaunchKernelGGL((mid_product_kernel<NT, GRADX, CV...>), grid, dim3(THREADS), lds, st, W, B, side, X, out, saved, rows, K, wld, D, tiles, lincomb, \
+                       cv...);                                                                                                             \
   } while (0)
   if (D <= 64) HYPAD_MID_LAUNCH(4);
   else if (D <= 128) HYPAD_MID_LAUNCH(8);
   else HYPAD_MID_LAUNCH(16);
 #undef HYPAD_MID_LAUNCH
   HYPAD_CHECK_LAUNCH();
+  return HYPAD_OK;
+}
+
+// the bodies of the bmm and the reduce entry points, at k = -1 (no cv) and at k = -c
+template <class... CV>
+int bmm_fwd(const float* xs, const float* weights, float* out, float* saved, int64_t batch, int64_t N, int64_t M, int D, int flags, hypad_stream_t s,
+            CV... cv) {
+  const int rc = bmm_check(xs, weights, batch, N, M, D, flags);
+  if (rc || N == 0) return rc;
+  if (!out) return HYPAD_EINVAL;
+  return launch_product<false>(weights, xs, nullptr, nullptr, out, saved, batch, (int)N, (int)M, (int)M, D, flags & HYPAD_MID_LINCOMB, (hipStream_t)s,
+                               cv...);
+}
+
+template <class... CV>
+int bmm_bwd(const float* xs, const float* weights, const float* saved, const float* grad_out, float* grad_xs, float* grad_weights, void* workspace,
+            size_t workspace_bytes, int64_t batch, int64_t N, int64_t M, int D, int flags, hypad_stream_t s, CV... cv) {
+  const int rc = bmm_check(xs, weights, batch, N, M, D, flags);
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)s;
+  if (N == 0) return zero_floats(grad_xs, (size_t)batch * M * D, st);      // a sum over no output rows
+  if (!saved || !grad_out) return HYPAD_EINVAL;
+  if (!grad_xs && !grad_weights) return HYPAD_OK;
+  const BmmWorkspace w = bmm_workspace(batch, N, D);
+  if (!workspace || workspace_bytes < w.total * sizeof(float)) return HYPAD_EWORKSPACE;
+  float* ws = (float*)workspace;
+  const int lincomb = flags & HYPAD_MID_LINCOMB;
+  hipLaunchKernelGGL((mid_rows_bwd<float, CV...>), dim3(wave_grid(batch * N)), dim3(THREADS), 0, st, saved, grad_out, ws + w.gs, ws + w.gd, ws + w.ga,
+                     batch * N, D, MidpointCfg{true, lincomb != 0, true, false}, 1.f, cv...);
+  HYPAD_CHECK_LAUNCH();
+  if (grad_weights) {
+    const int tn = (int)((N + MT - 1) / MT), tm = (int)((M + MT - 1) / MT);
+    const size_t lds = gw_lds(D);
+    const hipError_t e = allow_lds((const void*)mid_gradw_kernel<CV...>, lds);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(mid_gradw_kernel<CV...>, dim3((unsigned)(batch * tn * tm)), dim3(THREADS), lds, st, weights, xs, ws + w.gs, ws + w.gd, ws + w.ga,
+                       grad_weights, (int)N, (int)M, D, tn, tm, lincomb, cv...);
+    HYPAD_CHECK_LAUNCH();
+  }
+  if (grad_xs)
+    return launch_product<true>(weights, ws + w.gs, ws + w.gd, xs, grad_xs, nullptr, batch, (int)M, (int)N, (int)M, D, lincomb, st, cv...);
+  return HYPAD_OK;
+}
+
+template <class... CV>
+int red_fwd(const float* xs, const float* weights, int64_t w_count, float* out, double* saved, void* workspace, size_t workspace_bytes, int64_t M,
+            int64_t R, int D, int flags, hypad_stream_t s, CV... cv) {
+  const int rc = red_check(xs, weights, w_count, M, R, D, flags);
+  if (rc || R == 0) return rc;
+  if (!out || ((uintptr_t)saved & 7)) return HYPAD_EINVAL;
+  const RedPlan p = red_plan(M, R, D);
+  if (p.slices > 1 && (!workspace || ((uintptr_t)workspace & 7) || workspace_bytes < red_bytes(p))) return HYPAD_EWORKSPACE;
+  hipStream_t st = (hipStream_t)s;
+  double* part = (double*)workspace;
+  hipLaunchKernelGGL(mid_reduce_kernel<CV...>, dim3(wave_grid(R * p.slices)), dim3(THREADS), 0, st, xs, weights, red_wkind(weights, w_count, M * R), part,
+                     out, saved, M, R, D, p.slices, p.slice_len, flags, cv...);
+  HYPAD_CHECK_LAUNCH();
+  if (p.slices > 1) {
+    hipLaunchKernelGGL(mid_reduce_finish<CV...>, dim3(wave_grid(R)), dim3(THREADS), 0, st, (const double*)part, out, saved, R, D, p.slices, flags, cv...);
+    HYPAD_CHECK_LAUNCH();
+  }
+  return HYPAD_OK;
+}
+
+template <class... CV>
+int red_bwd(const float* xs, const float* weights, int64_t w_count, const double* saved, const float* grad_out, float* grad_xs, float* grad_weights,
+            void* workspace, size_t workspace_bytes, int64_t M, int64_t R, int D, int flags, hypad_stream_t s, CV... cv) {
+  const int rc = red_check(xs, weights, w_count, M, R, D, flags);
+  if (rc) return rc;
+  if (grad_weights && !weights) return HYPAD_EINVAL;
+  hipStream_t st = (hipStream_t)s;
+  const int wkind = red_wkind(weights, w_count, M * R);
+  if (R == 0) return wkind == W_SCALAR || w_count == 1 ? zero_floats(grad_weights, 1, st) : HYPAD_OK;   // a sum over no rows
+  if (!saved || ((uintptr_t)saved & 7) || !grad_out) return HYPAD_EINVAL;
+  if (!grad_xs && !grad_weights) return HYPAD_OK;
+  const RedPlan p = red_plan(M, R, D);
+  if (!workspace || ((uintptr_t)workspace & 7) || workspace_bytes < red_bytes(p)) return HYPAD_EWORKSPACE;
+  double* wd = (double*)workspace;
+  float* wf = (float*)(wd + p.doubles);
+  hipLaunchKernelGGL((mid_rows_bwd<double, CV...>), dim3(wave_grid(R)), dim3(THREADS), 0, st, saved, grad_out, wd + p.gnom, wd + p.gd, wd + p.ga, R, D,
+                     MidpointCfg{!(flags & (HYPAD_MID_LINCOMB | HYPAD_MID_COADD)), (flags & HYPAD_MID_LINCOMB) != 0, false, true}, 0.5f, cv...);
+  HYPAD_CHECK_LAUNCH();
+  float* gw = !grad_weights ? nullptr : wkind == W_SCALAR ? wf : grad_weights;
+  hipLaunchKernelGGL(mid_reduce_elem_bwd<CV...>, dim3(wave_grid(M * R)), dim3(THREADS), 0, st, xs, weights, wkind, (const double*)(wd + p.gnom),
+                     (const double*)(wd + p.gd), (const double*)(wd + p.ga), grad_xs, gw, M * R, R, D, flags, cv...);
+  HYPAD_CHECK_LAUNCH();
+  if (grad_weights && wkind == W_SCALAR) {
+    hipLaunchKernelGGL(fixed_sum_kernel, dim3(1), dim3(THREADS), 0, st, (const float*)wf, grad_weights, M * R);
+    HYPAD_CHECK_LAUNCH();
+  }
   return HYPAD_OK;
 }
 
@@ -506,40 +605,12 @@ size_t hypad_weighted_midpoint_bmm_workspace_bytes(int64_t batch, int64_t N, int
 
 int hypad_weighted_midpoint_bmm_fwd(const float* xs, const float* weights, float* out, float* saved, int64_t batch, int64_t N, int64_t M, int D,
                                     int flags, hypad_stream_t s) {
-  const int rc = bmm_check(xs, weights, batch, N, M, D, flags);
-  if (rc || N == 0) return rc;
-  if (!out) return HYPAD_EINVAL;
-  return launch_product<false>(weights, xs, nullptr, nullptr, out, saved, batch, (int)N, (int)M, (int)M, D, flags & HYPAD_MID_LINCOMB, (hipStream_t)s);
+  return bmm_fwd(xs, weights, out, saved, batch, N, M, D, flags, s);
 }
-
 int hypad_weighted_midpoint_bmm_bwd(const float* xs, const float* weights, const float* saved, const float* grad_out, float* grad_xs,
                                     float* grad_weights, void* workspace, size_t workspace_bytes, int64_t batch, int64_t N, int64_t M, int D,
                                     int flags, hypad_stream_t s) {
-  const int rc = bmm_check(xs, weights, batch, N, M, D, flags);
-  if (rc) return rc;
-  hipStream_t st = (hipStream_t)s;
-  if (N == 0) return zero_floats(grad_xs, (size_t)batch * M * D, st);      // a sum over no output rows
-  if (!saved || !grad_out) return HYPAD_EINVAL;
-  if (!grad_xs && !grad_weights) return HYPAD_OK;
-  const BmmWorkspace w = bmm_workspace(batch, N, D);
-  if (!workspace || workspace_bytes < w.total * sizeof(float)) return HYPAD_EWORKSPACE;
-  float* ws = (float*)workspace;
-  const int lincomb = flags & HYPAD_MID_LINCOMB;
-  hipLaunchKernelGGL(mid_rows_bwd<float>, dim3(wave_grid(batch * N)), dim3(THREADS), 0, st, saved, grad_out, ws + w.gs, ws + w.gd, ws + w.ga, batch * N,
-                     D, MidpointCfg{true, lincomb != 0, true, false}, 1.f);
-  HYPAD_CHECK_LAUNCH();
-  if (grad_weights) {
-    const int tn = (int)((N + MT - 1) / MT), tm = (int)((M + MT - 1) / MT);
-    const size_t lds = gw_lds(D);
-    const hipError_t e = allow_lds((const void*)mid_gradw_kernel, lds);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(mid_gradw_kernel, dim3((unsigned)(batch * tn * tm)), dim3(THREADS), lds, st, weights, xs, ws + w.gs, ws + w.gd, ws + w.ga,
-                       grad_weights, (int)N, (int)M, D, tn, tm, lincomb);
-    HYPAD_CHECK_LAUNCH();
-  }
-  if (grad_xs)
-    return launch_product<true>(weights, ws + w.gs, ws + w.gd, xs, grad_xs, nullptr, batch, (int)M, (int)N, (int)M, D, lincomb, st);
-  return HYPAD_OK;
+  return bmm_bwd(xs, weights, saved, grad_out, grad_xs, grad_weights, workspace, workspace_bytes, batch, N, M, D, flags, s);
 }
 
 size_t hypad_weighted_midpoint_workspace_bytes(int64_t M, int64_t R, int D) {
@@ -549,50 +620,34 @@ size_t hypad_weighted_midpoint_workspace_bytes(int64_t M, int64_t R, int D) {
 
 int hypad_weighted_midpoint_fwd(const float* xs, const float* weights, int64_t w_count, float* out, double* saved, void* workspace,
                                 size_t workspace_bytes, int64_t M, int64_t R, int D, int flags, hypad_stream_t s) {
-  const int rc = red_check(xs, weights, w_count, M, R, D, flags);
-  if (rc || R == 0) return rc;
-  if (!out || ((uintptr_t)saved & 7)) return HYPAD_EINVAL;
-  const RedPlan p = red_plan(M, R, D);
-  if (p.slices > 1 && (!workspace || ((uintptr_t)workspace & 7) || workspace_bytes < red_bytes(p))) return HYPAD_EWORKSPACE;
-  hipStream_t st = (hipStream_t)s;
-  double* part = (double*)workspace;
-  hipLaunchKernelGGL(mid_reduce_kernel, dim3(wave_grid(R * p.slices)), dim3(THREADS), 0, st, xs, weights, red_wkind(weights, w_count, M * R), part, out,
-                     saved, M, R, D, p.slices, p.slice_len, flags);
-  HYPAD_CHECK_LAUNCH();
-  if (p.slices > 1) {
-    hipLaunchKernelGGL(mid_reduce_finish, dim3(wave_grid(R)), dim3(THREADS), 0, st, (const double*)part, out, saved, R, D, p.slices, flags);
-    HYPAD_CHECK_LAUNCH();
-  }
-  return HYPAD_OK;
+  return red_fwd(xs, weights, w_count, out, saved, workspace, workspace_bytes, M, R, D, flags, s);
 }
-
 int hypad_weighted_midpoint_bwd(const float* xs, const float* weights, int64_t w_count, const double* saved, const float* grad_out, float* grad_xs,
                                 float* grad_weights, void* workspace, size_t workspace_bytes, int64_t M, int64_t R, int D, int flags,
                                 hypad_stream_t s) {
-  const int rc = red_check(xs, weights, w_count, M, R, D, flags);
-  if (rc) return rc;
-  if (grad_weights && !weights) return HYPAD_EINVAL;
-  hipStream_t st = (hipStream_t)s;
-  const int wkind = red_wkind(weights, w_count, M * R);
-  if (R == 0) return wkind == W_SCALAR || w_count == 1 ? zero_floats(grad_weights, 1, st) : HYPAD_OK;   // a sum over no rows
-  if (!saved || ((uintptr_t)saved & 7) || !grad_out) return HYPAD_EINVAL;
-  if (!grad_xs && !grad_weights) return HYPAD_OK;
-  const RedPlan p = red_plan(M, R, D);
-  if (!workspace || ((uintptr_t)workspace & 7) || workspace_bytes < red_bytes(p)) return HYPAD_EWORKSPACE;
-  double* wd = (double*)workspace;
-  float* wf = (float*)(wd + p.doubles);
-  hipLaunchKernelGGL(mid_rows_bwd<double>, dim3(wave_grid(R)), dim3(THREADS), 0, st, saved, grad_out, wd + p.gnom, wd + p.gd, wd + p.ga, R, D,
-                     MidpointCfg{!(flags & (HYPAD_MID_LINCOMB | HYPAD_MID_COADD)), (flags & HYPAD_MID_LINCOMB) != 0, false, true}, 0.5f);
-  HYPAD_CHECK_LAUNCH();
-  float* gw = !grad_weights ? nullptr : wkind == W_SCALAR ? wf : grad_weights;
-  hipLaunchKernelGGL(mid_reduce_elem_bwd, dim3(wave_grid(M * R)), dim3(THREADS), 0, st, xs, weights, wkind, (const double*)(wd + p.gnom),
-                     (const double*)(wd + p.gd), (const double*)(wd + p.ga), grad_xs, gw, M * R, R, D, flags);
-  HYPAD_CHECK_LAUNCH();
-  if (grad_weights && wkind == W_SCALAR) {
-    hipLaunchKernelGGL(fixed_sum_kernel, dim3(1), dim3(THREADS), 0, st, (const float*)wf, grad_weights, M * R);
-    HYPAD_CHECK_LAUNCH();
-  }
-  return HYPAD_OK;
+  return red_bwd(xs, weights, w_count, saved, grad_out, grad_xs, grad_weights, workspace, workspace_bytes, M, R, D, flags, s);
+}
+
+// the same at k = -c: c is checked first, then everything as above; the *_workspace_bytes functions serve both
+int hypad_ball_weighted_midpoint_bmm_fwd(const float* xs, const float* weights, float* out, float* saved, int64_t batch, int64_t N, int64_t M, int D,
+                                         int flags, double c, hypad_stream_t s) {
+  return curv_invalid(c) ? HYPAD_EINVAL : bmm_fwd(xs, weights, out, saved, batch, N, M, D, flags, s, curv_of(c));
+}
+int hypad_ball_weighted_midpoint_bmm_bwd(const float* xs, const float* weights, const float* saved, const float* grad_out, float* grad_xs,
+                                         float* grad_weights, void* workspace, size_t workspace_bytes, int64_t batch, int64_t N, int64_t M, int D,
+                                         int flags, double c, hypad_stream_t s) {
+  return curv_invalid(c) ? HYPAD_EINVAL
+                  : bmm_bwd(xs, weights, saved, grad_out, grad_xs, grad_weights, workspace, workspace_bytes, batch, N, M, D, flags, s, curv_of(c));
+}
+int hypad_ball_weighted_midpoint_fwd(const float* xs, const float* weights, int64_t w_count, float* out, double* saved, void* workspace,
+                                     size_t workspace_bytes, int64_t M, int64_t R, int D, int flags, double c, hypad_stream_t s) {
+  return curv_invalid(c) ? HYPAD_EINVAL : red_fwd(xs, weights, w_count, out, saved, workspace, workspace_bytes, M, R, D, flags, s, curv_of(c));
+}
+int hypad_ball_weighted_midpoint_bwd(const float* xs, const float* weights, int64_t w_count, const double* saved, const float* grad_out,
+                                     float* grad_xs, float* grad_weights, void* workspace, size_t workspace_bytes, int64_t M, int64_t R, int D,
+                                     int flags, double c, hypad_stream_t s) {
+  return curv_invalid(c) ? HYPAD_EINVAL
+                  : red_bwd(xs, weights, w_count, saved, grad_out, grad_xs, grad_weights, workspace, workspace_bytes, M, R, D, flags, s, curv_of(c));
 }
 
 }  // extern "C"

@@ -7,6 +7,7 @@
 // Formulas and clamp constants: /root/reference/math_.py (see oracle/gmath.py, oracle/manual.py which these
 // transcribe line by line).
 #pragma once
+#include <cmath>
 #include <type_traits>
 
 #include "device_utils.h"
@@ -461,6 +462,118 @@ __device__ __forceinline__ void dist_pair_bwd_d(double x2, double y2, double xy,
   const double gu = (u >= DIST_EPS && s <= ARTANH_TOP) ? g / (s * (1.0 - s) * (1.0 + s)) : 0.0;
   a = gu * rden;
   b = draw >= DIST_EPS ? -gu * u * rden : 0.0;
+}
+// The same maps at any negative curvature k = -c (docs/history/curvature_matmul.md): the reference's formulas with its k, not the k = -1
+// maps on scaled operands -- the floors under u, under a length and under den sit on the unscaled quantities.  The kernels of dist.hip,
+// midpoint.hip and attention.hip take the curvature as a trailing pack: empty at k = -1, where every call below resolves to the
+// function above it and curv_mul is the identity, one Curv at k = -c.  With s = sqrt(c):
+//   den = max(1 - 2 c xy + c^2 x2 y2, 1e-15)    u = max(num / den, 1e-15)    out = (2 / s) artanh(min(s sqrt(u), 1 - 1e-7))
+// The backward returns a = dL/dnum and b = c dL/dden, so that dL/dxy = -2 (a + b) as at k = -1 and dL/dx2 = a + b (c y2).
+struct Curv {
+  double c, s, rs;                                               // c, sqrt(c), 1 / sqrt(c)
+};
+// the entry points' rule for c, and the Curv of a valid one (host side)
+inline bool curv_invalid(double c) { return !(c > 0.0) || !std::isfinite(c); }
+inline Curv curv_of(double c) { return Curv{c, std::sqrt(c), 1.0 / std::sqrt(c)}; }
+__device__ __forceinline__ double curv_mul(double v) { return v; }
+__device__ __forceinline__ double curv_mul(double v, const Curv& k) { return k.c * v; }
+__device__ __forceinline__ double dist_pair_d(double x2, double y2, double xy, const Curv& k) {
+  const double cxy = k.c * xy;
+  const double num = x2 - 2.0 * xy + y2, den = fmax(1.0 - 2.0 * cxy + (k.c * x2) * (k.c * y2), DIST_EPS);
+  return 2.0 * k.rs * artanh_clamped_d(k.s * sqrt(fmax(num / den, DIST_EPS)));
+}
+__device__ __forceinline__ void dist_pair_bwd_d(double x2, double y2, double xy, double g, double& a, double& b, const Curv& k) {
+  const double num = x2 - 2.0 * xy + y2, draw = 1.0 - 2.0 * (k.c * xy) + (k.c * x2) * (k.c * y2);
+  const double rden = 1.0 / fmax(draw, DIST_EPS);
+  const double u = num * rden, r = sqrt(fmax(u, DIST_EPS)), z = k.s * r;
+  const double gu = (u >= DIST_EPS && z <= ARTANH_TOP) ? g / (r * (1.0 - z) * (1.0 + z)) : 0.0;
+  a = gu * rden;
+  b = draw >= DIST_EPS ? -k.c * gu * u * rden : 0.0;
+}
+// mobius_scalar_mul: tanh(r artanh(s n)) x / (s n), n = max(|x|, 1e-15); project: onto the radius (1 - 4e-3) / s
+template <class R>
+__device__ __forceinline__ R mobius_scalar_mul_d(double r, const R& x, const Curv& k) {
+  const double sn = k.s * fmax(sqrt(rowd_dot(x, x)), (double)MIN_NORM);
+  const double f = tanh_clamped2_d(r * artanh_clamped_d(sn)) / sn;
+  R o;
+#pragma unroll
+  HYPAD_ROW_EACH o.v[e] = f * x.v[e];
+  return o;
+}
+template <class R>
+__device__ __forceinline__ double mobius_scalar_mul_bwd_d(double r, const R& x, const R& go, R& dx, const Curv& k) {
+  const double raw = sqrt(rowd_dot(x, x));
+  const double n = fmax(raw, (double)MIN_NORM), sn = k.s * n;
+  const double a = artanh_clamped_d(sn), u = r * a;
+  const double t = tanh_clamped2_d(u), tp = tanh_prime2_d(u, t);
+  const double f = t / sn, gs = rowd_dot(go, x);                 // d L / d f
+  const double dfdn = k.s * (tp * r * artanh_prime_d(sn) * sn - t) / (sn * sn);
+  const double c = raw >= (double)MIN_NORM ? gs * dfdn / n : 0.0;
+#pragma unroll
+  HYPAD_ROW_EACH dx.v[e] = f * go.v[e] + c * x.v[e];
+  return gs * tp * a / sn;
+}
+template <class R>
+__device__ __forceinline__ R project_d(const R& x, const Curv& k) {
+  const double n = fmax(sqrt(rowd_dot(x, x)), (double)MIN_NORM), top = (double)BALL_MAXNORM * k.rs;
+  R o = x;
+  if (n > top) {
+    const double sc = top / n;
+#pragma unroll
+    HYPAD_ROW_EACH o.v[e] = x.v[e] * sc;
+  }
+  return o;
+}
+template <class R>
+__device__ __forceinline__ R project_bwd_d(const R& x, const R& go, const Curv& k) {
+  const double raw = sqrt(rowd_dot(x, x));
+  const double n = fmax(raw, (double)MIN_NORM), top = (double)BALL_MAXNORM * k.rs;
+  if (!(n > top)) return go;
+  const double s = raw >= (double)MIN_NORM ? rowd_dot(x, go) / (n * n) : 0.0, sc = top / n;
+  R gx;
+#pragma unroll
+  HYPAD_ROW_EACH gx.v[e] = sc * (go.v[e] - x.v[e] * s);
+  return gx;
+}
+// the midpoint's tail: the halving is t / (1 + sqrt(1 - c |t|^2)), f' = c f^2 / (2 root); den' and its rule are those of k = -1
+template <class R>
+__device__ __forceinline__ R midpoint_tail_d(const R& nom, double den, double r, const MidpointCfg c, const Curv& k) {
+  const double rd = 1.0 / midpoint_den(den, c.clamp_abs);
+  R a;
+#pragma unroll
+  HYPAD_ROW_EACH a.v[e] = nom.v[e] * rd;
+  if (c.halve) {
+    const double f = 1.0 / (1.0 + sqrt(1.0 - k.c * rowd_dot(a, a)));
+#pragma unroll
+    HYPAD_ROW_EACH a.v[e] *= f;
+  }
+  if (c.lincomb) a = mobius_scalar_mul_d(r, a, k);
+  return c.project ? project_d(a, k) : a;
+}
+template <class R>
+__device__ __forceinline__ void midpoint_tail_bwd_d(const R& nom, double den, double r, const MidpointCfg c, const R& go, R& gnom, double& gden,
+                                                    double& gr, const Curv& k) {
+  const double rd = 1.0 / midpoint_den(den, c.clamp_abs);
+  R t, a;
+#pragma unroll
+  HYPAD_ROW_EACH t.v[e] = nom.v[e] * rd;
+  double f = 1.0, root = 1.0;
+  if (c.halve) { root = sqrt(1.0 - k.c * rowd_dot(t, t)); f = 1.0 / (1.0 + root); }
+#pragma unroll
+  HYPAD_ROW_EACH a.v[e] = t.v[e] * f;
+  R g = go;
+  gr = 0.0;
+  if (c.project) g = project_bwd_d(c.lincomb ? mobius_scalar_mul_d(r, a, k) : a, g, k);
+  if (c.lincomb) { R ga; gr = mobius_scalar_mul_bwd_d(r, a, g, ga, k); g = ga; }
+  if (c.halve) {
+    const double s = k.c * rowd_dot(g, t) * f * f / root;
+#pragma unroll
+    HYPAD_ROW_EACH g.v[e] = f * g.v[e] + s * t.v[e];
+  }
+#pragma unroll
+  HYPAD_ROW_EACH gnom.v[e] = g.v[e] * rd;
+  const bool flows = c.clamp_abs ? den > 0.0 : den >= MIDPOINT_DEN_EPS;
+  gden = flows ? -rowd_dot(g, t) * rd : 0.0;
 }
 // dist (:893-902): 2 artanh(|(-x) (+) y|), the norm without a clamp.  Two rows that are equal element by element are at distance 0
 // with gradient 0 (the norm's backward at 0, as torch defines it): decided from the rows themselves, because (-x) (+) x is only zero

@@ -6,6 +6,11 @@ points (csrc/tangent.hip), which take c by value: with s = sqrt(c) the kernels s
 the result before the store, around the same per-row fp64 maps the k = -1 kernels run.  Operand rules and refusals are those of the
 ``gmath`` function of the same name and come before any device call; what ``gmath`` hands to its kernels as a one-row broadcast (the bias
 of mobius_add, the one-row w of mobius_pointwise_mul) is expanded here instead, which leaves the sum of that gradient to autograd.
+
+The matmul forms -- dist_matmul, weighted_midpoint, weighted_midpoint_bmm, hyperbolic_attention -- run the k = -1 kernels of csrc/dist.hip,
+midpoint.hip and attention.hip with c in their fp64 stages (``hypad_ball_dist_matmul_*`` and the like, docs/history/curvature_matmul.md):
+the reference's formulas at k = -c, whose floors sit on the unscaled quantities.  Their operand rules and their autograd functions are
+``gmath``'s own code: those functions take c as an optional last argument and then call the ``hypad_ball_*`` entry of their name.
 """
 import math
 
@@ -121,6 +126,23 @@ class _Projection(torch.autograd.Function):
         ga = torch.empty_like(a)
         _call(ctx.name, "bwd", _C.ptr(a), _C.ptr(_fp32(go)), _C.ptr(ga), gmath._rows_width(a)[0], ctx.ball, ctx.c, _C.stream())
         return None, None, ga, None
+
+
+def dist_matmul(c, x, y):
+    return gmath._dist_matmul(x, y, lambda x3, y3: gmath._DistMatmul.apply(x3, y3, c))
+
+
+def weighted_midpoint_bmm(c, xs, weights, lincomb):
+    return gmath._weighted_midpoint_bmm(xs, weights, lincomb, lambda x3, w3, flags: gmath._WeightedMidpointBmm.apply(x3, w3, flags, c))
+
+
+def weighted_midpoint(c, xs, weights, reducedim, dim, keepdim, lincomb, posweight, coadd):
+    return gmath._weighted_midpoint(xs, weights, reducedim, dim, keepdim, lincomb, posweight, coadd,
+                                    lambda x3, w2, flags: gmath._WeightedMidpoint.apply(x3, w2, flags, c))
+
+
+def hyperbolic_attention(c, q, keys, values, beta, bias):
+    return gmath._hyperbolic_attention(q, keys, values, beta, bias, lambda q3, k3, v3, b, bt: gmath._HyperbolicAttention.apply(q3, k3, v3, b, bt, c))
 
 
 def curvature(ball, what):

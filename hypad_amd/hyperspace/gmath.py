@@ -269,12 +269,19 @@ def mobius_scalar_mul(r, x, *, k=None, dim=-1):
     return _MobiusScalarMul.apply(r, x)
 
 
+def _entry(name, c):
+    """(the entry point ``hypad_<name>`` and nothing, or ``hypad_ball_<name>`` and c): the autograd functions of the matmul forms run at
+    k = -1 (c None) and, for the methods of PoincareBall(c) (hyperspace/ball.py), at k = -c -- the same argument list with c before the stream."""
+    full = ("hypad_" if c is None else "hypad_ball_") + name
+    return getattr(_C.lib, full), (() if c is None else (c,)), full
+
+
 class _WeightedMidpointBmm(torch.autograd.Function):
-    """hypad_weighted_midpoint_bmm_*: xs (batch, M, D), weights (batch, N, M) -> (batch, N, D); saves the operands and
+    """hypad_weighted_midpoint_bmm_* (c given: hypad_ball_weighted_midpoint_bmm_*): xs (batch, M, D), weights (batch, N, M) -> (batch, N, D); saves the operands and
     [nom | den | alpha] (batch, N, D + 2)."""
 
     @staticmethod
-    def forward(ctx, xs, weights, flags):
+    def forward(ctx, xs, weights, flags, c=None):
         xs = _C.require_cuda(xs.contiguous(), "xs")
         weights = _C.require_cuda(weights.contiguous(), "weights")
         batch, m, d = xs.shape
@@ -282,11 +289,11 @@ class _WeightedMidpointBmm(torch.autograd.Function):
         out = torch.empty(batch, n, d, device=xs.device, dtype=torch.float32)
         train = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
         saved = torch.empty(batch, n, d + 2, device=xs.device, dtype=torch.float32) if train else None
-        _C.check(_C.lib.hypad_weighted_midpoint_bmm_fwd(_C.ptr(xs), _C.ptr(weights), _C.ptr(out), _C.ptr(saved), batch, n, m, d, flags, _C.stream()),
-                 "weighted_midpoint_bmm_fwd")
+        fn, cv, name = _entry("weighted_midpoint_bmm_fwd", c)
+        _C.check(fn(_C.ptr(xs), _C.ptr(weights), _C.ptr(out), _C.ptr(saved), batch, n, m, d, flags, *cv, _C.stream()), name)
         if train:
             ctx.save_for_backward(xs, weights, saved)
-        ctx.flags = flags
+        ctx.flags, ctx.c = flags, c
         return out
 
     @staticmethod
@@ -300,9 +307,10 @@ class _WeightedMidpointBmm(torch.autograd.Function):
         gw = torch.empty_like(weights) if ctx.needs_input_grad[1] else None
         nbytes = _C.lib.hypad_weighted_midpoint_bmm_workspace_bytes(batch, n, m, d)
         ws = torch.empty(max(nbytes // 4, 1), device=xs.device, dtype=torch.float32)
-        _C.check(_C.lib.hypad_weighted_midpoint_bmm_bwd(_C.ptr(xs), _C.ptr(weights), _C.ptr(saved), _C.ptr(go), _C.ptr(gx), _C.ptr(gw), _C.ptr(ws),
-                                                        nbytes, batch, n, m, d, ctx.flags, _C.stream()), "weighted_midpoint_bmm_bwd")
-        return gx, gw, None
+        fn, cv, name = _entry("weighted_midpoint_bmm_bwd", ctx.c)
+        _C.check(fn(_C.ptr(xs), _C.ptr(weights), _C.ptr(saved), _C.ptr(go), _C.ptr(gx), _C.ptr(gw), _C.ptr(ws), nbytes, batch, n, m, d, ctx.flags, *cv,
+                    _C.stream()), name)
+        return gx, gw, None, None
 
 
 _BMM_SUPPORTED = ("supported: k = -1, fp32, xs (..., M, D) against weights (..., N, M) with the same leading batch dimensions on both, or "
@@ -317,6 +325,12 @@ def weighted_midpoint_bmm(xs, weights, k, lincomb=False):
     to autograd (the expand's backward)."""
     if k is not None and abs(float(k) + 1.0) > 1e-12:
         raise NotImplementedError(f"weighted_midpoint_bmm: curvature k = {float(k)} is not implemented; {_BMM_SUPPORTED}")
+    return _weighted_midpoint_bmm(xs, weights, lincomb, _WeightedMidpointBmm.apply)
+
+
+def _weighted_midpoint_bmm(xs, weights, lincomb, apply):
+    """The operand rules of weighted_midpoint_bmm, then ``apply(xs3, weights3, flags)``: the k = -1 autograd function, or the one of
+    PoincareBall(c) (hyperspace/ball.py)."""
     bx, bw = tuple(xs.shape[:-2]), tuple(weights.shape[:-2])
     if (xs.dim() < 2 or weights.dim() < 2 or weights.shape[-1] != xs.shape[-2] or (bx != bw and bx != () and bw != ())
             or xs.dtype != torch.float32 or weights.dtype != torch.float32):
@@ -329,16 +343,16 @@ def weighted_midpoint_bmm(xs, weights, k, lincomb=False):
         xs = xs.expand(*lead, *xs.shape[-2:])
     if bw != lead:
         weights = weights.expand(*lead, *weights.shape[-2:])
-    out = _WeightedMidpointBmm.apply(xs.reshape(-1, *xs.shape[-2:]), weights.reshape(-1, *weights.shape[-2:]), _C.MID_LINCOMB if lincomb else 0)
+    out = apply(xs.reshape(-1, *xs.shape[-2:]), weights.reshape(-1, *weights.shape[-2:]), _C.MID_LINCOMB if lincomb else 0)
     return out.view(*lead, weights.shape[-2], xs.shape[-1])
 
 
 class _WeightedMidpoint(torch.autograd.Function):
-    """hypad_weighted_midpoint_*: xs (M, R, D), weights (M, R), of one element, or None -> (R, D); saves the operands and
+    """hypad_weighted_midpoint_* (c given: hypad_ball_weighted_midpoint_*): xs (M, R, D), weights (M, R), of one element, or None -> (R, D); saves the operands and
     [nom | den | alpha] (R, D + 2) in fp64."""
 
     @staticmethod
-    def forward(ctx, xs, weights, flags):
+    def forward(ctx, xs, weights, flags, c=None):
         xs = _C.require_cuda(xs.contiguous(), "xs")
         m, r, d = xs.shape
         w = None if weights is None else _C.require_cuda(weights.contiguous().reshape(-1), "weights")
@@ -348,11 +362,11 @@ class _WeightedMidpoint(torch.autograd.Function):
         saved = torch.empty(r, d + 2, device=xs.device, dtype=torch.float64) if train else None
         nbytes = _C.lib.hypad_weighted_midpoint_workspace_bytes(m, r, d)
         ws = torch.empty(max(nbytes // 4, 1), device=xs.device, dtype=torch.float32)
-        _C.check(_C.lib.hypad_weighted_midpoint_fwd(_C.ptr(xs), _C.ptr(w), wn, _C.ptr(out), _C.ptr(saved), _C.ptr(ws), nbytes, m, r, d, flags,
-                                                    _C.stream()), "weighted_midpoint_fwd")
+        fn, cv, name = _entry("weighted_midpoint_fwd", c)
+        _C.check(fn(_C.ptr(xs), _C.ptr(w), wn, _C.ptr(out), _C.ptr(saved), _C.ptr(ws), nbytes, m, r, d, flags, *cv, _C.stream()), name)
         if train:
             ctx.save_for_backward(xs, saved, *(() if w is None else (w,)))
-        ctx.flags, ctx.wshape = flags, None if weights is None else weights.shape
+        ctx.flags, ctx.wshape, ctx.c = flags, None if weights is None else weights.shape, c
         return out
 
     @staticmethod
@@ -366,9 +380,10 @@ class _WeightedMidpoint(torch.autograd.Function):
         gw = torch.empty_like(w) if w is not None and ctx.needs_input_grad[1] else None
         nbytes = _C.lib.hypad_weighted_midpoint_workspace_bytes(m, r, d)
         ws = torch.empty(max(nbytes // 4, 1), device=xs.device, dtype=torch.float32)
-        _C.check(_C.lib.hypad_weighted_midpoint_bwd(_C.ptr(xs), _C.ptr(w), 0 if w is None else w.shape[0], _C.ptr(saved), _C.ptr(go), _C.ptr(gx),
-                                                    _C.ptr(gw), _C.ptr(ws), nbytes, m, r, d, ctx.flags, _C.stream()), "weighted_midpoint_bwd")
-        return gx, None if gw is None else gw.view(ctx.wshape), None
+        fn, cv, name = _entry("weighted_midpoint_bwd", ctx.c)
+        _C.check(fn(_C.ptr(xs), _C.ptr(w), 0 if w is None else w.shape[0], _C.ptr(saved), _C.ptr(go), _C.ptr(gx), _C.ptr(gw), _C.ptr(ws), nbytes, m, r,
+                    d, ctx.flags, *cv, _C.stream()), name)
+        return gx, None if gw is None else gw.view(ctx.wshape), None, None
 
 
 _MID_SUPPORTED = ("supported: k = -1, dim = -1, fp32, reducedim among the dimensions of xs before the last, weights None, of one element, or "
@@ -383,6 +398,12 @@ def weighted_midpoint(xs, k, weights=None, reducedim=None, dim=-1, keepdim=False
     that broadcast against xs.shape[:-1] are expanded and materialised, which leaves the sum of their gradient to autograd."""
     if k is not None and abs(float(k) + 1.0) > 1e-12:
         raise NotImplementedError(f"weighted_midpoint: curvature k = {float(k)} is not implemented; {_MID_SUPPORTED}")
+    return _weighted_midpoint(xs, weights, reducedim, dim, keepdim, lincomb, posweight, coadd, _WeightedMidpoint.apply)
+
+
+def _weighted_midpoint(xs, weights, reducedim, dim, keepdim, lincomb, posweight, coadd, apply):
+    """The operand rules of weighted_midpoint, then ``apply(xs3, weights2, flags)``: the k = -1 autograd function, or the one of
+    PoincareBall(c) (hyperspace/ball.py)."""
     if xs.dim() < 1 or (dim != -1 and dim != xs.dim() - 1):
         raise NotImplementedError(f"weighted_midpoint: dim = {dim} on xs {tuple(xs.shape)} is not implemented; {_MID_SUPPORTED}")
     nd = xs.dim() - 1
@@ -419,23 +440,25 @@ def weighted_midpoint(xs, k, weights=None, reducedim=None, dim=-1, keepdim=False
     if weights is not None and weights.numel() != 1:
         w2 = weights.expand(lead).permute(*order).reshape(m, r)
     flags = (_C.MID_LINCOMB if lincomb else 0) | (_C.MID_POSWEIGHT if posweight else 0) | (_C.MID_COADD if coadd else 0)
-    out = _WeightedMidpoint.apply(x3, w2, flags)
+    out = apply(x3, w2, flags)
     shape = [1 if a in red else xs.shape[a] for a in range(nd)] if keepdim else [xs.shape[a] for a in kept]
     return out.view(*shape, xs.shape[-1])
 
 
 class _DistMatmul(torch.autograd.Function):
-    """hypad_dist_matmul_*: x (batch, N, D), y (batch, M, D) -> (batch, N, M); saves the operands alone."""
+    """hypad_dist_matmul_* (c given: hypad_ball_dist_matmul_*): x (batch, N, D), y (batch, M, D) -> (batch, N, M); saves the operands alone."""
 
     @staticmethod
-    def forward(ctx, x, y):
+    def forward(ctx, x, y, c=None):
         x = _C.require_cuda(x.contiguous(), "x")
         y = _C.require_cuda(y.contiguous(), "y")
         batch, n, d = x.shape
         m = y.shape[1]
         out = torch.empty(batch, n, m, device=x.device, dtype=torch.float32)
-        _C.check(_C.lib.hypad_dist_matmul_fwd(_C.ptr(x), _C.ptr(y), _C.ptr(out), batch, n, m, d, _C.stream()), "dist_matmul_fwd")
+        fn, cv, name = _entry("dist_matmul_fwd", c)
+        _C.check(fn(_C.ptr(x), _C.ptr(y), _C.ptr(out), batch, n, m, d, *cv, _C.stream()), name)
         ctx.save_for_backward(x, y)
+        ctx.c = c
         return out
 
     @staticmethod
@@ -446,9 +469,9 @@ class _DistMatmul(torch.autograd.Function):
         go = go.to(torch.float32).contiguous()
         gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         gy = torch.empty_like(y) if ctx.needs_input_grad[1] else None
-        _C.check(_C.lib.hypad_dist_matmul_bwd(_C.ptr(x), _C.ptr(y), _C.ptr(go), _C.ptr(gx), _C.ptr(gy), batch, n, y.shape[1], d, _C.stream()),
-                 "dist_matmul_bwd")
-        return gx, gy
+        fn, cv, name = _entry("dist_matmul_bwd", ctx.c)
+        _C.check(fn(_C.ptr(x), _C.ptr(y), _C.ptr(go), _C.ptr(gx), _C.ptr(gy), batch, n, y.shape[1], d, *cv, _C.stream()), name)
+        return gx, gy, None
 
 
 _DISTMM_SUPPORTED = ("supported: k = -1, fp32, x (..., N, D) against y (..., D, M) with the same leading batch dimensions on both, or none on one "
@@ -464,6 +487,12 @@ def dist_matmul(x, y, k):
     its gradient over the batch is left to autograd (the expand's backward)."""
     if k is not None and abs(float(k) + 1.0) > 1e-12:
         raise NotImplementedError(f"dist_matmul: curvature k = {float(k)} is not implemented; {_DISTMM_SUPPORTED}")
+    return _dist_matmul(x, y, _DistMatmul.apply)
+
+
+def _dist_matmul(x, y, apply):
+    """The operand rules of dist_matmul, then ``apply(x3, y3)``: the k = -1 autograd function, or the one of PoincareBall(c)
+    (hyperspace/ball.py)."""
     bx, by = tuple(x.shape[:-2]), tuple(y.shape[:-2])
     if (x.dim() < 2 or y.dim() < 2 or y.shape[-2] != x.shape[-1] or (bx != by and bx != () and by != ())
             or x.dtype != torch.float32 or y.dtype != torch.float32):
@@ -477,7 +506,7 @@ def dist_matmul(x, y, k):
         raise NotImplementedError(f"dist_matmul: x {tuple(x.shape)} against y {tuple(y.shape)} is not implemented; {_DISTMM_SUPPORTED}")
     yt = y.transpose(-1, -2)                                 # (..., M, D): contiguous already in the usual call
     x3, (y3,) = _over_batch(lead, x, (yt,))
-    out = _DistMatmul.apply(x3, y3)
+    out = apply(x3, y3)
     return out.view(*lead, x.shape[-2], yt.shape[-2])
 
 
@@ -635,11 +664,11 @@ def dist0(x, *, k, keepdim=False, dim=-1):
 
 
 class _HyperbolicAttention(torch.autograd.Function):
-    """hypad_hyp_attention_*: q (batch, N, D), keys (batch, M, D), values (batch, M, E), bias None, (N, M) or (batch, N, M) ->
+    """hypad_hyp_attention_* (c given: hypad_ball_hyp_attention_*): q (batch, N, D), keys (batch, M, D), values (batch, M, E), bias None, (N, M) or (batch, N, M) ->
     (batch, N, E); saves the operands, [nom | den] (batch, N, E + 1) and L (batch, N) -- nothing of size N x M."""
 
     @staticmethod
-    def forward(ctx, q, keys, values, bias, beta):
+    def forward(ctx, q, keys, values, bias, beta, c=None):
         q = _C.require_cuda(q.contiguous(), "q")
         keys = _C.require_cuda(keys.contiguous(), "keys")
         values = _C.require_cuda(values.contiguous(), "values")
@@ -652,11 +681,12 @@ class _HyperbolicAttention(torch.autograd.Function):
         train = any(ctx.needs_input_grad[:3])
         saved = torch.empty(batch, n, e + 1, device=q.device, dtype=torch.float32) if train else None
         lse = torch.empty(batch, n, device=q.device, dtype=torch.float32) if train else None
-        _C.check(_C.lib.hypad_hyp_attention_fwd(_C.ptr(q), _C.ptr(keys), _C.ptr(values), _C.ptr(bias), stride, beta, _C.ptr(out), _C.ptr(saved),
-                                                _C.ptr(lse), batch, n, m, d, e, _C.stream()), "hyp_attention_fwd")
+        fn, cv, name = _entry("hyp_attention_fwd", c)
+        _C.check(fn(_C.ptr(q), _C.ptr(keys), _C.ptr(values), _C.ptr(bias), stride, beta, _C.ptr(out), _C.ptr(saved), _C.ptr(lse), batch, n, m, d, e, *cv,
+                    _C.stream()), name)
         if train:
             ctx.save_for_backward(q, keys, values, saved, lse, *(() if bias is None else (bias,)))
-        ctx.beta, ctx.stride = beta, stride
+        ctx.beta, ctx.stride, ctx.c = beta, stride, c
         return out
 
     @staticmethod
@@ -672,10 +702,10 @@ class _HyperbolicAttention(torch.autograd.Function):
         gv = torch.empty_like(values) if ctx.needs_input_grad[2] else None
         nbytes = _C.lib.hypad_hyp_attention_workspace_bytes(batch, n, m, d, e)
         ws = torch.empty(max(nbytes // 4, 1), device=q.device, dtype=torch.float32)
-        _C.check(_C.lib.hypad_hyp_attention_bwd(_C.ptr(q), _C.ptr(keys), _C.ptr(values), _C.ptr(bias), ctx.stride, ctx.beta, _C.ptr(saved),
-                                                _C.ptr(lse), _C.ptr(go), _C.ptr(gq), _C.ptr(gk), _C.ptr(gv), _C.ptr(ws), nbytes, batch, n, m, d, e,
-                                                _C.stream()), "hyp_attention_bwd")
-        return gq, gk, gv, None, None
+        fn, cv, name = _entry("hyp_attention_bwd", ctx.c)
+        _C.check(fn(_C.ptr(q), _C.ptr(keys), _C.ptr(values), _C.ptr(bias), ctx.stride, ctx.beta, _C.ptr(saved), _C.ptr(lse), _C.ptr(go), _C.ptr(gq),
+                    _C.ptr(gk), _C.ptr(gv), _C.ptr(ws), nbytes, batch, n, m, d, e, *cv, _C.stream()), name)
+        return gq, gk, gv, None, None, None
 
 
 _ATTN_SUPPORTED = ("supported: k = -1, fp32, q (..., N, D), keys (..., M, D) and values (..., M, E) with the same leading batch dimensions, or "
@@ -702,6 +732,12 @@ def hyperbolic_attention(q, keys, values, k, beta=1.0, bias=None):
     adds nothing to any gradient; the composition returns NaN there."""
     if k is not None and abs(float(k) + 1.0) > 1e-12:
         raise NotImplementedError(f"hyperbolic_attention: curvature k = {float(k)} is not implemented; {_ATTN_SUPPORTED}")
+    return _hyperbolic_attention(q, keys, values, beta, bias, _HyperbolicAttention.apply)
+
+
+def _hyperbolic_attention(q, keys, values, beta, bias, apply):
+    """The operand rules of hyperbolic_attention, then ``apply(q3, keys3, values3, bias, beta)``: the k = -1 autograd function, or the one
+    of PoincareBall(c) (hyperspace/ball.py)."""
     if isinstance(beta, torch.Tensor):
         if beta.numel() != 1 or beta.requires_grad:
             raise NotImplementedError(f"hyperbolic_attention: beta {tuple(beta.shape)} requires_grad={beta.requires_grad} is not implemented; "
@@ -731,7 +767,7 @@ def hyperbolic_attention(q, keys, values, k, beta=1.0, bias=None):
                                       f"{desc} is not implemented; {_ATTN_SUPPORTED}")
         bias = bias if bias.dim() == 2 else bias.reshape(nb, n, m)
     q3, k3, v3 = (t.expand(*lead, *t.shape[-2:]).reshape(nb, *t.shape[-2:]) for t in ops)
-    out = _HyperbolicAttention.apply(q3, k3, v3, bias, beta)
+    out = apply(q3, k3, v3, bias, beta)
     return out.view(*lead, n, e)
 
 

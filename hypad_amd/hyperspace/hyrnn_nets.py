@@ -22,19 +22,21 @@ class PoincareBall:
     """The Poincare ball of curvature k = -c (the reference's geoopt.PoincareBall(c)): the tag of ball-valued parameters, and the
     object through which the 25 row-wise functions of math_.py and ``antipode`` are reached with k = -c bound -- ``ball.expmap(x, u)``,
     ``ball.dist(x, y)``, ``ball.transp(x, y, v)`` -- under the names of math_.py and geoopt's aliases ``projx``, ``transp``, ``transp0``
-    and ``transp0back``.
+    and ``transp0back``; and ``dist_matmul``, ``weighted_midpoint``, ``weighted_midpoint_bmm`` and ``hyperbolic_attention``, the k = -1
+    kernels with c in their fp64 stages (docs/history/curvature_matmul.md).
 
     Each method takes the operands of the ``gmath`` function of its name without ``k`` and applies that function's operand rules and
-    refusals before any device call.  At c == 1 it calls that function, so its bits are ``gmath``'s; at any other finite c > 0 it runs
-    the ``hypad_ball_*`` kernels, one HIP launch forward and one backward, a wave per row in fp64 registers (hyperspace/ball.py,
+    refusals before any device call.  The refusals are ``gmath``'s own and carry its text, "supported: k = -1, ...": read through a ball
+    of another c, everything after "k = -1" in that list is the rule here too, and the curvature is the ball's.  At c == 1 a method
+    calls that function, so its bits are ``gmath``'s; at any other finite c > 0 it runs the ``hypad_ball_*`` kernels, one HIP launch forward and one backward, a wave per row in fp64 registers (hyperspace/ball.py,
     docs/history/curvature.md).  c <= 0, a c that is not finite and a c that requires grad raise NotImplementedError.  c is read on
     the host from the tensor stored here: nothing waits for the device, the launches go to the current stream and can be captured
     under ``torch.cuda.graph`` (a replay uses the c it was captured with).
 
     The methods are the functions of math_.py and nothing more: unlike geoopt's manifold class none of them projects its result back
     into the ball implicitly (geoopt's ``expmap(..., project=True)``, ``mobius_add(..., project=True)``); call ``project`` where it is
-    wanted.  The layers, the matmul forms (dist_matmul, dist2plane, weighted_midpoint, hyperbolic_attention) and the optimisers stay
-    at c = 1."""
+    wanted (weighted_midpoint_bmm and hyperbolic_attention project because the reference's functions do).  dist2plane,
+    dist2plane_matmul, the Moebius layers and GRU, and the optimisers stay at c = 1."""
 
     def __init__(self, c=1.0):
         self.c = torch.tensor(float(c))
@@ -210,6 +212,40 @@ class PoincareBall:
         from . import ball, gmath
         c = self._c("inner")
         return gmath.inner(x, u, v, k=-1.0, keepdim=keepdim, dim=dim) if c == 1.0 else ball.per_row("inner", c, keepdim, dim, x=x, u=u, v=v)
+
+    # ---- the matmul forms and what is built on them (docs/history/curvature_matmul.md)
+    def dist_matmul(self, x, y):
+        """The geodesic distance at curvature -c of every point of x (..., N, D) from every point of y (..., D, M) -> (..., N, M)
+        (math_.py:905-947); a coincident pair is at (2 / sqrt(c)) artanh(sqrt(c) sqrt(1e-15)) = 6.3e-8, the reference's floor."""
+        from . import ball, gmath
+        c = self._c("dist_matmul")
+        return gmath.dist_matmul(x, y, -1.0) if c == 1.0 else ball.dist_matmul(c, x, y)
+
+    def weighted_midpoint(self, xs, weights=None, reducedim=None, dim=-1, keepdim=False, lincomb=False, posweight=False, coadd=False):
+        """The weighted gyromidpoint at curvature -c of the points of xs (..., D) over ``reducedim`` (math_.py:1953-2087): the pooling
+        form, which does not project."""
+        from . import ball, gmath
+        c = self._c("weighted_midpoint")
+        if c == 1.0:
+            return gmath.weighted_midpoint(xs, -1.0, weights, reducedim, dim, keepdim, lincomb, posweight, coadd)
+        return ball.weighted_midpoint(c, xs, weights, reducedim, dim, keepdim, lincomb, posweight, coadd)
+
+    def weighted_midpoint_bmm(self, xs, weights, lincomb=False):
+        """The weighted gyromidpoint at curvature -c of xs (..., M, D) under every row of weights (..., N, M) -> (..., N, D)
+        (math_.py:2090-2122), projected onto the radius (1 - 4e-3) / sqrt(c)."""
+        from . import ball, gmath
+        c = self._c("weighted_midpoint_bmm")
+        return gmath.weighted_midpoint_bmm(xs, weights, -1.0, lincomb) if c == 1.0 else ball.weighted_midpoint_bmm(c, xs, weights, lincomb)
+
+    def hyperbolic_attention(self, q, keys, values, beta=1.0, bias=None):
+        """Per query of q (..., N, D) the gyromidpoint of values (..., M, E) under softmax_j(-beta d_c(q_i, keys_j) + bias_ij), all at
+        curvature -c, -> (..., N, E): ``gmath.hyperbolic_attention`` with k = -c, no (N, M) tensor in memory.  A fully masked query gives
+        the origin."""
+        from . import ball, gmath
+        c = self._c("hyperbolic_attention")
+        if c == 1.0:
+            return gmath.hyperbolic_attention(q, keys, values, -1.0, beta, bias)
+        return ball.hyperbolic_attention(c, q, keys, values, beta, bias)
 
     # geoopt's names
     projx = project

@@ -452,6 +452,43 @@ int hypad_hyp_attention_bwd(const float* q, const float* keys, const float* valu
                             double beta, const float* saved, const float* lse, const float* grad_out, float* grad_q, float* grad_keys,
                             float* grad_values, void* workspace, size_t workspace_bytes, int64_t batch, int64_t N, int64_t M, int D, int E,
                             hypad_stream_t stream);
+/* dist_matmul, weighted_midpoint_bmm, weighted_midpoint and the attention above at any negative curvature k = -c, c > 0 and finite: what
+ * the matmul methods of hyrnn_nets.PoincareBall(c) run (docs/history/curvature_matmul.md).  Each has the arguments of the entry point
+ * hypad_<name>_* plus `c` before the stream, the same kernels with c in their fp64 stages only (no operand tile is scaled), the same
+ * validation and return codes after HYPAD_EINVAL for a c that is not finite and positive -- c is checked first --, and the same
+ * workspace: the hypad_*_workspace_bytes functions above serve both.  With s = sqrt(c), the reference's formulas at k = -c:
+ *   dist_matmul   num = x2 - 2 xy + y2    den = max(1 - 2 c xy + c^2 x2 y2, 1e-15)    u = max(num / den, 1e-15)
+ *                 out = (2 / s) artanh(min(s sqrt(u), 1 - 1e-7))
+ *   midpoints     gamma_j = 2 / max(1 - c |x_j|^2, 1e-15);  nom, den, alpha and den' (its 1e-10) as at k = -1;  t = nom / den'
+ *                 a = t / (1 + sqrt(1 - c |t|^2))    lincomb: a = tanh(r artanh(s |a|)) a / (s |a|), r = alpha (bmm), alpha / 2 (reduce)
+ *                 bmm and attention: project onto the radius (1 - 4e-3) / s;  the reduce form does not project
+ *   attention     softmax_j(-beta d_c(q_i, keys_j) + bias_ij), then the bmm midpoint of the values without lincomb; a fully masked row
+ *                 gives the origin and adds nothing to any gradient
+ * The floors 1e-15 under u, under a length and under 1 - c |x|^2 sit on the unscaled quantities, so these are not everywhere the k = -1
+ * functions on operands times s: a coincident pair is at distance (2 / s) artanh(s sqrt(1e-15)) = 6.3e-8 for every c.  Where a clamp holds
+ * nothing flows back through it, as at k = -1.  c = 1.0 is within rounding of hypad_<name>_*, not its bits. */
+int hypad_ball_dist_matmul_fwd(const float* x, const float* y, float* out, int64_t batch, int64_t N, int64_t M, int D, double c,
+                               hypad_stream_t stream);
+int hypad_ball_dist_matmul_bwd(const float* x, const float* y, const float* grad_out, float* grad_x, float* grad_y, int64_t batch, int64_t N,
+                               int64_t M, int D, double c, hypad_stream_t stream);
+int hypad_ball_weighted_midpoint_bmm_fwd(const float* xs, const float* weights, float* out, float* saved /* NULL: inference */, int64_t batch,
+                                         int64_t N, int64_t M, int D, int flags, double c, hypad_stream_t stream);
+int hypad_ball_weighted_midpoint_bmm_bwd(const float* xs, const float* weights, const float* saved, const float* grad_out, float* grad_xs,
+                                         float* grad_weights, void* workspace, size_t workspace_bytes, int64_t batch, int64_t N, int64_t M,
+                                         int D, int flags, double c, hypad_stream_t stream);
+int hypad_ball_weighted_midpoint_fwd(const float* xs, const float* weights /* NULL: none */, int64_t w_count, float* out,
+                                     double* saved /* NULL: inference */, void* workspace, size_t workspace_bytes, int64_t M, int64_t R, int D,
+                                     int flags, double c, hypad_stream_t stream);
+int hypad_ball_weighted_midpoint_bwd(const float* xs, const float* weights, int64_t w_count, const double* saved, const float* grad_out,
+                                     float* grad_xs, float* grad_weights, void* workspace, size_t workspace_bytes, int64_t M, int64_t R, int D,
+                                     int flags, double c, hypad_stream_t stream);
+int hypad_ball_hyp_attention_fwd(const float* q, const float* keys, const float* values, const float* bias /* NULL: none */,
+                                 int64_t bias_batch_stride, double beta, float* out, float* saved /* NULL: inference */, float* lse,
+                                 int64_t batch, int64_t N, int64_t M, int D, int E, double c, hypad_stream_t stream);
+int hypad_ball_hyp_attention_bwd(const float* q, const float* keys, const float* values, const float* bias, int64_t bias_batch_stride,
+                                 double beta, const float* saved, const float* lse, const float* grad_out, float* grad_q, float* grad_keys,
+                                 float* grad_values, void* workspace, size_t workspace_bytes, int64_t batch, int64_t N, int64_t M, int D, int E,
+                                 double c, hypad_stream_t stream);
 /* The Moebius GRU hyperspace/hyrnn_nets.py:61-151 (one_rnn_transform :61-65, mobius_gru_cell :68-91, the equal-length branch of
  * mobius_gru_loop :113-127) at k = -1.  x (steps, rows, in_dim) and h0 (rows, hidden) on the ball, w_ih (3 hidden, in_dim),
  * w_hh (3 hidden, hidden), bias (3, hidden) on the ball, chunk order r, h, z; out (steps, rows, hidden) = the hidden state after
