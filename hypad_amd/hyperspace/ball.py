@@ -6,6 +6,8 @@ points (csrc/tangent.hip), which take c by value: with s = sqrt(c) the kernels s
 the result before the store, around the same per-row fp64 maps the k = -1 kernels run.  Operand rules and refusals are those of the
 ``gmath`` function of the same name and come before any device call; what ``gmath`` hands to its kernels as a one-row broadcast (the bias
 of mobius_add, the one-row w of mobius_pointwise_mul) is expanded here instead, which leaves the sum of that gradient to autograd.
+The autograd functions are ``gmath``'s -- ``_RowMap``, ``_TimeRowMap``, ``_RowScalar`` and ``_Projection`` with c in place of None
+(docs/history/row_plumbing.md); this module holds the operand rules alone.
 
 The matmul forms -- dist_matmul, weighted_midpoint, weighted_midpoint_bmm, hyperbolic_attention -- run the k = -1 kernels of csrc/dist.hip,
 midpoint.hip and attention.hip with c in their fp64 stages (``hypad_ball_dist_matmul_*`` and the like, docs/history/curvature_matmul.md):
@@ -18,114 +20,6 @@ import torch
 
 from .. import _C
 from . import gmath
-
-
-def _call(name, direction, *args):
-    entry = f"hypad_ball_{name}_{direction}"
-    _C.check(getattr(_C.lib, entry)(*args), entry)
-
-
-def _fp32(go):
-    return go.to(torch.float32).contiguous()
-
-
-class _Rows(torch.autograd.Function):
-    """hypad_ball_<name>_*: one to three operands of one shape (..., D) -> (..., D); saves the operands alone."""
-
-    @staticmethod
-    def forward(ctx, name, c, *ops):
-        ops = [_C.require_cuda(t.contiguous(), f"{name}: operand {i}") for i, t in enumerate(ops)]
-        rows, d = gmath._rows_width(ops[0])
-        out = torch.empty_like(ops[0])
-        _call(name, "fwd", *map(_C.ptr, ops), _C.ptr(out), rows, d, c, _C.stream())
-        ctx.save_for_backward(*ops)
-        ctx.name, ctx.c = name, c
-        return out
-
-    @staticmethod
-    @_C.first_order_only
-    def backward(ctx, go):
-        ops = ctx.saved_tensors
-        rows, d = gmath._rows_width(ops[0])
-        grads = [torch.empty_like(t) if need else None for t, need in zip(ops, ctx.needs_input_grad[2:])]
-        _call(ctx.name, "bwd", *map(_C.ptr, ops), _C.ptr(_fp32(go)), *map(_C.ptr, grads), rows, d, ctx.c, _C.stream())
-        return (None, None, *grads)
-
-
-class _TimeRows(torch.autograd.Function):
-    """hypad_ball_<name>_* for geodesic, geodesic_unit (two row operands) and mobius_scalar_mul (one): t of one element, or of one element
-    per row."""
-
-    @staticmethod
-    def forward(ctx, name, c, t, *ops):
-        ops = [_C.require_cuda(a.contiguous(), f"{name}: row operand {i}") for i, a in enumerate(ops)]
-        t1 = _C.require_cuda(t.contiguous().reshape(-1), "t")
-        rows, d = gmath._rows_width(ops[0])
-        out = torch.empty_like(ops[0])
-        _call(name, "fwd", _C.ptr(t1), *map(_C.ptr, ops), _C.ptr(out), rows, d, t1.shape[0], c, _C.stream())
-        ctx.save_for_backward(t1, *ops)
-        ctx.name, ctx.c, ctx.ts = name, c, t.shape
-        return out
-
-    @staticmethod
-    @_C.first_order_only
-    def backward(ctx, go):
-        t1, *ops = ctx.saved_tensors
-        rows, d = gmath._rows_width(ops[0])
-        gt = torch.empty(rows, device=ops[0].device, dtype=torch.float32) if ctx.needs_input_grad[2] else None
-        grads = [torch.empty_like(a) if need else None for a, need in zip(ops, ctx.needs_input_grad[3:])]
-        _call(ctx.name, "bwd", _C.ptr(t1), *map(_C.ptr, ops), _C.ptr(_fp32(go)), _C.ptr(gt), *map(_C.ptr, grads), rows, d, t1.shape[0], ctx.c,
-              _C.stream())
-        if gt is not None and t1.shape[0] == 1 and rows != 1:   # one t for every row: the rows' contributions, added in a fixed order
-            gt = gmath._column_sum(gt.view(rows, 1))
-        return (None, None, None if gt is None else gt.view(ctx.ts), *grads)
-
-
-class _RowScalar(torch.autograd.Function):
-    """hypad_ball_<name>_* for lambda_x, norm, inner, dist and dist0: operands of one shape (..., D) -> (...), one value per row."""
-
-    @staticmethod
-    def forward(ctx, name, c, *ops):
-        ops = [_C.require_cuda(t.contiguous(), f"{name}: operand {i}") for i, t in enumerate(ops)]
-        rows, d = gmath._rows_width(ops[0])
-        out = torch.empty(ops[0].shape[:-1], device=ops[0].device, dtype=torch.float32)
-        _call(name, "fwd", *map(_C.ptr, ops), _C.ptr(out), rows, d, c, _C.stream())
-        ctx.save_for_backward(*ops)
-        ctx.name, ctx.c = name, c
-        return out
-
-    @staticmethod
-    @_C.first_order_only
-    def backward(ctx, go):
-        ops = ctx.saved_tensors
-        rows, d = gmath._rows_width(ops[0])
-        grads = [torch.empty_like(t) if need else None for t, need in zip(ops, ctx.needs_input_grad[2:])]
-        _call(ctx.name, "bwd", *map(_C.ptr, ops), _C.ptr(_fp32(go)), *map(_C.ptr, grads), rows, d, ctx.c, _C.stream())
-        return (None, None, *grads)
-
-
-class _Projection(torch.autograd.Function):
-    """hypad_ball_sproj_* (grow = -1) and hypad_ball_inv_sproj_* (grow = +1): a (..., W) -> (..., W + grow); the entry points take the
-    ball's width."""
-
-    @staticmethod
-    def forward(ctx, name, c, a, grow):
-        a = _C.require_cuda(a.contiguous(), name)
-        rows, w = gmath._rows_width(a)
-        ball = w if grow > 0 else w - 1
-        out = torch.empty(*a.shape[:-1], w + grow, device=a.device, dtype=torch.float32)
-        _call(name, "fwd", _C.ptr(a), _C.ptr(out), rows, ball, c, _C.stream())
-        ctx.save_for_backward(a)
-        ctx.name, ctx.c, ctx.ball = name, c, ball
-        return out
-
-    @staticmethod
-    @_C.first_order_only
-    def backward(ctx, go):
-        (a,) = ctx.saved_tensors
-        ga = torch.empty_like(a)
-        _call(ctx.name, "bwd", _C.ptr(a), _C.ptr(_fp32(go)), _C.ptr(ga), gmath._rows_width(a)[0], ctx.ball, ctx.c, _C.stream())
-        return None, None, ga, None
 
 
 def dist_matmul(c, x, y):
@@ -180,7 +74,7 @@ def cast_rows(what, dim, **ops):
 
 def unary(name, c, x, dim):
     (x,) = cast_rows(name, dim, x=x)
-    return _Rows.apply(name, c, x)
+    return gmath._RowMap.apply(name, c, x)
 
 
 def mobius_add(c, x, y, dim):
@@ -189,7 +83,7 @@ def mobius_add(c, x, y, dim):
         x, y = torch.broadcast_tensors(x, y)
     except RuntimeError:
         raise _C.HypadError(f"mobius_add: x {tuple(x.shape)} and y {tuple(y.shape)} do not broadcast against each other") from None
-    return _Rows.apply("mobius_add", c, x, y)
+    return gmath._RowMap.apply("mobius_add", c, x, y)
 
 
 def mobius_pointwise_mul(c, w, x, dim):
@@ -199,7 +93,7 @@ def mobius_pointwise_mul(c, w, x, dim):
     if dim != -1 and dim != x.dim() - 1:
         raise NotImplementedError(f"mobius_pointwise_mul: dim = {dim} is not implemented; {_ROWS_SUPPORTED}")
     w, x = cast_rows("mobius_pointwise_mul", -1, w=w, x=x)
-    return _Rows.apply("mobius_pointwise_mul", c, w.reshape(-1).expand(x.shape) if w.shape != x.shape else w, x)
+    return gmath._RowMap.apply("mobius_pointwise_mul", c, w.reshape(-1).expand(x.shape) if w.shape != x.shape else w, x)
 
 
 def mobius_scalar_mul(c, r, x, dim):
@@ -209,35 +103,35 @@ def mobius_scalar_mul(c, r, x, dim):
     if not r.is_floating_point() or (r.numel() != 1 and tuple(r.shape) != tuple(x.shape[:-1]) + (1,)):
         raise NotImplementedError(f"mobius_scalar_mul: r {tuple(r.shape)} {r.dtype} against x {tuple(x.shape)} is not implemented; supported: r of "
                                   f"one element or of shape x.shape[:-1] + (1,); {_ROWS_SUPPORTED}")
-    return _TimeRows.apply("mobius_scalar_mul", c, r.to(torch.float32), x)
+    return gmath._TimeRowMap.apply("mobius_scalar_mul", c, r.to(torch.float32), x)
 
 
 def rows(name, c, dim, **ops):
-    return _Rows.apply(name, c, *gmath._tangent_operands(name, None, dim, **ops))
+    return gmath._RowMap.apply(name, c, *gmath._tangent_operands(name, None, dim, **ops))
 
 
 def timed(name, c, t, dim, **ops):
     x, y = gmath._tangent_operands(name, None, dim, **ops)
     t, x = gmath._time_operand(name, t, x)
-    return _TimeRows.apply(name, c, t, x, y)
+    return gmath._TimeRowMap.apply(name, c, t, x, y)
 
 
 def per_row(name, c, keepdim, dim, **ops):
-    return gmath._per_row(_RowScalar.apply(name, c, *gmath._tangent_operands(name, None, dim, **ops)), keepdim)
+    return gmath._per_row(gmath._RowScalar.apply(name, c, *gmath._tangent_operands(name, None, dim, **ops)), keepdim)
 
 
 def dist(c, x, y, keepdim, dim):
     gmath._dist_refusals("dist", x, None, dim)
     if y.shape != x.shape or y.dtype != torch.float32:
         raise NotImplementedError(f"dist: y {tuple(y.shape)} {y.dtype} against x {tuple(x.shape)} is not implemented; {gmath._DIST_SUPPORTED}")
-    return gmath._per_row(_RowScalar.apply("dist", c, x, y), keepdim)
+    return gmath._per_row(gmath._RowScalar.apply("dist", c, x, y), keepdim)
 
 
 def dist0(c, x, keepdim, dim):
     gmath._dist_refusals("dist0", x, None, dim)
-    return gmath._per_row(_RowScalar.apply("dist0", c, x), keepdim)
+    return gmath._per_row(gmath._RowScalar.apply("dist0", c, x), keepdim)
 
 
 def projection(name, c, x, dim, grow):
     gmath._projection_refusals(name, x, None, dim, grow)
-    return _Projection.apply(name, c, x, grow)
+    return gmath._Projection.apply(name, c, x, grow)

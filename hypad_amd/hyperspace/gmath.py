@@ -38,6 +38,12 @@ def _check_k(k):
         raise NotImplementedError(_K_MSG)
 
 
+def _refuse_k(what, k, supported):
+    """The refusal of any curvature but k = -1 (None: the default), in the words of the functions after the first generation."""
+    if k is not None and abs(float(k) + 1.0) > 1e-12:
+        raise NotImplementedError(f"{what}: curvature k = {float(k)} is not implemented; {supported}")
+
+
 def _check_last_dim(what, x, dim):
     """The row kernels work along the last dimension alone: any other ``dim`` is refused, not ignored."""
     if dim != -1 and dim != x.dim() - 1:
@@ -208,8 +214,7 @@ def mobius_pointwise_mul(w, x, *, k=None, dim=-1):
     """diag(w) (x) x for ball-valued rows of x (math_.py:1328-1371) at k = -1: one HIP launch forward and one backward, first-order
     differentiable in w and x.  w has the shape of x, or is a single row broadcast over the rows of x.  Floating operands of any dtype
     are cast to fp32 and the result is fp32."""
-    if k is not None and abs(float(k) + 1.0) > 1e-12:
-        raise NotImplementedError(f"mobius_pointwise_mul: curvature k = {float(k)} is not implemented; {_PMUL_SUPPORTED}")
+    _refuse_k("mobius_pointwise_mul", k, _PMUL_SUPPORTED)
     if dim != -1 and dim != x.dim() - 1:
         raise NotImplementedError(f"mobius_pointwise_mul: dim = {dim} is not implemented; {_PMUL_SUPPORTED}")
     one_row = w.dim() >= 1 and w.numel() == w.shape[-1]
@@ -256,8 +261,7 @@ def mobius_scalar_mul(r, x, *, k=None, dim=-1):
     """r (x) x = tanh(r artanh |x|) x / |x| for ball-valued rows of x (math_.py:788-858) at k = -1: one HIP launch forward and one
     backward, first-order differentiable in r and x.  r is a tensor of one element (or a number) or holds one value per row of x,
     shape x.shape[:-1] + (1,).  Floating operands of any dtype are cast to fp32 and the result is fp32."""
-    if k is not None and abs(float(k) + 1.0) > 1e-12:
-        raise NotImplementedError(f"mobius_scalar_mul: curvature k = {float(k)} is not implemented; {_SMUL_SUPPORTED}")
+    _refuse_k("mobius_scalar_mul", k, _SMUL_SUPPORTED)
     if dim != -1 and dim != x.dim() - 1:
         raise NotImplementedError(f"mobius_scalar_mul: dim = {dim} is not implemented; {_SMUL_SUPPORTED}")
     if x.dim() < 1 or x.shape[-1] > 256:
@@ -270,8 +274,9 @@ def mobius_scalar_mul(r, x, *, k=None, dim=-1):
 
 
 def _entry(name, c):
-    """(the entry point ``hypad_<name>`` and nothing, or ``hypad_ball_<name>`` and c): the autograd functions of the matmul forms run at
-    k = -1 (c None) and, for the methods of PoincareBall(c) (hyperspace/ball.py), at k = -c -- the same argument list with c before the stream."""
+    """(the entry point ``hypad_<name>`` and nothing, or ``hypad_ball_<name>`` and c): the autograd functions of the matmul forms and
+    of the row forms (``_row_call``) run at k = -1 (c None) and, for the methods of PoincareBall(c) (hyperspace/ball.py), at k = -c --
+    the same argument list with c before the stream."""
     full = ("hypad_" if c is None else "hypad_ball_") + name
     return getattr(_C.lib, full), (() if c is None else (c,)), full
 
@@ -323,8 +328,7 @@ def weighted_midpoint_bmm(xs, weights, k, lincomb=False):
     MFMA; first-order differentiable in xs and weights.  Both operands carry the same leading batch dimensions, or one of them carries
     none: that operand is expanded over the batch and materialised on the host, and the sum of its gradient over the batch is left
     to autograd (the expand's backward)."""
-    if k is not None and abs(float(k) + 1.0) > 1e-12:
-        raise NotImplementedError(f"weighted_midpoint_bmm: curvature k = {float(k)} is not implemented; {_BMM_SUPPORTED}")
+    _refuse_k("weighted_midpoint_bmm", k, _BMM_SUPPORTED)
     return _weighted_midpoint_bmm(xs, weights, lincomb, _WeightedMidpointBmm.apply)
 
 
@@ -396,8 +400,7 @@ def weighted_midpoint(xs, k, weights=None, reducedim=None, dim=-1, keepdim=False
     HIP kernels forward and backward (a wave per kept row, fp64 sums); first-order differentiable in xs and weights.  The reduced
     dimensions are moved to the front and xs is flattened to (reduced, kept, D) -- a copy only where the layout needs one; weights
     that broadcast against xs.shape[:-1] are expanded and materialised, which leaves the sum of their gradient to autograd."""
-    if k is not None and abs(float(k) + 1.0) > 1e-12:
-        raise NotImplementedError(f"weighted_midpoint: curvature k = {float(k)} is not implemented; {_MID_SUPPORTED}")
+    _refuse_k("weighted_midpoint", k, _MID_SUPPORTED)
     return _weighted_midpoint(xs, weights, reducedim, dim, keepdim, lincomb, posweight, coadd, _WeightedMidpoint.apply)
 
 
@@ -485,8 +488,7 @@ def dist_matmul(x, y, k):
     that is the transposed view of such a tensor is passed as it is, any other is copied once.  Both operands carry the same leading
     batch dimensions, or one of them carries none: that operand is expanded over the batch and materialised on the host, and the sum of
     its gradient over the batch is left to autograd (the expand's backward)."""
-    if k is not None and abs(float(k) + 1.0) > 1e-12:
-        raise NotImplementedError(f"dist_matmul: curvature k = {float(k)} is not implemented; {_DISTMM_SUPPORTED}")
+    _refuse_k("dist_matmul", k, _DISTMM_SUPPORTED)
     return _dist_matmul(x, y, _DistMatmul.apply)
 
 
@@ -567,8 +569,7 @@ def dist2plane_matmul(x, p, z, *, k):
     to the kernels as rows (..., M, D): a p or z that is the transposed view of such a tensor is passed as it is, any other is copied
     once.  x and the planes carry the same leading batch dimensions, or one side carries none: that side is expanded over the batch and
     materialised on the host, and the sum of its gradient over the batch is left to autograd (the expand's backward)."""
-    if k is not None and abs(float(k) + 1.0) > 1e-12:
-        raise NotImplementedError(f"dist2plane_matmul: curvature k = {float(k)} is not implemented; {_D2PMM_SUPPORTED}")
+    _refuse_k("dist2plane_matmul", k, _D2PMM_SUPPORTED)
     bx, bp = tuple(x.shape[:-2]), tuple(p.shape[:-2])
     if (x.dim() < 2 or p.dim() < 2 or p.shape != z.shape or p.shape[-2] != x.shape[-1] or (bx != bp and bx != () and bp != ())
             or x.dtype != torch.float32 or p.dtype != torch.float32 or z.dtype != torch.float32):
@@ -585,58 +586,11 @@ def dist2plane_matmul(x, p, z, *, k):
     return out.view(*lead, x.shape[-2], p.shape[-1])
 
 
-class _Dist(torch.autograd.Function):
-    """hypad_dist_*: the rows of x and y (rows, D) -> (rows)."""
-
-    @staticmethod
-    def forward(ctx, x, y):
-        x = _C.require_cuda(x.contiguous(), "x")
-        y = _C.require_cuda(y.contiguous(), "y")
-        rows, d = x.shape
-        out = torch.empty(rows, device=x.device, dtype=torch.float32)
-        _C.check(_C.lib.hypad_dist_fwd(_C.ptr(x), _C.ptr(y), _C.ptr(out), rows, d, _C.stream()), "dist_fwd")
-        ctx.save_for_backward(x, y)
-        return out
-
-    @staticmethod
-    @_C.first_order_only
-    def backward(ctx, go):
-        x, y = ctx.saved_tensors
-        go = go.to(torch.float32).contiguous()
-        gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        gy = torch.empty_like(y) if ctx.needs_input_grad[1] else None
-        _C.check(_C.lib.hypad_dist_bwd(_C.ptr(x), _C.ptr(y), _C.ptr(go), _C.ptr(gx), _C.ptr(gy), x.shape[0], x.shape[1], _C.stream()), "dist_bwd")
-        return gx, gy
-
-
-class _Dist0(torch.autograd.Function):
-    """hypad_dist0_*: the rows of x (rows, D) -> (rows)."""
-
-    @staticmethod
-    def forward(ctx, x):
-        x = _C.require_cuda(x.contiguous(), "x")
-        rows, d = x.shape
-        out = torch.empty(rows, device=x.device, dtype=torch.float32)
-        _C.check(_C.lib.hypad_dist0_fwd(_C.ptr(x), _C.ptr(out), rows, d, _C.stream()), "dist0_fwd")
-        ctx.save_for_backward(x)
-        return out
-
-    @staticmethod
-    @_C.first_order_only
-    def backward(ctx, go):
-        (x,) = ctx.saved_tensors
-        go = go.to(torch.float32).contiguous()
-        gx = torch.empty_like(x)
-        _C.check(_C.lib.hypad_dist0_bwd(_C.ptr(x), _C.ptr(go), _C.ptr(gx), x.shape[0], x.shape[1], _C.stream()), "dist0_bwd")
-        return gx
-
-
 _DIST_SUPPORTED = "supported: k = -1, dim = -1, fp32, x and y of the same shape (nothing is broadcast), rows of 1 to 256 elements"
 
 
 def _dist_refusals(what, x, k, dim):
-    if k is not None and abs(float(k) + 1.0) > 1e-12:
-        raise NotImplementedError(f"{what}: curvature k = {float(k)} is not implemented; {_DIST_SUPPORTED}")
+    _refuse_k(what, k, _DIST_SUPPORTED)
     if x.dim() < 1 or (dim != -1 and dim != x.dim() - 1):
         raise NotImplementedError(f"{what}: dim = {dim} on x {tuple(x.shape)} is not implemented; {_DIST_SUPPORTED}")
     if x.dtype != torch.float32 or x.shape[-1] > 256 or x.shape[-1] < 1:
@@ -650,17 +604,14 @@ def dist(x, y, *, k, keepdim=False, dim=-1):
     _dist_refusals("dist", x, k, dim)
     if y.shape != x.shape or y.dtype != torch.float32:
         raise NotImplementedError(f"dist: y {tuple(y.shape)} {y.dtype} against x {tuple(x.shape)} is not implemented; {_DIST_SUPPORTED}")
-    rows = _rows_width(x)[0]
-    out = _Dist.apply(x.reshape(rows, x.shape[-1]), y.reshape(rows, y.shape[-1]))
-    return out.view(*x.shape[:-1], 1) if keepdim else out.view(x.shape[:-1])
+    return _per_row(_RowScalar.apply("dist", None, x, y), keepdim)
 
 
 def dist0(x, *, k, keepdim=False, dim=-1):
     """The geodesic distance 2 artanh(|x|) of the rows of x from the origin (math_.py:950-975) at k = -1: one HIP launch forward and
     one backward; an all-zero row gets gradient 0."""
     _dist_refusals("dist0", x, k, dim)
-    out = _Dist0.apply(x.reshape(_rows_width(x)[0], x.shape[-1]))
-    return out.view(*x.shape[:-1], 1) if keepdim else out.view(x.shape[:-1])
+    return _per_row(_RowScalar.apply("dist0", None, x), keepdim)
 
 
 class _HyperbolicAttention(torch.autograd.Function):
@@ -730,8 +681,7 @@ def hyperbolic_attention(q, keys, values, k, beta=1.0, bias=None):
 
     One difference from the composition: a query whose every score is -inf (a fully masked row) gives the origin, an all-zero row, and
     adds nothing to any gradient; the composition returns NaN there."""
-    if k is not None and abs(float(k) + 1.0) > 1e-12:
-        raise NotImplementedError(f"hyperbolic_attention: curvature k = {float(k)} is not implemented; {_ATTN_SUPPORTED}")
+    _refuse_k("hyperbolic_attention", k, _ATTN_SUPPORTED)
     return _hyperbolic_attention(q, keys, values, beta, bias, _HyperbolicAttention.apply)
 
 
@@ -771,18 +721,24 @@ def _hyperbolic_attention(q, keys, values, beta, bias, apply):
     return out.view(*lead, n, e)
 
 
+def _row_call(name, direction, c, *args):
+    """hypad_<name>_<direction> (c given: hypad_ball_<name>_<direction>, with c before the stream) on the current stream."""
+    fn, cv, full = _entry(f"{name}_{direction}", c)
+    _C.check(fn(*args, *cv, _C.stream()), f"{name}_{direction}" if c is None else full)
+
+
 class _RowMap(torch.autograd.Function):
-    """hypad_<name>_fwd / _bwd for the tangent maps of two or three operands, all of one shape (..., D); saves the operands alone."""
+    """hypad_<name>_fwd / _bwd (c given: hypad_ball_<name>_*) for the maps of one to three operands, all of one shape (..., D); saves the
+    operands alone."""
 
     @staticmethod
-    def forward(ctx, name, *ops):
+    def forward(ctx, name, c, *ops):
         ops = [_C.require_cuda(t.contiguous(), f"{name}: operand {i}") for i, t in enumerate(ops)]
-        shape = ops[0].shape
         rows, d = _rows_width(ops[0])
-        out = torch.empty(shape, device=ops[0].device, dtype=torch.float32)
-        _C.check(getattr(_C.lib, f"hypad_{name}_fwd")(*map(_C.ptr, ops), _C.ptr(out), rows, d, _C.stream()), f"{name}_fwd")
+        out = torch.empty(ops[0].shape, device=ops[0].device, dtype=torch.float32)
+        _row_call(name, "fwd", c, *map(_C.ptr, ops), _C.ptr(out), rows, d)
         ctx.save_for_backward(*ops)
-        ctx.name = name
+        ctx.name, ctx.c = name, c
         return out
 
     @staticmethod
@@ -791,56 +747,52 @@ class _RowMap(torch.autograd.Function):
         ops = ctx.saved_tensors
         rows, d = _rows_width(ops[0])
         go = go.to(torch.float32).contiguous()
-        grads = [torch.empty_like(t) if need else None for t, need in zip(ops, ctx.needs_input_grad[1:])]
-        _C.check(getattr(_C.lib, f"hypad_{ctx.name}_bwd")(*map(_C.ptr, ops), _C.ptr(go), *map(_C.ptr, grads), rows, d, _C.stream()),
-                 f"{ctx.name}_bwd")
-        return (None, *grads)
+        grads = [torch.empty_like(t) if need else None for t, need in zip(ops, ctx.needs_input_grad[2:])]
+        _row_call(ctx.name, "bwd", ctx.c, *map(_C.ptr, ops), _C.ptr(go), *map(_C.ptr, grads), rows, d)
+        return (None, None, *grads)
 
 
 class _TimeRowMap(torch.autograd.Function):
-    """hypad_<name>_fwd / _bwd for geodesic and geodesic_unit: t of one element, or of one element per row of the two operands (..., D)."""
+    """hypad_<name>_fwd / _bwd (c given: hypad_ball_<name>_*) for geodesic, geodesic_unit (two row operands (..., D)) and the curved
+    mobius_scalar_mul (one): t of one element, or of one element per row."""
 
     @staticmethod
-    def forward(ctx, name, t, x, y):
-        x = _C.require_cuda(x.contiguous(), "x")
-        y = _C.require_cuda(y.contiguous(), f"{name}: the second row operand")
+    def forward(ctx, name, c, t, *ops):
+        ops = [_C.require_cuda(a.contiguous(), "x" if i == 0 else f"{name}: the second row operand") for i, a in enumerate(ops)]
         t1 = _C.require_cuda(t.contiguous().reshape(-1), "t")
-        rows, d = _rows_width(x)
-        out = torch.empty_like(x)
-        _C.check(getattr(_C.lib, f"hypad_{name}_fwd")(_C.ptr(t1), _C.ptr(x), _C.ptr(y), _C.ptr(out), rows, d, t1.shape[0], _C.stream()), f"{name}_fwd")
-        ctx.save_for_backward(t1, x, y)
-        ctx.name, ctx.ts = name, t.shape
+        rows, d = _rows_width(ops[0])
+        out = torch.empty_like(ops[0])
+        _row_call(name, "fwd", c, _C.ptr(t1), *map(_C.ptr, ops), _C.ptr(out), rows, d, t1.shape[0])
+        ctx.save_for_backward(t1, *ops)
+        ctx.name, ctx.c, ctx.ts = name, c, t.shape
         return out
 
     @staticmethod
     @_C.first_order_only
     def backward(ctx, go):
-        t1, x, y = ctx.saved_tensors
-        rows, d = _rows_width(x)
+        t1, *ops = ctx.saved_tensors
+        rows, d = _rows_width(ops[0])
         go = go.to(torch.float32).contiguous()
-        gt = torch.empty(rows, device=x.device, dtype=torch.float32) if ctx.needs_input_grad[1] else None
-        gx = torch.empty_like(x) if ctx.needs_input_grad[2] else None
-        gy = torch.empty_like(y) if ctx.needs_input_grad[3] else None
-        _C.check(getattr(_C.lib, f"hypad_{ctx.name}_bwd")(_C.ptr(t1), _C.ptr(x), _C.ptr(y), _C.ptr(go), _C.ptr(gt), _C.ptr(gx), _C.ptr(gy), rows, d,
-                                                          t1.shape[0], _C.stream()), f"{ctx.name}_bwd")
+        gt = torch.empty(rows, device=ops[0].device, dtype=torch.float32) if ctx.needs_input_grad[2] else None
+        grads = [torch.empty_like(a) if need else None for a, need in zip(ops, ctx.needs_input_grad[3:])]
+        _row_call(ctx.name, "bwd", ctx.c, _C.ptr(t1), *map(_C.ptr, ops), _C.ptr(go), _C.ptr(gt), *map(_C.ptr, grads), rows, d, t1.shape[0])
         if gt is not None and t1.shape[0] == 1 and rows != 1:   # one t for every row: the rows' contributions, added in a fixed order
-            red = torch.empty(1, device=x.device, dtype=torch.float32)
-            _C.check(_C.lib.hypad_column_sum(_C.ptr(gt), _C.ptr(red), rows, 1, _C.stream()))
-            gt = red
-        return None, None if gt is None else gt.view(ctx.ts), gx, gy
+            gt = _column_sum(gt.view(rows, 1))
+        return (None, None, None if gt is None else gt.view(ctx.ts), *grads)
 
 
 class _RowScalar(torch.autograd.Function):
-    """hypad_<name>_fwd / _bwd for lambda_x, norm and inner: one to three operands of one shape (..., D) -> (...), one value per row."""
+    """hypad_<name>_fwd / _bwd (c given: hypad_ball_<name>_*) for lambda_x, norm, inner, dist and dist0: one to three operands of one
+    shape (..., D) -> (...), one value per row."""
 
     @staticmethod
-    def forward(ctx, name, *ops):
+    def forward(ctx, name, c, *ops):
         ops = [_C.require_cuda(t.contiguous(), f"{name}: operand {i}") for i, t in enumerate(ops)]
         rows, d = _rows_width(ops[0])
         out = torch.empty(ops[0].shape[:-1], device=ops[0].device, dtype=torch.float32)
-        _C.check(getattr(_C.lib, f"hypad_{name}_fwd")(*map(_C.ptr, ops), _C.ptr(out), rows, d, _C.stream()), f"{name}_fwd")
+        _row_call(name, "fwd", c, *map(_C.ptr, ops), _C.ptr(out), rows, d)
         ctx.save_for_backward(*ops)
-        ctx.name = name
+        ctx.name, ctx.c = name, c
         return out
 
     @staticmethod
@@ -849,24 +801,24 @@ class _RowScalar(torch.autograd.Function):
         ops = ctx.saved_tensors
         rows, d = _rows_width(ops[0])
         go = go.to(torch.float32).contiguous()
-        grads = [torch.empty_like(t) if need else None for t, need in zip(ops, ctx.needs_input_grad[1:])]
-        _C.check(getattr(_C.lib, f"hypad_{ctx.name}_bwd")(*map(_C.ptr, ops), _C.ptr(go), *map(_C.ptr, grads), rows, d, _C.stream()),
-                 f"{ctx.name}_bwd")
-        return (None, *grads)
+        grads = [torch.empty_like(t) if need else None for t, need in zip(ops, ctx.needs_input_grad[2:])]
+        _row_call(ctx.name, "bwd", ctx.c, *map(_C.ptr, ops), _C.ptr(go), *map(_C.ptr, grads), rows, d)
+        return (None, None, *grads)
 
 
 class _Projection(torch.autograd.Function):
-    """hypad_sproj_* (grow = -1) and hypad_inv_sproj_* (grow = +1): a (..., W) -> (..., W + grow); the entry points take the ball's width."""
+    """hypad_sproj_* (grow = -1) and hypad_inv_sproj_* (grow = +1), or with c their hypad_ball_* forms: a (..., W) -> (..., W + grow); the
+    entry points take the ball's width."""
 
     @staticmethod
-    def forward(ctx, name, a, grow):
+    def forward(ctx, name, c, a, grow):
         a = _C.require_cuda(a.contiguous(), name)
         rows, w = _rows_width(a)
         ball = w if grow > 0 else w - 1
         out = torch.empty(*a.shape[:-1], w + grow, device=a.device, dtype=torch.float32)
-        _C.check(getattr(_C.lib, f"hypad_{name}_fwd")(_C.ptr(a), _C.ptr(out), rows, ball, _C.stream()), f"{name}_fwd")
+        _row_call(name, "fwd", c, _C.ptr(a), _C.ptr(out), rows, ball)
         ctx.save_for_backward(a)
-        ctx.name, ctx.ball = name, ball
+        ctx.name, ctx.c, ctx.ball = name, c, ball
         return out
 
     @staticmethod
@@ -875,8 +827,8 @@ class _Projection(torch.autograd.Function):
         (a,) = ctx.saved_tensors
         go = go.to(torch.float32).contiguous()
         ga = torch.empty_like(a)
-        _C.check(getattr(_C.lib, f"hypad_{ctx.name}_bwd")(_C.ptr(a), _C.ptr(go), _C.ptr(ga), _rows_width(a)[0], ctx.ball, _C.stream()), f"{ctx.name}_bwd")
-        return None, ga, None
+        _row_call(ctx.name, "bwd", ctx.c, _C.ptr(a), _C.ptr(go), _C.ptr(ga), _rows_width(a)[0], ctx.ball)
+        return None, None, ga, None
 
 
 _TANGENT_SUPPORTED = ("supported: k = -1, dim = -1, fp32, operands of the same last dimension whose leading dimensions broadcast against "
@@ -886,8 +838,7 @@ _TANGENT_SUPPORTED = ("supported: k = -1, dim = -1, fp32, operands of the same l
 def _tangent_operands(what, k, dim, **ops):
     """The operands of a tangent map, broadcast against each other by torch's rules (expanded views: a broadcast operand's gradient is
     summed by autograd, the expand's backward); every refusal comes before any device call."""
-    if k is not None and abs(float(k) + 1.0) > 1e-12:
-        raise NotImplementedError(f"{what}: curvature k = {float(k)} is not implemented; {_TANGENT_SUPPORTED}")
+    _refuse_k(what, k, _TANGENT_SUPPORTED)
     desc = ", ".join(f"{n} {tuple(t.shape)} {t.dtype}" for n, t in ops.items())
     ts = list(ops.values())
     if any(t.dim() < 1 or t.dtype != torch.float32 or t.shape[-1] != ts[0].shape[-1] for t in ts) or not 1 <= ts[0].shape[-1] <= 256:
@@ -920,7 +871,7 @@ def expmap(x, u, *, k, dim=-1):
     """The exponential map at x: the point reached from x along the tangent vector u, x (+) (tanh(lambda_x |u| / 2) u / |u|)
     (math_.py:1052-1102) at k = -1.  One HIP launch forward and one backward, a wave per row in fp64 registers; first-order
     differentiable in x and u, which are broadcast against each other."""
-    return _RowMap.apply("expmap", *_tangent_operands("expmap", k, dim, x=x, u=u))
+    return _RowMap.apply("expmap", None, *_tangent_operands("expmap", k, dim, x=x, u=u))
 
 
 def logmap(x, y, *, k, dim=-1):
@@ -931,7 +882,7 @@ def logmap(x, y, *, k, dim=-1):
     The one deliberate difference from the reference: artanh is 0.5 (log1p(n) - log1p(-n)), so at coincident or near-coincident points
     the result and its gradient follow the analytic limit artanh(n) / n -> 1, where the reference's fp32 run -- a difference of two
     logarithms -- returns a gradient of exactly 0.  There is no singularity at x == y and no special case for it."""
-    return _RowMap.apply("logmap", *_tangent_operands("logmap", k, dim, x=x, y=y))
+    return _RowMap.apply("logmap", None, *_tangent_operands("logmap", k, dim, x=x, y=y))
 
 
 def geodesic(t, x, y, *, k, dim=-1):
@@ -942,51 +893,51 @@ def geodesic(t, x, y, *, k, dim=-1):
     As in logmap, artanh is the log1p form: at coincident or near-coincident x and y the result and its gradients follow the analytic
     limit, where the reference's fp32 run returns a gradient of exactly 0."""
     x, y = _tangent_operands("geodesic", k, dim, x=x, y=y)
-    return _TimeRowMap.apply("geodesic", *_time_operand("geodesic", t, x), y)
+    return _TimeRowMap.apply("geodesic", None, *_time_operand("geodesic", t, x), y)
 
 
 def gyration(a, b, u, *, k, dim=-1):
     """The gyration gyr[a, b] u = -(a (+) b) (+) (a (+) (b (+) u)) in its closed form (math_.py:592-675) at k = -1.  One HIP launch
     forward and one backward; first-order differentiable in a, b and u, which are broadcast against each other."""
-    return _RowMap.apply("gyration", *_tangent_operands("gyration", k, dim, a=a, b=b, u=u))
+    return _RowMap.apply("gyration", None, *_tangent_operands("gyration", k, dim, a=a, b=b, u=u))
 
 
 def parallel_transport(x, y, v, *, k, dim=-1):
     """The parallel transport of the tangent vector v from x to y along their geodesic, gyr[y, -x] v lambda_x / lambda_y
     (math_.py:1669-1746) at k = -1.  One HIP launch forward and one backward; first-order differentiable in x, y and v, which are
     broadcast against each other."""
-    return _RowMap.apply("parallel_transport", *_tangent_operands("parallel_transport", k, dim, x=x, y=y, v=v))
+    return _RowMap.apply("parallel_transport", None, *_tangent_operands("parallel_transport", k, dim, x=x, y=y, v=v))
 
 
 def parallel_transport0(y, v, *, k, dim=-1):
     """The parallel transport of v from the origin to y, v (1 - |y|^2) (math_.py:1749-1779) at k = -1.  One HIP launch forward and one
     backward; first-order differentiable in y and v, which are broadcast against each other."""
-    return _RowMap.apply("parallel_transport0", *_tangent_operands("parallel_transport0", k, dim, y=y, v=v))
+    return _RowMap.apply("parallel_transport0", None, *_tangent_operands("parallel_transport0", k, dim, y=y, v=v))
 
 
 def parallel_transport0back(x, v, *, k, dim=-1):
     """The parallel transport of v from x to the origin, v / (1 - |x|^2) (math_.py:1782-1813) at k = -1.  One HIP launch forward and one
     backward; first-order differentiable in x and v, which are broadcast against each other."""
-    return _RowMap.apply("parallel_transport0back", *_tangent_operands("parallel_transport0back", k, dim, x=x, v=v))
+    return _RowMap.apply("parallel_transport0back", None, *_tangent_operands("parallel_transport0back", k, dim, x=x, v=v))
 
 
 def mobius_sub(x, y, *, k, dim=-1):
     """The Moebius subtraction x (+) (-y) (math_.py:558-589) at k = -1.  One HIP launch forward and one backward; first-order
     differentiable in x and y, which are broadcast against each other."""
-    return _RowMap.apply("mobius_sub", *_tangent_operands("mobius_sub", k, dim, x=x, y=y))
+    return _RowMap.apply("mobius_sub", None, *_tangent_operands("mobius_sub", k, dim, x=x, y=y))
 
 
 def mobius_coadd(x, y, *, k, dim=-1):
     """The Moebius coaddition ((1 - |y|^2) x + (1 - |x|^2) y) / (1 - |x|^2 |y|^2), the commutative sum of the gyrogroup
     (math_.py:678-744) at k = -1.  One HIP launch forward and one backward; first-order differentiable in x and y, which are broadcast
     against each other."""
-    return _RowMap.apply("mobius_coadd", *_tangent_operands("mobius_coadd", k, dim, x=x, y=y))
+    return _RowMap.apply("mobius_coadd", None, *_tangent_operands("mobius_coadd", k, dim, x=x, y=y))
 
 
 def mobius_cosub(x, y, *, k, dim=-1):
     """The Moebius cosubtraction mobius_coadd(x, -y) (math_.py:747-779) at k = -1: ``mobius_cosub(mobius_add(x, y), y) = x``.  One HIP
     launch forward and one backward; first-order differentiable in x and y, which are broadcast against each other."""
-    return _RowMap.apply("mobius_cosub", *_tangent_operands("mobius_cosub", k, dim, x=x, y=y))
+    return _RowMap.apply("mobius_cosub", None, *_tangent_operands("mobius_cosub", k, dim, x=x, y=y))
 
 
 def geodesic_unit(t, x, u, *, k, dim=-1):
@@ -995,7 +946,7 @@ def geodesic_unit(t, x, u, *, k, dim=-1):
     broadcast against each other; t is a number, a tensor of one element, or holds one value per row, shape x.shape[:-1] + (1,) after
     that broadcast."""
     x, u = _tangent_operands("geodesic_unit", k, dim, x=x, u=u)
-    return _TimeRowMap.apply("geodesic_unit", *_time_operand("geodesic_unit", t, x), u)
+    return _TimeRowMap.apply("geodesic_unit", None, *_time_operand("geodesic_unit", t, x), u)
 
 
 def _per_row(out, keepdim):
@@ -1005,7 +956,7 @@ def _per_row(out, keepdim):
 def lambda_x(x, *, k, keepdim=False, dim=-1):
     """The conformal factor lambda_x = 2 / (1 - |x|^2) of the rows of x (math_.py:355-383) at k = -1 -> x.shape[:-1], or
     x.shape[:-1] + (1,) with keepdim.  One HIP launch forward and one backward."""
-    return _per_row(_RowScalar.apply("lambda_x", *_tangent_operands("lambda_x", k, dim, x=x)), keepdim)
+    return _per_row(_RowScalar.apply("lambda_x", None, *_tangent_operands("lambda_x", k, dim, x=x)), keepdim)
 
 
 def inner(x, u, v, *, k, keepdim=False, dim=-1):
@@ -1015,21 +966,21 @@ def inner(x, u, v, *, k, keepdim=False, dim=-1):
     One deliberate difference from the reference: with keepdim=False the result has the shape x.shape[:-1] (after the broadcast), as
     lambda_x, norm and dist have.  The reference multiplies lambda_x^2 of shape (..., 1) with a sum of shape (...), which broadcasts the
     rows against each other: (33, 5) operands give (33, 33) there.  With keepdim=True the two agree."""
-    return _per_row(_RowScalar.apply("inner", *_tangent_operands("inner", k, dim, x=x, u=u, v=v)), keepdim)
+    return _per_row(_RowScalar.apply("inner", None, *_tangent_operands("inner", k, dim, x=x, u=u, v=v)), keepdim)
 
 
 def norm(x, u, *, k, keepdim=False, dim=-1):
     """The Riemannian norm lambda_x |u| of the tangent vector u at x (math_.py:433-472) at k = -1, one value per row.  One HIP launch
     forward and one backward; first-order differentiable in x and u, which are broadcast against each other; a zero tangent gets
     gradient 0."""
-    return _per_row(_RowScalar.apply("norm", *_tangent_operands("norm", k, dim, x=x, u=u)), keepdim)
+    return _per_row(_RowScalar.apply("norm", None, *_tangent_operands("norm", k, dim, x=x, u=u)), keepdim)
 
 
 def egrad2rgrad(x, grad, *, k, dim=-1):
     """The Riemannian gradient at x of a function whose Euclidean gradient there is ``grad``: grad / lambda_x^2 (math_.py:1816-1845) at
     k = -1.  ``p <- expmap(p, -lr * egrad2rgrad(p, p.grad))`` is one step of Riemannian gradient descent.  One HIP launch forward and one
     backward; first-order differentiable in x and grad, which are broadcast against each other."""
-    return _RowMap.apply("egrad2rgrad", *_tangent_operands("egrad2rgrad", k, dim, x=x, grad=grad))
+    return _RowMap.apply("egrad2rgrad", None, *_tangent_operands("egrad2rgrad", k, dim, x=x, grad=grad))
 
 
 _PROJ_SUPPORTED = ("supported: k = -1, dim = -1, fp32, a ball side of 1 to 255 elements a row (the hyperboloid side, one more, of 2 to 256), fewer "
@@ -1037,8 +988,7 @@ _PROJ_SUPPORTED = ("supported: k = -1, dim = -1, fp32, a ball side of 1 to 255 e
 
 
 def _projection_refusals(what, a, k, dim, grow):
-    if k is not None and abs(float(k) + 1.0) > 1e-12:
-        raise NotImplementedError(f"{what}: curvature k = {float(k)} is not implemented; {_PROJ_SUPPORTED}")
+    _refuse_k(what, k, _PROJ_SUPPORTED)
     if a.dim() < 1 or (dim != -1 and dim != a.dim() - 1):
         raise NotImplementedError(f"{what}: dim = {dim} on {tuple(a.shape)} is not implemented; {_PROJ_SUPPORTED}")
     rows, wide = _rows_width(a)[0], a.shape[-1] + max(grow, 0)            # the hyperboloid side
@@ -1051,20 +1001,19 @@ def sproj(x, *, k, dim=-1):
     x[..., :D] / (1 + x[..., D]) (math_.py:1848-1874) at k = -1, where the reference's inv_r = sqrt(|k| + 1e-15) is 1.  No clamp, as in the
     reference.  One HIP launch forward and one backward."""
     _projection_refusals("sproj", x, k, dim, -1)
-    return _Projection.apply("sproj", x, -1)
+    return _Projection.apply("sproj", None, x, -1)
 
 
 def inv_sproj(x, *, k, dim=-1):
     """The inverse stereographic projection of ball points x (..., D) onto the hyperboloid: cat(lambda_x x, lambda_x - 1), shape
     (..., D + 1) (math_.py:1877-1905) at k = -1.  One HIP launch forward and one backward."""
     _projection_refusals("inv_sproj", x, k, dim, 1)
-    return _Projection.apply("inv_sproj", x, 1)
+    return _Projection.apply("inv_sproj", None, x, 1)
 
 
 def antipode(x, *, k, dim=-1):
     """The antipode of x (math_.py:1908-1950): -x for every k <= 0, as the reference returns.  No kernel."""
-    if k is not None and abs(float(k) + 1.0) > 1e-12:
-        raise NotImplementedError(f"antipode: curvature k = {float(k)} is not implemented; supported: k = -1")
+    _refuse_k("antipode", k, "supported: k = -1")
     return -x
 
 
@@ -1160,8 +1109,7 @@ def dist2plane(x, p, a, *, k=None, keepdim=False, signed=False, scaled=False, di
     """Geodesic distance of x to the hyperplanes through p with normals a (math_.py:1599-1666) at k = -1, for the layer's calling
     pattern: x (..., 1, K) against p, a (N, K) -> (..., N), or (..., N, 1) with keepdim.  One HIP launch forward; first-order
     differentiable in x, p and a.  A floating x of any dtype is cast to fp32; p and a are fp32, and so is the result."""
-    if k is not None and abs(float(k) + 1.0) > 1e-12:
-        raise NotImplementedError(f"dist2plane: curvature k = {float(k)} is not implemented; {_D2P_SUPPORTED}")
+    _refuse_k("dist2plane", k, _D2P_SUPPORTED)
     if dim != -1 and dim != x.dim() - 1:
         raise NotImplementedError(f"dist2plane: dim = {dim} is not implemented; {_D2P_SUPPORTED}")
     if (p.dim() != 2 or a.shape != p.shape or x.dim() < 2 or x.shape[-2] != 1 or x.shape[-1] != p.shape[-1]):
